@@ -784,6 +784,103 @@ class ReshapeGroupFn(Function):
         return (None, None, None, None, *dxs, *grads)
 
 
+# ---------------------------------------------------------------- mixed-edge sum with FC primitives
+FC_KINDS = {'fc_relu': 0, 'fc_mish': 1}
+
+
+class FcEdgeSumFn(Function):
+    """out = sum_j sum_p w[j, p] OPS[prims[p]](x_j) over n states (FusionCell.forward model_search.py:58 /
+    NodeCell.forward node_search.py:54 with FusionMixedOp.forward operations.py:104-105) when `prims` — the
+    participating primitives, one per column of the weight rows `w` (n, P) — holds one or two of fc_relu / fc_mish
+    (operations.py:22-38, 48-65) next to none / skip: three launches forward (zero-fill of the BatchNorm batch sums —
+    training only —, grouped GEMM, finalise + weighted sum), four backward (zero-fill, reductions, dU, grouped
+    GEMMs), whatever n is.  tensors: the n states, then per edge and FC primitive (list order) linear.weight,
+    linear.bias, bn.weight, bn.bias; buffers[j][f] = (running_mean, running_var, num_batches_tracked), updated in
+    place in training mode.  One dropout site per (edge, FC primitive), edge by edge, primitives in list order.
+    States that are the same tensor object share one gradient (returned for the first of them).
+    The pre-activations stay reachable as `out.grad_fn.fc_U` (n, b, F*C, L)."""
+
+    @staticmethod
+    def forward(ctx, n, prims, training, p, buffers, w, *tensors):
+        xs_in = tensors[:n]
+        _require_gpu(xs_in[0], 'mixed-edge sum with FC primitives')
+        xs = [_c(_f32(t)) for t in xs_in]
+        fcols = [c for c, name in enumerate(prims) if name in FC_KINDS]
+        F, P = len(fcols), len(prims)
+        skip_cols = sum(1 << c for c, name in enumerate(prims) if name == 'skip')
+        if any(name not in FC_KINDS and name not in ('none', 'skip') for name in prims):
+            raise ValueError(f'FcEdgeSumFn: unknown primitive in {prims}')
+        b, Cc, L = xs[0].shape
+        w = _c(_f32(w))
+        if tuple(w.shape) != (n, P) or not lib.fc_edges_ok(n, F, P, b, Cc, L):
+            raise lib.BmnasError(f'FcEdgeSumFn: unsupported sum (n={n}, prims={prims}, w {tuple(w.shape)}, '
+                                 f'x {tuple(xs[0].shape)})')
+        if training and b * L < 2:
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {[b, Cc, L]}')
+        dev = xs[0].device
+        prm = [[[_c(_f32(t)) for t in tensors[n + 4 * (j * F + f):n + 4 * (j * F + f) + 4]] for f in range(F)]
+               for j in range(n)]
+        U = torch.empty((n, b, F * Cc, L), device=dev, dtype=torch.float32)
+        chan = torch.empty((n, F, 4 * Cc), device=dev, dtype=torch.float32)
+        stat = None
+        if training:
+            adv = K.DROP.take_advance() if p > 0.0 else None
+            stat = torch.empty((n, F, 2 * Cc), device=dev, dtype=torch.float32)
+            lib.fc_edges_zero(stat.view(-1), 'fwd', adv)
+        drops = [[K.DROP.make(p, b * Cc * L, training) for _ in range(F)] for _ in range(n)]
+        edges = [dict(x=xs[j], U=U[j],
+                      fc=[dict(W=prm[j][f][0], bias=prm[j][f][1], bn_w=prm[j][f][2], bn_b=prm[j][f][3],
+                               running_mean=buffers[j][f][0], running_var=buffers[j][f][1],
+                               num_batches_tracked=buffers[j][f][2], stat=None if stat is None else stat[j, f],
+                               chan=chan[j, f], drop=drops[j][f], col=fcols[f], mish=FC_KINDS[prims[fcols[f]]])
+                          for f in range(F)]) for j in range(n)]
+        arr = lib.make_fc_edges(edges)
+        lib.fc_edges_gemm_fwd(arr, F, training, b, Cc, L)
+        out = torch.empty_like(xs[0])
+        lib.fc_edges_mix_fwd(arr, F, w, P, skip_cols, training, out, b, Cc, L)
+        # which states are one tensor object: they share a gradient buffer (NodeCell's states = [sif, sif])
+        first = [next(i for i in range(j + 1) if xs_in[i] is xs_in[j]) for j in range(n)]
+        ctx.n, ctx.F, ctx.P, ctx.skip_cols, ctx.training = n, F, P, skip_cols, training
+        ctx.edges, ctx.w, ctx.first, ctx.fc_U, ctx.fc_chan, ctx.fc_drops = edges, w, first, U, chan, drops
+        ctx.wshapes = [[tuple(t.shape) for t in tensors[n + 4 * (j * F + f):n + 4 * (j * F + f) + 2]]
+                       for j in range(n) for f in range(F)]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n, F, P, edges, w = ctx.n, ctx.F, ctx.P, ctx.edges, ctx.w
+        g = _c(g)
+        b, Cc, L = g.shape
+        dev = g.device
+        per = 2 * Cc + Cc * Cc + Cc                    # bn_grad | dW | dbias of one (edge, FC primitive)
+        head = (n * P + 3) // 4 * 4
+        pool = torch.empty(head + n * F * per, device=dev, dtype=torch.float32)
+        lib.fc_edges_zero(pool, 'bwd')
+        dw = pool[:n * P].view(n, P)
+        dU = torch.empty_like(ctx.fc_U)
+        grads = []
+        for j in range(n):
+            edges[j]['dU'] = dU[j]
+            for f in range(F):
+                o = head + (j * F + f) * per
+                q = edges[j]['fc'][f]
+                q['bn_grad'], q['dW'], q['dbias'] = pool[o:o + 2 * Cc], pool[o + 2 * Cc:o + 2 * Cc + Cc * Cc], \
+                    pool[o + 2 * Cc + Cc * Cc:o + per]
+                ws, bs = ctx.wshapes[j * F + f]
+                grads += [q['dW'].view(ws), q['dbias'].view(bs), q['bn_grad'][:Cc], q['bn_grad'][Cc:]]
+        arr = lib.make_fc_edges(edges)
+        lib.fc_edges_bwd_reduce(arr, F, w, P, ctx.skip_cols, g, dw, b, Cc, L)
+        lib.fc_edges_bwd_du(arr, F, w, P, g, ctx.training, b, Cc, L)
+        dxs, targets, masks = [None] * n, [], []
+        for j in range(n):
+            if ctx.first[j] == j and ctx.needs_input_grad[6 + j]:
+                dxs[j] = torch.empty_like(g)
+                targets.append(dxs[j])
+                masks.append(sum(1 << i for i in range(n) if ctx.first[i] == j))
+        lib.fc_edges_bwd_gemm(arr, F, w, P, ctx.skip_cols, g, targets, masks, b, Cc, L)
+        return (None, None, None, None, None, dw, *dxs, *grads)
+
+
 # ---------------------------------------------------------------- search NodeMixedOp
 class NodeMixedFn(Function):
     """NodeMixedOp.forward(x, y, weights) (node_operations.py:118-120) as one fused

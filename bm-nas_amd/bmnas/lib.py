@@ -102,6 +102,22 @@ class ConvBwdProb(C.Structure):
                 ('accumulate', C.c_int)]
 
 
+class FcPrim(C.Structure):
+    """bmnas_fc_prim_t"""
+    _fields_ = [('W', C.c_void_p), ('bias', C.c_void_p), ('bn_w', C.c_void_p), ('bn_b', C.c_void_p),
+                ('running_mean', C.c_void_p), ('running_var', C.c_void_p), ('num_batches_tracked', C.c_void_p),
+                ('stat', C.c_void_p), ('chan', C.c_void_p), ('dW', C.c_void_p), ('dbias', C.c_void_p),
+                ('bn_grad', C.c_void_p), ('drop', Dropout), ('col', C.c_int), ('mish', C.c_int)]
+
+
+class FcEdge(C.Structure):
+    """bmnas_fc_edge_t"""
+    _fields_ = [('x', C.c_void_p), ('U', C.c_void_p), ('dU', C.c_void_p), ('fc', FcPrim * 2)]
+
+
+FC_MAX_EDGES = 15
+
+
 def make_bn_fin(stat, shards, conv_bias, bn_w, bn_b, rm, rv, nbt, training):
     """Descriptor for in-kernel BatchNorm finalisation (bmnas_bn_fin_t): the consumer of a conv output
     derives scale / shift from the atomically accumulated batch sums `stat` (training) or from the
@@ -238,6 +254,13 @@ SIGNATURES = {
                                   _P, _P, _I64, _PP, _I, _P, _P, _P, _P, _I64, _P], _I),
     'bmnas_arch_softmax_multi': ([_PP, _PP, _PP, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I64,
                                  _P], _I),
+    'bmnas_fc_edges_ok': ([_I, _I, _I, _I, _I, _I], _I),
+    'bmnas_fc_edges_gemm_fwd': ([C.POINTER(FcEdge), _I, _I, _I, _I, _I, _I, _P], _I),
+    'bmnas_fc_edges_mix_fwd': ([C.POINTER(FcEdge), _I, _I, _P, _I, _U32, _I, _P, _I, _I, _I, _P], _I),
+    'bmnas_fc_edges_bwd_reduce': ([C.POINTER(FcEdge), _I, _I, _P, _I, _U32, _P, _P, _I, _I, _I, _P], _I),
+    'bmnas_fc_edges_bwd_du': ([C.POINTER(FcEdge), _I, _I, _P, _I, _P, _I, _I, _I, _I, _P], _I),
+    'bmnas_fc_edges_bwd_gemm': ([C.POINTER(FcEdge), _I, _I, _P, _I, _U32, _P, _PP, C.POINTER(C.c_uint32), _I, _I,
+                                 _I, _I, _P], _I),
 }
 
 _lib = None
@@ -1168,3 +1191,65 @@ def _timed(name, fn):
     wrapper.__name__ = name
     wrapper.__doc__ = fn.__doc__
     return wrapper
+
+
+# ------------------------------------------------------------- mixed-edge sums with FC primitives (csrc/fcedge.hip)
+FC_EDGE_LAUNCHES = {'fwd': 0, 'bwd': 0}      # launches issued by the wrappers below (tests/test_fc_edges_gpu.py)
+
+
+def fc_edges_ok(n, F, P, b, Cc, L):
+    """Whether the grouped FC-edge kernels take this mixed-edge sum (bmnas_fc_edges_ok)."""
+    return bool(load().bmnas_fc_edges_ok(int(n), int(F), int(P), int(b), int(Cc), int(L)))
+
+
+def fc_edges_zero(pool, direction, step=None):
+    """Zero-fill of the accumulation buffers of one direction ('fwd' | 'bwd'): the scrub job of bmnas_cell_prologue,
+    which under hipGraph capture also carries the dropout step counter's advance."""
+    cell_prologue([], [], [], [], 4, 4, step, pool)
+    FC_EDGE_LAUNCHES[direction] += 1
+
+
+def make_fc_edges(edges):
+    """edges: per edge a dict x, U, dU (optional) and fc = list of dicts with the bmnas_fc_prim_t fields (tensors
+    or None; drop a Dropout; col, mish ints).  Returns the ctypes array (keep the tensors alive)."""
+    p = lambda t: None if t is None else t.data_ptr()
+    arr = (FcEdge * len(edges))()
+    for j, e in enumerate(edges):
+        arr[j].x, arr[j].U, arr[j].dU = _ptr(e['x']), _ptr(e['U']), p(e.get('dU'))
+        for f, q in enumerate(e['fc']):
+            arr[j].fc[f] = FcPrim(_ptr(q['W']), _ptr(q['bias']), _ptr(q['bn_w']), _ptr(q['bn_b']),
+                                  p(q.get('running_mean')), p(q.get('running_var')),
+                                  p(q.get('num_batches_tracked')), p(q.get('stat')), _ptr(q['chan']), p(q.get('dW')),
+                                  p(q.get('dbias')), p(q.get('bn_grad')), q.get('drop', NO_DROP), int(q['col']),
+                                  int(q['mish']))
+    return arr
+
+
+def fc_edges_gemm_fwd(arr, F, training, b, Cc, L):
+    _check(load().bmnas_fc_edges_gemm_fwd(arr, len(arr), F, int(training), b, Cc, L, _stream()), 'fc_edges_gemm_fwd')
+    FC_EDGE_LAUNCHES['fwd'] += 1
+
+
+def fc_edges_mix_fwd(arr, F, w, P, skip_cols, training, out, b, Cc, L):
+    _check(load().bmnas_fc_edges_mix_fwd(arr, len(arr), F, _ptr(w), P, skip_cols, int(training), _ptr(out), b, Cc, L,
+                                         _stream()), 'fc_edges_mix_fwd')
+    FC_EDGE_LAUNCHES['fwd'] += 1
+
+
+def fc_edges_bwd_reduce(arr, F, w, P, skip_cols, g, dw, b, Cc, L):
+    _check(load().bmnas_fc_edges_bwd_reduce(arr, len(arr), F, _ptr(w), P, skip_cols, _ptr(g), _ptr(dw), b, Cc, L,
+                                            _stream()), 'fc_edges_bwd_reduce')
+    FC_EDGE_LAUNCHES['bwd'] += 1
+
+
+def fc_edges_bwd_du(arr, F, w, P, g, training, b, Cc, L):
+    _check(load().bmnas_fc_edges_bwd_du(arr, len(arr), F, _ptr(w), P, _ptr(g), int(training), b, Cc, L, _stream()),
+           'fc_edges_bwd_du')
+    FC_EDGE_LAUNCHES['bwd'] += 1
+
+
+def fc_edges_bwd_gemm(arr, F, w, P, skip_cols, g, dxs, dx_edges, b, Cc, L):
+    masks = (C.c_uint32 * max(1, len(dx_edges)))(*[int(m) for m in dx_edges])
+    _check(load().bmnas_fc_edges_bwd_gemm(arr, len(arr), F, _ptr(w), P, skip_cols, _ptr(g), _ptrs(dxs), masks,
+                                          len(dxs), b, Cc, L, _stream()), 'fc_edges_bwd_gemm')
+    FC_EDGE_LAUNCHES['bwd'] += 1

@@ -13,7 +13,7 @@ from bmnas.functions import CatLnFn, FusedCellFn, arch_softmax
 
 from .genotypes import PRIMITIVES, Genotype
 from .node_search import FusionNode
-from .operations import FusionMixedOp, mixed_edge_sum
+from .operations import FusionMixedOp, general_edge_sum, mixed_edge_sum
 
 
 class FusionCell(nn.Module):
@@ -120,13 +120,13 @@ class FusionCell(nn.Module):
             return out if classifier is None else classifier(out)
         if weights_are_logits:
             w = arch_softmax(w, dev)
-        # edited primitive lists: same dataflow, composed op by op
+        # edited primitive lists: same dataflow, one autograd node per mixed-edge sum / step node
         offset = 0
         for i in range(self._steps):
             if self._fusable:
                 sif = mixed_edge_sum(states, w, offset)
             else:
-                sif = sum(self._ops[offset + j](h, w[offset + j]) for j, h in enumerate(states))
+                sif = general_edge_sum(self._ops, states, w, offset)
             s = self._step_nodes[i](sif, sif)
             offset += len(states)
             states.append(s)

@@ -12,7 +12,7 @@ from bmnas.functions import CatLnFn, ConvBnActFn, arch_softmax
 
 from .genotypes import PRIMITIVES, STEP_EDGE_PRIMITIVES, STEP_STEP_PRIMITIVES, StepGenotype
 from .node_operations import NodeMixedOp
-from .operations import FusionMixedOp, mixed_edge_sum
+from .operations import FusionMixedOp, general_edge_sum, mixed_edge_sum
 
 
 class NodeCell(nn.Module):
@@ -94,9 +94,9 @@ class NodeCell(nn.Module):
                 z = mixed_edge_sum(states, edge_weights, offset)
             else:
                 # an edited PRIMITIVES list reaches the inner edges too (they are FusionMixedOps,
-                # reference node_search.py:31): composed op by op; zip() inside FusionMixedOp stops
-                # at the len(STEP_EDGE_PRIMITIVES) weights of the row, like the reference's
-                z = sum(self.edge_ops[offset + j](h, edge_weights[offset + j]) for j, h in enumerate(states))
+                # reference node_search.py:31); zip() inside FusionMixedOp stops at the
+                # len(STEP_EDGE_PRIMITIVES) weights of the row (operations.participating_primitives)
+                z = general_edge_sum(self.edge_ops, states, edge_weights, offset)
             s = self.node_ops[i](z, z, node_weights[i])
             offset += len(states)
             states.append(s)

@@ -4,13 +4,16 @@ Mirror of the reference's models/search/darts/operations.py (OPS :7-12, Zero :14
 FC_Relu :22-38, FC_Mish :48-65, Identity :88-93, FusionMixedOp :95-105) on the gfx950
 kernels: with the default PRIMITIVES ['none', 'skip'] the mixed edge is the HIP mixsum
 kernel (bmnas_mixsum_fwd/bwd).  FC_Relu / FC_Mish are not in the default search space
-(SURVEY.md a14); they stay ordinary PyTorch modules so an edited PRIMITIVES list works.
+(SURVEY.md a14): they stay ordinary PyTorch modules (same state_dict keys, usable alone), and the
+sum over the incoming edges of a cell / node step runs them on the grouped kernels of
+csrc/fcedge.hip (bmnas.functions.FcEdgeSumFn) — general_edge_sum below.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from bmnas.functions import MixSumFn
+from bmnas import lib
+from bmnas.functions import FC_KINDS, FcEdgeSumFn, MixSumFn
 
 from .genotypes import *  # noqa: F401,F403
 from .genotypes import PRIMITIVES
@@ -75,7 +78,8 @@ class FusionMixedOp(nn.Module):
     def __init__(self, C, L, args):
         super().__init__()
         self._ops = nn.ModuleList(OPS[p](C, L, args) for p in PRIMITIVES)
-        self._default = list(PRIMITIVES) == ['none', 'skip']
+        self._prims = list(PRIMITIVES)
+        self._default = self._prims == ['none', 'skip']
 
     def forward(self, x, weights):
         if self._default:
@@ -91,3 +95,75 @@ def mixed_edge_sum(states, weights, offset):
     n = len(states)
     w = weights if weights.device == states[0].device else weights.to(states[0].device)
     return MixSumFn.apply(w[offset:offset + n, 1], *states)
+
+
+FC_EDGES_NATIVE = True      # False: general_edge_sum always composes (A/B timing, tests of the fallback)
+_BUILTIN = {'none': Zero, 'skip': Identity, 'fc_relu': FC_Relu, 'fc_mish': FC_Mish}
+
+
+def participating_primitives(primitives, n_cols):
+    """The primitives a FusionMixedOp evaluates for a weight row of n_cols columns: `zip(weights, self._ops)`
+    (reference operations.py:105) stops at the shorter sequence, so a NodeCell's inner rows — always
+    len(STEP_EDGE_PRIMITIVES) = 2 columns — reach only the first two entries of an edited PRIMITIVES list."""
+    return list(primitives[:n_cols])
+
+
+def _composed_edge_sum(ops, states, weights, offset):
+    return sum(ops[offset + j](h, weights[offset + j]) for j, h in enumerate(states))
+
+
+def edge_sum_route(ops, states, weights, offset):
+    """How general_edge_sum evaluates this sum: 'fc' (FcEdgeSumFn), 'mixsum' (no FC primitive takes part: the K1
+    kernel over the skip column) or 'composed' (op by op — primitives registered by a user, shapes outside the
+    kernels' limits, CPU tensors)."""
+    n = len(states)
+    mods = [ops[offset + j] for j in range(n)]
+    x = states[0]
+    if not (FC_EDGES_NATIVE and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and weights.dim() == 2
+            and all(h.shape == x.shape for h in states)):
+        return 'composed', None
+    prims = participating_primitives(mods[0]._prims, weights.shape[-1])
+    for m in mods:
+        if m._prims != mods[0]._prims or len(m._ops) != len(m._prims):
+            return 'composed', None
+        # the registry may have been edited: only the four built-in classes have kernels
+        if any(name not in _BUILTIN or type(op) is not _BUILTIN[name] for name, op in zip(prims, m._ops)):
+            return 'composed', None
+    F = sum(name in FC_KINDS for name in prims)
+    if F == 0:
+        return ('mixsum', prims) if prims.count('skip') == 1 else ('composed', None)
+    fcs = [op for m in mods for name, op in zip(prims, m._ops) if name in FC_KINDS]
+    same_mode = all(op.training == fcs[0].training and op.bn.training == fcs[0].training
+                    and op.dropout.training == fcs[0].training
+                    and op.dropout.p == fcs[0].dropout.p and op.bn.track_running_stats
+                    and op.bn.momentum == 0.1 and op.bn.eps == 1e-5 and op.bn.affine for op in fcs)
+    b, Cc, L = x.shape
+    if not same_mode or not lib.fc_edges_ok(n, F, len(prims), b, Cc, L):
+        return 'composed', None
+    return 'fc', prims
+
+
+def general_edge_sum(ops, states, weights, offset):
+    """sum_j ops[offset + j](states[j], weights[offset + j]) for FusionMixedOps built from an edited PRIMITIVES
+    list (reference model_search.py:58 / node_search.py:54)."""
+    route, prims = edge_sum_route(ops, states, weights, offset)
+    if route == 'composed':
+        return _composed_edge_sum(ops, states, weights, offset)
+    n = len(states)
+    w = weights if weights.device == states[0].device else weights.to(states[0].device)
+    if route == 'mixsum':
+        return MixSumFn.apply(w[offset:offset + n, prims.index('skip')], *states)
+    rows = w if offset == 0 and n == w.shape[0] else w[offset:offset + n]
+    return fc_edge_sum_apply(ops, states, rows, prims, offset)
+
+
+def fc_edge_sum_apply(ops, states, rows, prims, offset=0):
+    """FcEdgeSumFn over the FC modules of ops[offset : offset + len(states)]; rows: their (n, len(prims)) weights."""
+    n = len(states)
+    fcs = [[op for name, op in zip(prims, ops[offset + j]._ops) if name in FC_KINDS] for j in range(n)]
+    params, buffers = [], []
+    for row in fcs:
+        for op in row:
+            params += [op.linear.weight, op.linear.bias, op.bn.weight, op.bn.bias]
+        buffers.append([(op.bn.running_mean, op.bn.running_var, op.bn.num_batches_tracked) for op in row])
+    return FcEdgeSumFn.apply(n, tuple(prims), fcs[0][0].training, fcs[0][0].dropout.p, buffers, rows, *states, *params)

@@ -811,6 +811,71 @@ int bmnas_probe_read(const float* p, int64_t n_floats, int width, int row_stride
 int bmnas_probe_barrier(const float* in, float* tmp, float* out, int64_t n_floats, int blocks, int mode,
                         unsigned int* counter, int round, void* stream);
 
+/* ---- mixed-edge sum with FC primitives (csrc/fcedge.hip) ------------------------
+ * out = sum_j sum_p w[j*P + p] * OPS[prims[p]](x_j) over n incoming states x_j (b, C, L): FusionCell.forward's
+ * `sum(self._ops[offset+j](h, weights[offset+j]) ...)` (model_search.py:58) and NodeCell.forward's
+ * (node_search.py:54) with FusionMixedOp.forward (operations.py:104-105) over OPS (operations.py:7-12):
+ * Zero (:14-20; not evaluated, as in bmnas_mixsum_fwd), Identity (:88-93), FC_Relu (:22-38), FC_Mish (:48-65):
+ * u = Linear(C, C) over channels, a = relu(u) | u * tanh(softplus(u)), y = BatchNorm1d(C)(a), o = Dropout(y).
+ * A fixed number of launches whatever n is — forward: bmnas_fc_edges_gemm_fwd, bmnas_fc_edges_mix_fwd;
+ * backward: bmnas_fc_edges_bwd_reduce, bmnas_fc_edges_bwd_du, bmnas_fc_edges_bwd_gemm — plus one zero-fill of
+ * the caller's accumulation buffers in front of each direction (bmnas_cell_prologue's scrub).
+ * Limits (bmnas_fc_edges_ok; BMNAS_E_* otherwise): 1 <= n <= 15, F in {1, 2} FC primitives per edge (the same
+ * kinds on every edge), P <= 8 weight columns, C % 16 == 0, L in {4, 8, 16}, b <= 65535.
+ * Per (edge, FC primitive), bmnas_fc_prim_t: the module's tensors plus
+ *   stat (2C, ZERO-FILLED; training): sums over b*L of d = a - act(bias[c]) and of d^2 — taken about the activation
+ *        of the bias so that E[d^2] - E[d]^2 does not cancel (relu(u)'s mean is of the order of its deviation);
+ *   chan (4C): mean | rstd | scale | shift, written by bmnas_fc_edges_mix_fwd, read by the backward;
+ *   dW (C, C), dbias (C), bn_grad (2C: dBN.weight | dBN.bias): ZERO-FILLED, the backward adds with atomics;
+ *   drop: the primitive's dropout site (its output is (b, C, L)); col: its column of the weight rows. */
+#define BMNAS_FC_MAX_EDGES 15
+typedef struct {
+  const float* W;
+  const float* bias;
+  const float* bn_w;
+  const float* bn_b;
+  float* running_mean;
+  float* running_var;
+  int64_t* num_batches_tracked;
+  float* stat;
+  float* chan;
+  float* dW;
+  float* dbias;
+  float* bn_grad;
+  bmnas_dropout_t drop;
+  int col;
+  int mish;               /* 0: FC_Relu, 1: FC_Mish */
+} bmnas_fc_prim_t;
+typedef struct {
+  const float* x;         /* (b, C, L) */
+  float* U;               /* (b, F*C, L): pre-activations, the edge's FC primitives stacked in list order */
+  float* dU;              /* (b, F*C, L): backward scratch, gradient w.r.t. U */
+  bmnas_fc_prim_t fc[2];
+} bmnas_fc_edge_t;
+int bmnas_fc_edges_ok(int n, int F, int P, int b, int C, int L);
+/* U_j = W_j^stack x_j + bias_j for all edges in one grid (fp32 MFMA); training: the batch sums into stat. */
+int bmnas_fc_edges_gemm_fwd(const bmnas_fc_edge_t* edges, int n, int F, int training, int b, int C, int L,
+                            void* stream);
+/* BatchNorm finalisation (training: from stat, running statistics and counters updated; eval: from the running
+ * statistics) inside the launch, then out[e] = sum_j (wskip_j x_j[e] + sum_f w[j*P + col_f] drop_jf(scale_jf
+ * act(U_jf[e]) + shift_jf)), wskip_j = sum of w[j*P + p] over the bits p of skip_cols (0: no x_j read). */
+int bmnas_fc_edges_mix_fwd(const bmnas_fc_edge_t* edges, int n, int F, const float* w, int P, uint32_t skip_cols,
+                           int training, float* out, int b, int C, int L, void* stream);
+/* g: gradient of out.  dw[j*P + col_f] += <g, o_jf>, dw[j*P + p] += <g, x_j> for the skip columns (other columns
+ * are left as zero-filled); bn_grad_jf += (sum dy a_hat | sum dy), dy = w[j*P + col_f] mask g. */
+int bmnas_fc_edges_bwd_reduce(const bmnas_fc_edge_t* edges, int n, int F, const float* w, int P,
+                              uint32_t skip_cols, const float* g, float* dw, int b, int C, int L, void* stream);
+/* dU_jf = da act'(U_jf), da = scale (dy - (dBN.bias + a_hat dBN.weight) / (b L)) (training) | scale dy (eval);
+ * dbias_jf += sum dU_jf. */
+int bmnas_fc_edges_bwd_du(const bmnas_fc_edge_t* edges, int n, int F, const float* w, int P, const float* g,
+                          int training, int b, int C, int L, void* stream);
+/* The data- and weight-gradient GEMMs in one grid: for each of n_dx destinations,
+ * dxs[q] = sum_{j in bits of dx_edges[q]} (W_j^stack^T dU_j + wskip_j g) — several edges that read the same
+ * tensor share one destination — and dW_jf += dU_jf x_j^T for every (edge, FC primitive). */
+int bmnas_fc_edges_bwd_gemm(const bmnas_fc_edge_t* edges, int n, int F, const float* w, int P, uint32_t skip_cols,
+                            const float* g, float* const* dxs, const uint32_t* dx_edges, int n_dx, int b, int C,
+                            int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
