@@ -537,14 +537,15 @@ class LazyNode(Pack):
 
 
 def _mixed_conv_fwd(sv, x, y, same, P, training, C, attn=None, Weff=None, stats=None):
-    # stacked [LinearGLU | ConcatFC] conv + BN
+    # stacked [LinearGLU | ConcatFC] conv + BN (an edited primitive list: whichever of the two it holds)
     if same:
         # conv(cat[z, z]) = (W[:, :C] + W[:, C:]) z: K is C instead of 2C.  The halves are added once
         # into a folded copy (2.3 us); letting the GEMMs add them while fetching their operand
         # (fold_cols of the C ABI) was measured slower: +4 us per GEMM for the doubled weight loads.
         if Weff is None:                     # (the fused cell folds every node's weights up front)
-            Weff = _empty(x, 3 * C, C)
-            lib.fold_weight(P.stack_W, Weff, 3 * C, C)
+            M = P.stack_W.shape[0]           # 3C; an edited primitive list: the present conv rows
+            Weff = _empty(x, M, C)
+            lib.fold_weight(P.stack_W, Weff, M, C)
         U, chan, sv.conv = conv_bn_fwd([x], C, Weff, C, P.stack_bias, P.stack_bn_w, P.stack_bn_b,
                                        P.stack_rm, P.stack_rv, P.stack_nbt, training, dup=C, attn=attn,
                                        stats=stats)
@@ -583,7 +584,8 @@ def _ln_affine(deferred, g, gscale, srcs, resid, ln_w, ln_b, stats, dln_w, dln_b
 
 def _attn_affine_bwd(sv, g, G, deferred=None):
     b, C, L = sv.x.shape
-    _ln_affine(deferred, g, sv.gamma[1:2], [sv.xhat1], None, None, None, None, G.dln_w, G.dln_b, b, C, L,
+    col = getattr(sv, 'attn_col', 1)         # the gamma column of ScaleDotAttn (an edited list: its list position)
+    _ln_affine(deferred, g, sv.gamma[col:col + 1], [sv.xhat1], None, None, None, None, G.dln_w, G.dln_b, b, C, L,
                False, True)
 
 
@@ -660,6 +662,102 @@ def node_mixed_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_stride=
 
 
 # ------------------------------------------------------------------- search-mode NodeCell
+# ------------------------------------------- NodeMixedOp over an edited STEP_STEP_PRIMITIVES list (csrc/nodemix_sel.hip)
+def node_mixed_sel_fwd(x, y, gamma_row, P, training):
+    """NodeMixedOp.forward (node_operations.py:118-120) for a list P.prims that is a subset / permutation of the four
+    built-in primitives: the launches of node_mixed_fwd over the PRESENT terms — the attention branch (inside the
+    conv GEMM launch when x is y and a conv is present), ONE conv GEMM over the present conv rows (P.M of them; the
+    x-is-y weight fold at that M), bn_finalize, and the selected-term combine.  No conv: no GEMM and no BatchNorm
+    launch; ['Sum'] alone: the combine only.  One dropout site per primitive that owns one, issued in LIST order."""
+    b, C, L = x.shape
+    same = x is y or x.data_ptr() == y.data_ptr()
+    prims, M = P.prims, P.M
+    has_attn, has_sum = 'ScaleDotAttn' in prims, 'Sum' in prims
+    sv = MixedSaved()
+    sv.x, sv.y, sv.same, sv.gamma, sv.P, sv.training = x, y, same, gamma_row, P, training
+    sv.sel = lib.make_node_sel(prims)
+    sv.d_attn = sv.d_glu = sv.d_fc = lib.NO_DROP
+    for name in prims:
+        if name == 'ScaleDotAttn':
+            sv.d_attn = DROP.make(P.attn_p, x.numel(), training)
+        elif name == 'LinearGLU':
+            sv.d_glu = DROP.make(P.glu_p, x.numel(), training)
+        elif name == 'ConcatFC':
+            sv.d_fc = DROP.make(P.fc_p, x.numel(), training)
+    sv.p1 = sv.xhat1 = sv.stats1 = sv.conv = None
+    sv.merged = False
+    attn = None
+    if has_attn:
+        sv.attn_col = prims.index('ScaleDotAttn')
+        sv.p1, sv.xhat1, sv.stats1 = torch.empty_like(x), torch.empty_like(x), _empty(x, b * 2)
+        attn = (x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, C, sv.d_attn)
+    U = chan = None
+    fin = lib.NO_FIN
+    if M > 0:
+        if has_attn and same and FUSE_ATTN_GEMM:
+            # forward: the merged launch takes any M; backward: its merged kernels are those of M = 3C, other row
+            # counts run the conv backward as its own (one-launch) call with the attention backward behind it
+            sv.merged = M == 3 * C
+            U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C, attn=attn)
+        elif has_attn:
+            with _Fork(x.device) as fork:
+                fork.side(lambda: lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, b, C, L,
+                                                  sv.d_attn))
+                U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C)
+        else:
+            U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C)
+        fin = sv.conv.fin
+    elif has_attn:
+        lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, b, C, L, sv.d_attn)
+    out = torch.empty_like(x)
+    lib.node_mix_sel_fwd(x if has_sum else None, y if has_sum else None, sv.p1, U, chan, gamma_row, sv.sel, out,
+                         b, C, L, sv.d_glu, sv.d_fc, fin)
+    return out, sv
+
+
+def node_mixed_sel_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_stride=0, deferred=None):
+    """Backward of node_mixed_sel_fwd.  dgamma_row: len(P.prims) floats (+=); x_slot / y_slot: GradSlots (y_slot None
+    when x is y); G: the gradient pack of NodeMixedOp.bind_grads (absent kinds: None), all +=."""
+    x, y, P = sv.x, sv.y, sv.P
+    b, C, L = x.shape
+    prims, M = P.prims, P.M
+    has_attn, has_sum = 'ScaleDotAttn' in prims, 'Sum' in prims
+    dV = _empty(x, b, M, L) if M > 0 else None
+    bn_grad = G.stack_bn_grad if M > 0 else None
+    U, chan = (sv.conv.U, sv.conv.chan) if M > 0 else (None, None)
+    # Sum writes gamma * g into the input gradients; without it the launch leaves them alone and the first
+    # contraction behind it (conv data gradient, attention backward) overwrites / accumulates by the slots' own state
+    dxb = dyb = None
+    acc = 0
+    if has_sum:
+        dxb, acc = x_slot.buf(), x_slot.acc_bit()
+        if not sv.same:
+            dyb = y_slot.buf()
+            acc |= y_slot.acc_bit() << 1
+    lib.node_mix_sel_bwd(g, x if has_sum else None, y if has_sum else None, sv.p1, U, chan, sv.gamma, sv.sel,
+                         dgamma_row, dxb, dyb, acc, dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride)
+    slots = [x_slot] if sv.same else [x_slot, y_slot]
+    if has_attn:
+        gcol = sv.gamma[sv.attn_col:sv.attn_col + 1]
+    if sv.merged and x_slot.extra is None:
+        # every contraction in one launch, exactly as node_mixed_bwd: the attention gradient goes to its own buffer
+        x_slot.extra = torch.empty_like(x)
+        conv_bn_bwd(sv.conv, dV, bn_grad, slots, G.stack_dW, G.stack_dbias,
+                    attn=(g, gcol, x, y, P.ln_w, sv.xhat1, sv.stats1, x_slot.extra, None, 0, C, sv.d_attn))
+    else:
+        if M > 0:
+            conv_bn_bwd(sv.conv, dV, bn_grad, slots, G.stack_dW, G.stack_dbias)
+        if has_attn:
+            dxa, amask = x_slot.buf(), x_slot.acc_bit()
+            dya = None
+            if not sv.same:
+                dya = y_slot.buf()
+                amask |= y_slot.acc_bit() << 1
+            lib.sdpa_ln_bwd(g, gcol, x, y, P.ln_w, sv.xhat1, sv.stats1, dxa, dya, amask, b, C, L, sv.d_attn)
+    if has_attn:
+        _attn_affine_bwd(sv, g, G, deferred)
+
+
 class NodeCellSaved:
     pass
 

@@ -917,6 +917,44 @@ class NodeMixedFn(Function):
         return (None, None, dx_half, dy, dgamma, *op.grads_in_param_order(G))
 
 
+class NodeMixedSelFn(Function):
+    """NodeMixedOp.forward(x, y, weights) (node_operations.py:118-120) over an edited STEP_STEP_PRIMITIVES list — a
+    subset / permutation of Sum, ScaleDotAttn, LinearGLU, ConcatFC (op._prims) — as the fused sequence of NodeMixedFn
+    restricted to the present terms (bmnas.cell.node_mixed_sel_fwd).  gamma_row / its gradient: len(op._prims)."""
+
+    @staticmethod
+    def forward(ctx, op, training, x, y, gamma_row, *params):
+        _require_gpu(x, 'NodeMixedOp')
+        same = x is y
+        x = _c(_f32(x))
+        y = x if same else _c(_f32(y))
+        P = op.pack()
+        out, sv = K.node_mixed_sel_fwd(x, y, _c(_f32(gamma_row)), P, training)
+        ctx.op, ctx.sv = op, sv
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        sv, op = ctx.sv, ctx.op
+        x = sv.x
+        # ONE zero fill for everything the launches accumulate into with atomics, dgamma included
+        arena = K.Arena()
+        h = op.plan_grads(arena)
+        hg = arena.ask(len(op._prims))
+        arena.alloc(x.device)
+        G = op.bind_grads(arena, h)
+        dgamma = arena.view(hg)
+        xs = K.GradSlot(x)
+        ys = None if sv.same else K.GradSlot(sv.y)
+        K.node_mixed_sel_bwd(sv, _c(g), dgamma, xs, ys, G)
+        dx = xs.get()
+        if xs.extra is not None:                 # attention part produced next to the GEMM
+            dx = dx.add_(xs.extra) if dx is not None else xs.extra
+        # x is y: the one tensor's whole gradient is returned for x (autograd skips the None)
+        dy = None if sv.same else ys.get()
+        return (None, None, dx, dy, dgamma, *op.grads_in_param_order(G))
+
+
 # -------------------------------------------------------------------- fused FusionCell
 class FusedCellFn(Function):
     """FusionCell.forward in search mode (model_search.py:50-68 with FusionNode(x, x)):

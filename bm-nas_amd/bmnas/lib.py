@@ -63,6 +63,11 @@ class BnFin(C.Structure):
 NO_FIN = BnFin()
 
 
+class NodeSel(C.Structure):
+    """bmnas_node_sel_t: gamma column of Sum | ScaleDotAttn | LinearGLU | ConcatFC (-1: absent), number of columns"""
+    _fields_ = [('col', C.c_int * 4), ('n', C.c_int)]
+
+
 class LazyLn(C.Structure):
     """bmnas_lazy_ln_t: a step-node output whose LayerNorm its consumers apply (csrc/lazyln.hip)"""
     _fields_ = [('pre', C.c_void_p), ('rec', C.c_void_p), ('prm', C.c_void_p), ('ln_w', C.c_void_p),
@@ -178,6 +183,10 @@ SIGNATURES = {
                                Dropout, _P, _P], _I),
     'bmnas_node_mix_bwd': ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _P, _P, _U32, _P, _P, _I, _I, _I,
                             Dropout, Dropout, _P], _I),
+    'bmnas_node_mix_sel_ok': ([_I, _I, _I, _I], _I),
+    'bmnas_node_mix_sel_fwd': ([_P, _P, _P, _P, _P, BnFin, _P, NodeSel, _P, _I, _I, _I, Dropout, Dropout, _P], _I),
+    'bmnas_node_mix_sel_bwd': ([_P, _P, _P, _P, _P, _P, _P, NodeSel, _P, _I, _I64, _P, _P, _U32, _P, _P, _I, _I, _I,
+                                Dropout, Dropout, _P], _I),
     'bmnas_node_mix_ln_bwd_ok': ([_I, _I, _I], _I),
     'bmnas_node_mix_ln_bwd': ([_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _P, _P, _U32,
                                _P, _P, _I, _I, _I, Dropout, Dropout, _P], _I),
@@ -849,6 +858,43 @@ def node_mix_bwd(g, x, y, p1, U, chan, gamma, dgamma, dx, dy, acc_mask, dV, bn_g
                                           _ptr(bn_grad), b, Cc, L, dglu, dfc, _ptrs(prev), _ptrs(dprev), len(prev),
                                           pacc, w.data_ptr(), ws, dw.data_ptr(), dws, dwst, _ptr(s), _ptr(gz),
                                           _ptr(gz2), _ptr(g_out), _stream()), 'node_mix_bwd_next')
+
+
+# ------------------------------------------------- NodeMixedOp over an edited primitive list (csrc/nodemix_sel.hip)
+NODE_SEL_LAUNCHES = {'fwd': 0, 'bwd': 0}     # launches issued by the two wrappers below (tests/test_node_prims_gpu.py)
+NODE_KINDS = ('Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC')
+
+
+def make_node_sel(prims):
+    """bmnas_node_sel_t of a STEP_STEP_PRIMITIVES list (the four built-in names, each at most once)."""
+    prims = list(prims)
+    if not prims or len(set(prims)) != len(prims) or any(p not in NODE_KINDS for p in prims):
+        raise ValueError(f'node selection: {prims} is not a non-empty list of distinct names out of {NODE_KINDS}')
+    cols = [prims.index(k) if k in prims else -1 for k in NODE_KINDS]
+    return NodeSel((C.c_int * 4)(*cols), len(prims))
+
+
+def node_sel_mask(sel):
+    return sum(1 << k for k in range(4) if sel.col[k] >= 0)
+
+
+def node_mix_sel_ok(mask, b, Cc, L):
+    return bool(load().bmnas_node_mix_sel_ok(int(mask), int(b), int(Cc), int(L)))
+
+
+def node_mix_sel_fwd(x, y, p1, U, chan, gamma, sel, out, b, Cc, L, dglu=NO_DROP, dfc=NO_DROP, fin=NO_FIN):
+    _check(load().bmnas_node_mix_sel_fwd(_ptr(x), _ptr(y), _ptr(p1), _ptr(U), _ptr(chan), fin, gamma.data_ptr(), sel,
+                                         _ptr(out), b, Cc, L, dglu, dfc, _stream()), 'node_mix_sel_fwd')
+    NODE_SEL_LAUNCHES['fwd'] += 1
+
+
+def node_mix_sel_bwd(g, x, y, p1, U, chan, gamma, sel, dgamma, dx, dy, acc_mask, dV, bn_grad, b, Cc, L,
+                     dglu=NO_DROP, dfc=NO_DROP, dg_shards=1, dg_stride=0):
+    _check(load().bmnas_node_mix_sel_bwd(_ptr(g), _ptr(x), _ptr(y), _ptr(p1), _ptr(U), _ptr(chan), gamma.data_ptr(),
+                                         sel, None if dgamma is None else dgamma.data_ptr(), dg_shards, dg_stride,
+                                         _ptr(dx), _ptr(dy), acc_mask, _ptr(dV), _ptr(bn_grad), b, Cc, L, dglu, dfc,
+                                         _stream()), 'node_mix_sel_bwd')
+    NODE_SEL_LAUNCHES['bwd'] += 1
 
 
 def node_mix_ln_bwd_ok(b, Cc, L):

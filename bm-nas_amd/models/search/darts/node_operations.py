@@ -9,7 +9,9 @@ import torch
 import torch.nn as nn
 
 from bmnas.cell import Arena, Pack
-from bmnas.functions import ConvBnActFn, ConvBnActThruFn, MixSumFn, NodeMixedFn, SdpaLnFn
+from bmnas import lib as _lib
+from bmnas.functions import (ConvBnActFn, ConvBnActThruFn, MixSumFn, NodeMixedFn, NodeMixedSelFn,
+                             SdpaLnFn)
 
 from .genotypes import *  # noqa: F401,F403
 from .genotypes import STEP_STEP_PRIMITIVES
@@ -95,28 +97,81 @@ class ScaledDotAttn(nn.Module):
         return SdpaLnFn.apply(x, y, self.ln.weight, self.ln.bias, self.dropout.p, self.training)
 
 
+_DEFAULT_PRIMS = ['Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC']
+_BUILTIN = {'Sum': Sum, 'ScaleDotAttn': ScaledDotAttn, 'LinearGLU': LinearGLU, 'ConcatFC': ConcatFC}
+
+# An edited STEP_STEP_PRIMITIVES list made of the four built-in primitives runs on the selected-term kernels
+# (csrc/nodemix_sel.hip); False forces the composed sum `sum(w * op(x, y))` for A/B timing and tests (the cell-level
+# counterpart is operations.FC_EDGES_NATIVE).  The default list is not affected either way.
+NODE_PRIMS_NATIVE = True
+
+
+def node_mix_route(op, x, y, weights):
+    """Which path NodeMixedOp.forward(x, y, weights) takes: 'default' (the unedited list: NodeMixedFn), 'selected'
+    (a subset / permutation of the built-in primitives: NodeMixedSelFn) or 'composed' (everything else: the
+    reference's own sum over the primitive modules, node_operations.py:118-120).  Host logic only."""
+    if op._default:
+        return 'default'
+    if not NODE_PRIMS_NATIVE:
+        return 'composed'
+    prims = op._prims
+    if not prims or len(set(prims)) != len(prims) or any(p not in _BUILTIN for p in prims):
+        return 'composed'
+    if len(op._ops) != len(prims) or any(type(m) is not _BUILTIN[p] for p, m in zip(prims, op._ops)):
+        return 'composed'                    # an edited STEP_STEP_OPS registry: somebody else's module
+    for t in (x, y):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+            return 'composed'
+    if x.shape != y.shape or x.device != y.device or tuple(x.shape[1:]) != (op.C, op.L):
+        return 'composed'
+    if not (torch.is_tensor(weights) and weights.dim() == 1 and weights.numel() == len(prims)
+            and weights.dtype == torch.float32):
+        return 'composed'
+    if any(m.training != op.training for m in op.modules()):
+        return 'composed'
+    for m in op._ops:
+        if isinstance(m, _CatConvBn):
+            bn = m.bn
+            if not (bn.momentum == 0.1 and bn.eps == 1e-5 and bn.affine and bn.track_running_stats
+                    and bn.running_mean is not None and bn.weight.is_cuda):
+                return 'composed'
+        elif isinstance(m, ScaledDotAttn):
+            if not (m.ln.eps == 1e-5 and m.ln.elementwise_affine and m.ln.weight.is_cuda):
+                return 'composed'
+    mask = sum(1 << _DEFAULT_PRIMS.index(p) for p in prims)
+    if not _lib.node_mix_sel_ok(mask, x.shape[0], op.C, op.L):
+        return 'composed'
+    return 'selected'
+
+
 class NodeMixedOp(nn.Module):
     """sum_p weights[p] * op_p(x, y) over STEP_STEP_PRIMITIVES (reference :110-120).
 
     With the default primitive list the whole mixed op is one fused kernel sequence
-    (bmnas.functions.NodeMixedFn).  To feed ONE stacked GEMM, the LinearGLU and ConcatFC
-    conv / BatchNorm parameters and buffers are kept as views into stacked tensors
-    (rows [0, 2C) = LinearGLU, rows [2C, 3C) = ConcatFC); names, shapes and state_dict
-    keys are exactly the reference's."""
+    (bmnas.functions.NodeMixedFn); with a subset / permutation of the four built-in primitives it is the same
+    sequence over the present terms (bmnas.functions.NodeMixedSelFn, see node_mix_route).  To feed ONE stacked GEMM,
+    the LinearGLU and ConcatFC conv / BatchNorm parameters and buffers — when both are in the list — are kept as
+    views into stacked tensors (rows [0, 2C) = LinearGLU, rows [2C, 3C) = ConcatFC, whatever their list order);
+    names, shapes and state_dict keys are exactly the reference's (`_ops.<list position>.…`)."""
 
     def __init__(self, C, L, args):
         super().__init__()
         self._ops = nn.ModuleList(STEP_STEP_OPS[p](C, L, args) for p in STEP_STEP_PRIMITIVES)
         self.C, self.L = C, L
-        self._default = list(STEP_STEP_PRIMITIVES) == ['Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC']
+        self._prims = list(STEP_STEP_PRIMITIVES)
+        self._default = self._prims == _DEFAULT_PRIMS
         self._stack = None
+
+    def _kind(self, name):
+        """The module of built-in primitive `name`, or None when the list does not hold it."""
+        return self._ops[self._prims.index(name)] if name in self._prims else None
 
     # -- stacked storage ---------------------------------------------------------------
     def _stack_ok(self):
         st = self._stack
         if st is None:
             return False
-        glu, cfc = self._ops[2], self._ops[3]
+        glu, cfc = self._kind('LinearGLU'), self._kind('ConcatFC')
         C = self.C
         return (glu.conv.weight.data_ptr() == st.W.data_ptr()
                 and cfc.conv.weight.data_ptr() == st.W[2 * C:].data_ptr()
@@ -127,7 +182,7 @@ class NodeMixedOp(nn.Module):
 
     @torch.no_grad()
     def _restack(self):
-        glu, cfc = self._ops[2], self._ops[3]
+        glu, cfc = self._kind('LinearGLU'), self._kind('ConcatFC')
         C = self.C
         dev = glu.conv.weight.device
 
@@ -151,28 +206,53 @@ class NodeMixedOp(nn.Module):
         cfc.bn.num_batches_tracked.data = nbt[1]
         self._stack = Pack(W=W, bias=bias, bn_w=bn_w, bn_b=bn_b, rm=rm, rv=rv, nbt=nbt)
 
+    def conv_rows(self):
+        """M: rows of the one conv GEMM of this op (2C LinearGLU + C ConcatFC, as present)."""
+        return (2 * self.C if 'LinearGLU' in self._prims else 0) + (self.C if 'ConcatFC' in self._prims else 0)
+
     def pack(self):
-        """Parameter pack consumed by bmnas.cell.node_mixed_fwd."""
-        if not self._stack_ok():
-            self._restack()
-        st, attn = self._stack, self._ops[1]
-        return Pack(ln_w=attn.ln.weight.detach(), ln_b=attn.ln.bias.detach(), attn_p=attn.dropout.p,
-                    glu_p=self._ops[2].dropout.p, fc_p=self._ops[3].dropout.p,
-                    stack_W=st.W, stack_bias=st.bias, stack_bn_w=st.bn_w, stack_bn_b=st.bn_b,
-                    stack_rm=st.rm, stack_rv=st.rv, stack_nbt=st.nbt)
+        """Parameter pack consumed by bmnas.cell.node_mixed_fwd / node_mixed_sel_fwd: by kind and presence (absent:
+        None / p = 0).  stack_*: the conv + BatchNorm storage of the present conv rows — the stacked tensors when
+        both convs are in the list, else the one conv's own tensors."""
+        attn, glu, cfc = self._kind('ScaleDotAttn'), self._kind('LinearGLU'), self._kind('ConcatFC')
+        P = Pack(prims=self._prims, M=self.conv_rows(),
+                 ln_w=None if attn is None else attn.ln.weight.detach(),
+                 ln_b=None if attn is None else attn.ln.bias.detach(),
+                 attn_p=0.0 if attn is None else attn.dropout.p,
+                 glu_p=0.0 if glu is None else glu.dropout.p, fc_p=0.0 if cfc is None else cfc.dropout.p)
+        if glu is not None and cfc is not None:
+            if not self._stack_ok():
+                self._restack()
+            st = self._stack
+            P.__dict__.update(stack_W=st.W, stack_bias=st.bias, stack_bn_w=st.bn_w, stack_bn_b=st.bn_b,
+                              stack_rm=st.rm, stack_rv=st.rv, stack_nbt=st.nbt)
+        elif glu is not None or cfc is not None:
+            m = glu if glu is not None else cfc
+            P.__dict__.update(stack_W=m.conv.weight.detach().view(P.M, 2 * self.C), stack_bias=m.conv.bias.detach(),
+                              stack_bn_w=m.bn.weight.detach(), stack_bn_b=m.bn.bias.detach(),
+                              stack_rm=m.bn.running_mean, stack_rv=m.bn.running_var,
+                              stack_nbt=m.bn.num_batches_tracked)
+        return P
 
     def param_list(self):
-        attn, glu, cfc = self._ops[1], self._ops[2], self._ops[3]
-        return [attn.ln.weight, attn.ln.bias, glu.conv.weight, glu.conv.bias, glu.bn.weight, glu.bn.bias,
-                cfc.conv.weight, cfc.conv.bias, cfc.bn.weight, cfc.bn.bias]
+        """The parameters in named_parameters() order: list position by list position."""
+        out = []
+        for m in self._ops:
+            if isinstance(m, ScaledDotAttn):
+                out += [m.ln.weight, m.ln.bias]
+            elif isinstance(m, _CatConvBn):
+                out += [m.conv.weight, m.conv.bias, m.bn.weight, m.bn.bias]
+        return out
 
     def plan_grads(self, arena):
-        C, L = self.C, self.L
-        return (arena.ask(3 * C, 2 * C), arena.ask(3 * C), arena.ask(6 * C), arena.ask(C, L), arena.ask(C, L))
+        C, L, M = self.C, self.L, self.conv_rows()
+        attn = 'ScaleDotAttn' in self._prims
+        return (arena.ask(M, 2 * C) if M else None, arena.ask(M) if M else None, arena.ask(2 * M) if M else None,
+                arena.ask(C, L) if attn else None, arena.ask(C, L) if attn else None)
 
     def bind_grads(self, arena, h):
-        return Pack(stack_dW=arena.view(h[0]), stack_dbias=arena.view(h[1]), stack_bn_grad=arena.view(h[2]),
-                    dln_w=arena.view(h[3]), dln_b=arena.view(h[4]))
+        v = [None if i is None else arena.view(i) for i in h]
+        return Pack(stack_dW=v[0], stack_dbias=v[1], stack_bn_grad=v[2], dln_w=v[3], dln_b=v[4])
 
     def grad_pack(self, device):
         arena = Arena()
@@ -181,14 +261,24 @@ class NodeMixedOp(nn.Module):
         return self.bind_grads(arena, h)
 
     def grads_in_param_order(self, G):
-        C = self.C
+        C, M = self.C, self.conv_rows()
         dW, db, bn = G.stack_dW, G.stack_dbias, G.stack_bn_grad
-        return [G.dln_w, G.dln_b,
-                dW[:2 * C].view(2 * C, 2 * C, 1), db[:2 * C], bn[0:2 * C], bn[3 * C:5 * C],
-                dW[2 * C:].view(C, 2 * C, 1), db[2 * C:], bn[2 * C:3 * C], bn[5 * C:6 * C]]
+        fo = 2 * C if 'LinearGLU' in self._prims else 0          # first ConcatFC row
+        out = []
+        for p in self._prims:
+            if p == 'ScaleDotAttn':
+                out += [G.dln_w, G.dln_b]
+            elif p == 'LinearGLU':
+                out += [dW[:2 * C].view(2 * C, 2 * C, 1), db[:2 * C], bn[0:2 * C], bn[M:M + 2 * C]]
+            elif p == 'ConcatFC':
+                out += [dW[fo:fo + C].view(C, 2 * C, 1), db[fo:fo + C], bn[fo:fo + C], bn[M + fo:M + fo + C]]
+        return out
 
     def forward(self, x, y, weights):
-        if not self._default:
+        route = node_mix_route(self, x, y, weights)
+        if route == 'composed':
             return sum(w * op(x, y) for w, op in zip(weights, self._ops))
         w = weights if weights.device == x.device else weights.to(x.device)
+        if route == 'selected':
+            return NodeMixedSelFn.apply(self, self.training, x, y, w, *self.param_list())
         return NodeMixedFn.apply(self, self.training, x, y, w, *self.param_list())

@@ -343,6 +343,38 @@ int bmnas_node_mix_bwd(const float* g, const float* x, const float* y, const flo
                        uint32_t accumulate_mask, float* dV, float* bn_grad, int b, int C, int L,
                        bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream);
 
+/* ---- K2 for an edited STEP_STEP_PRIMITIVES list (csrc/nodemix_sel.hip) ---------------------
+ * NodeMixedOp.forward node_operations.py:110-120, `sum(w * op(x, y) for w, op in zip(weights, self._ops))`, over any
+ * non-empty subset of {Sum, ScaleDotAttn, LinearGLU, ConcatFC} in any order, each at most once:
+ *   s = sum_{p present} gamma[col[p]] * term_p
+ * with the terms of bmnas_node_mix_fwd.  col[k] is the gamma column (the list position) of kind k — 0 Sum,
+ * 1 ScaleDotAttn, 2 LinearGLU, 3 ConcatFC — or -1 when the kind is absent; n = number of present kinds = length of
+ * gamma (and of every dgamma shard).  The presence mask has bit k set for a present kind.
+ * U: (b, M, L) with M = 2C [LinearGLU present] + C [ConcatFC present], LinearGLU rows first; chan: 4M floats;
+ * dV: (b, M, L); bn_grad: [M | M].  M = 0: U, chan, dV, bn_grad are NULL (fin is ignored).  p1 is NULL without
+ * ScaleDotAttn; x / y may be NULL without Sum.  The kernels are compiled per mask: an absent term costs no load,
+ * store, reduction or LDS.  fin: on = 0 or 1 as in bmnas_node_mix_fwd (running statistics, n_nbt counters of one
+ * or two BatchNorms). */
+typedef struct {
+  int col[4];
+  int n;
+} bmnas_node_sel_t;
+/* The limits of the path (BMNAS_E_LIMIT from the two calls outside them): L % 4 == 0; with ScaleDotAttn or a conv,
+ * L in {4, 8, 16} and C % 16 == 0 (the 16 x 16 tiles of bmnas_sdpa_ln_* / bmnas_conv1x1_*, the L / 4-lane row
+ * reductions of the backward); with ScaleDotAttn C <= 512; M <= 4096 (scale | shift of every conv row in LDS). */
+int bmnas_node_mix_sel_ok(int mask, int b, int C, int L);
+int bmnas_node_mix_sel_fwd(const float* x, const float* y, const float* p1, const float* U, float* chan,
+                           bmnas_bn_fin_t fin, const float* gamma, bmnas_node_sel_t sel, float* out, int b, int C,
+                           int L, bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream);
+/* Backward, phase A, as bmnas_node_mix_bwd: dgamma[shard*dgamma_shard_stride + col[k]] += <g, term_k>;
+ * dx / dy (=|+=) gamma[col[Sum]] * g (dy NULL: both halves into dx) — without Sum the only write is a zero where
+ * the accumulate bit is clear; dV / bn_grad over the present conv rows. */
+int bmnas_node_mix_sel_bwd(const float* g, const float* x, const float* y, const float* p1, const float* U,
+                           const float* chan, const float* gamma, bmnas_node_sel_t sel, float* dgamma,
+                           int dgamma_shards, int64_t dgamma_shard_stride, float* dx, float* dy,
+                           uint32_t accumulate_mask, float* dV, float* bn_grad, int b, int C, int L,
+                           bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream);
+
 /* K6 backward + K2 backward in one launch (node_multiplier == 1; reference node_search.py:55,67-68 run
  * backwards): g = grad of out = LayerNorm_[C, L](pre), pre / stats as saved by bmnas_node_mix_ln_fwd.
  * g_in (nullable) receives the LayerNorm input gradient (the attention backward reads it), dresid (=|+= by
