@@ -1,5 +1,7 @@
 """-m gpu: every HIP kernel of libbmnas_hip.so (through the C ABI) against the CPU oracle
-on the same seeded inputs.  Tolerance: 1e-4 of the expected tensor's scale (fp32)."""
+on the same seeded inputs.  Tolerance: 1e-4 of the expected tensor's scale (fp32).
+The attention kernels' channel range (every KCH instantiation up to C = 512, the merged conv + attention
+launches called directly) is in tests/test_attention_channels_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -90,6 +92,8 @@ def test_cat_ln_fwd_bwd(n_src, b, C, L, relu, resid):
                                         (7, 48, 4, False), (2, 192, 16, True), (9, 128, 8, False),
                                         (1, 16, 16, True)])
 def test_sdpa_ln_fwd_bwd(b, C, L, same):
+    """The module path (SdpaLnFn) at C <= 192, i.e. KCH 1..3; C = 64 .. 512 (KCH 4, 6, 8, ragged and rounded-up
+    chunk counts, dropout, gscale, accumulate bits) through the C ABI: tests/test_attention_channels_gpu.py."""
     from bmnas.functions import SdpaLnFn
     g = _gen(200 + b + C + L)
     x = _rand(g, b, C, L)
