@@ -140,11 +140,7 @@ __global__ __launch_bounds__(256) void node_mix_fwd_k(
     const float4 vf = affine4(ld4(U + ub + (int64_t)2 * C * L), sc[2 * C + c], sh[2 * C + c]);
     const float4 m2 = drop_mult4(rglu, (uint64_t)e), m3 = drop_mult4(rfc, (uint64_t)e);
     const float4 xv = ld4(x + e), yv = ld4(y + e), pv = ld4(p1 + e);
-    float4 o;
-    o.x = g0 * (xv.x + yv.x) + g1 * pv.x + g2 * (va.x * sigmoidf(vg.x) * m2.x) + g3 * (fmaxf(vf.x, 0.f) * m3.x);
-    o.y = g0 * (xv.y + yv.y) + g1 * pv.y + g2 * (va.y * sigmoidf(vg.y) * m2.y) + g3 * (fmaxf(vf.y, 0.f) * m3.y);
-    o.z = g0 * (xv.z + yv.z) + g1 * pv.z + g2 * (va.z * sigmoidf(vg.z) * m2.z) + g3 * (fmaxf(vf.z, 0.f) * m3.z);
-    o.w = g0 * (xv.w + yv.w) + g1 * pv.w + g2 * (va.w * sigmoidf(vg.w) * m2.w) + g3 * (fmaxf(vf.w, 0.f) * m3.w);
+    const float4 o = mix_fwd4<kMixAll>(g0, g1, g2, g3, f4_add(xv, yv), pv, va, vg, vf, m2, m3);
     st4_wtg<2>(out + e, o);
     if (NP > 0) {
       float4 z = f4_scale(o, N.w[NP * N.ws]);
@@ -217,11 +213,7 @@ __global__ __launch_bounds__(BS) void node_mix_ln_fwd_k(
       const float4 vg = affine4(ug[k], sc[C + c], sh[C + c]);
       const float4 vf = affine4(uf[k], sc[2 * C + c], sh[2 * C + c]);
       const float4 m2 = drop_mult4(rglu, (uint64_t)e), m3 = drop_mult4(rfc, (uint64_t)e);
-      float4 o;
-      o.x = g0 * (xv[k].x + yv[k].x) + g1 * pv[k].x + g2 * (va.x * sigmoidf(vg.x) * m2.x) + g3 * (fmaxf(vf.x, 0.f) * m3.x);
-      o.y = g0 * (xv[k].y + yv[k].y) + g1 * pv[k].y + g2 * (va.y * sigmoidf(vg.y) * m2.y) + g3 * (fmaxf(vf.y, 0.f) * m3.y);
-      o.z = g0 * (xv[k].z + yv[k].z) + g1 * pv[k].z + g2 * (va.z * sigmoidf(vg.z) * m2.z) + g3 * (fmaxf(vf.z, 0.f) * m3.z);
-      o.w = g0 * (xv[k].w + yv[k].w) + g1 * pv[k].w + g2 * (va.w * sigmoidf(vg.w) * m2.w) + g3 * (fmaxf(vf.w, 0.f) * m3.w);
+      const float4 o = mix_fwd4<kMixAll>(g0, g1, g2, g3, f4_add(xv[k], yv[k]), pv[k], va, vg, vf, m2, m3);
       v[k] = f4_add(o, rv[k]);
       st4_wtg<2>(pre + e, v[k]);
       sum += f4_hsum(v[k]);
@@ -300,14 +292,7 @@ __global__ __launch_bounds__(256) void node_mix_bwd_k(
   const int c = active ? r / l4n : 0;
   const float g0 = gamma[0], g2 = gamma[2], g3 = gamma[3];
   const DropRt rglu = drop_begin(dglu), rfc = drop_begin(dfc);
-  float sc[3], sh[3], mu[3], rs[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    mu[k] = chan[k * C + c];
-    rs[k] = chan[M + k * C + c];
-    sc[k] = chan[2 * M + k * C + c];
-    sh[k] = chan[3 * M + k * C + c];
-  }
+  const ChanBn<3> bn = chan_load<3>(chan, M, C, c);
   float dgam[4] = {0.f, 0.f, 0.f, 0.f};
   float sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
   const int s_beg = blockIdx.y * chunk;
@@ -341,45 +326,12 @@ __global__ __launch_bounds__(256) void node_mix_bwd_k(
       }
       const float4 xv = ld4(x + e), yv = ld4(y + e), pv = ld4(p1 + e);
       const float4 m2 = drop_mult4(rglu, (uint64_t)e), m3 = drop_mult4(rfc, (uint64_t)e);
-      const float gq[4] = {gv.x, gv.y, gv.z, gv.w};
-      const float uaq[4] = {ua.x, ua.y, ua.z, ua.w}, ugq[4] = {ug.x, ug.y, ug.z, ug.w},
-                  ufq[4] = {uf.x, uf.y, uf.z, uf.w};
-      const float xq[4] = {xv.x + yv.x, xv.y + yv.y, xv.z + yv.z, xv.w + yv.w};
-      const float pq[4] = {pv.x, pv.y, pv.z, pv.w};
-      const float m2q[4] = {m2.x, m2.y, m2.z, m2.w}, m3q[4] = {m3.x, m3.y, m3.z, m3.w};
-      float da[4], dg[4], df[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float va = fmaf(uaq[t], sc[0], sh[0]), vg = fmaf(ugq[t], sc[1], sh[1]),
-                    vf = fmaf(ufq[t], sc[2], sh[2]);
-        const float sg = sigmoidf(vg);
-        dgam[0] += gq[t] * xq[t];
-        dgam[1] += gq[t] * pq[t];
-        dgam[2] += gq[t] * (va * sg * m2q[t]);
-        dgam[3] += gq[t] * (fmaxf(vf, 0.f) * m3q[t]);
-        const float gm2 = g2 * gq[t] * m2q[t];
-        da[t] = gm2 * sg;
-        dg[t] = gm2 * va * sg * (1.f - sg);
-        df[t] = (vf > 0.f) ? g3 * gq[t] * m3q[t] : 0.f;
-        sw[0] += da[t] * (uaq[t] - mu[0]) * rs[0];
-        sw[1] += dg[t] * (ugq[t] - mu[1]) * rs[1];
-        sw[2] += df[t] * (ufq[t] - mu[2]) * rs[2];
-        sb[0] += da[t]; sb[1] += dg[t]; sb[2] += df[t];
-      }
-      st4_wtg<2>(dV + ub, make_float4(da[0], da[1], da[2], da[3]));
-      st4_wtg<2>(dV + ub + (int64_t)C * L, make_float4(dg[0], dg[1], dg[2], dg[3]));
-      st4_wtg<2>(dV + ub + (int64_t)2 * C * L, make_float4(df[0], df[1], df[2], df[3]));
-      const float4 d0 = f4_scale(gv, g0);
-      if (dx != nullptr) {
-        float4 v = (dy == nullptr) ? f4_scale(d0, 2.f) : d0;
-        if (acc_mask & 1u) v = f4_add(v, ld4(dx + e));
-        st4_wtg<2>(dx + e, v);
-      }
-      if (dy != nullptr) {
-        float4 v = d0;
-        if (acc_mask & 2u) v = f4_add(v, ld4(dy + e));
-        st4_wtg<2>(dy + e, v);
-      }
+      float4 da, dg, df;
+      mix_bwd4<kMixAll>(g2, g3, gv, f4_add(xv, yv), pv, ua, ug, uf, m2, m3, bn, dgam, da, dg, df, sw, sb);
+      st4_wtg<2>(dV + ub, da);
+      st4_wtg<2>(dV + ub + (int64_t)C * L, dg);
+      st4_wtg<2>(dV + ub + (int64_t)2 * C * L, df);
+      mix_dxy_store([](float* p, float4 v) { st4_wtg<2>(p, v); }, dx, dy, e, gv, g0, acc_mask);
     }
   }
   // per-channel batch sums -> BatchNorm affine gradients: reduce over the l4 lanes of a
@@ -440,7 +392,7 @@ __global__ __launch_bounds__(256) void node_mix_bwd_k(
 // gradient of the node output never makes a round trip of its own.  TWO workgroups per sample so that
 // 128 samples still cover 256 CUs: both reduce the sample's two LayerNorm sums (the 24 KB of a sample's
 // gy / pre-norm rows are read twice — against a 5 us launch), then each takes one half of the sample's
-// channels through LayerNorm backward -> gamma-mix backward (the arithmetic of node_mix_bwd_k).
+// channels through LayerNorm backward -> gamma-mix backward (the block of mix_bwd4, mix_terms.hpp).
 // A thread's element k of the first phase (k < VPT2) IS its element of the second phase: half h
 // starts its walk over the sample at its own half.  BatchNorm reductions: one atomic pair per
 // channel per sample (as bn_relu_ln_bwd_k), which is why the launcher keeps this to b <= 128.
@@ -460,14 +412,12 @@ __global__ __launch_bounds__(BS) void node_mix_ln_bwd_k(
   const DropRt rglu = drop_begin(dglu), rfc = drop_begin(dfc);
   // second-phase operands first: they do not depend on the sums
   float4 ua[VPT2], ug[VPT2], uf[VPT2], xv[VPT2], yv[VPT2], pv[VPT2], oldr[VPT2], oldx[VPT2], oldy[VPT2];
-  float csc[VPT2][3], csh[VPT2][3], cmu[VPT2][3], crs[VPT2][3];
+  ChanBn<3> bn[VPT2];
 #pragma unroll
   for (int k = 0; k < VPT2; ++k) {
     const int idx = threadIdx.x + k * BS;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     ua[k] = ug[k] = uf[k] = xv[k] = yv[k] = pv[k] = oldr[k] = oldx[k] = oldy[k] = zero;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) csc[k][q] = csh[k][q] = cmu[k][q] = crs[k][q] = 0.f;
     {                                                    // clamped addresses, no predicate around the loads
       const int r = half * h4 + (idx < h4 ? idx : h4 - 1);
       const int c = r / l4n;
@@ -482,13 +432,7 @@ __global__ __launch_bounds__(BS) void node_mix_ln_bwd_k(
       if (acc_resid) oldr[k] = ld4(dresid + e);
       if (dx != nullptr && (acc_mask & 1u)) oldx[k] = ld4(dx + e);
       if (dy != nullptr && (acc_mask & 2u)) oldy[k] = ld4(dy + e);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        cmu[k][q] = chan[q * C + c];
-        crs[k][q] = chan[M + q * C + c];
-        csc[k][q] = chan[2 * M + q * C + c];
-        csh[k][q] = chan[3 * M + q * C + c];
-      }
+      bn[k] = chan_load<3>(chan, M, C, c);
     }
   }
   const float g0 = gamma[0], g2 = gamma[2], g3 = gamma[3];
@@ -546,10 +490,11 @@ __global__ __launch_bounds__(BS) void node_mix_ln_bwd_k(
       const float pq[4] = {pv[k].x, pv[k].y, pv[k].z, pv[k].w};
       const float m2q[4] = {m2d.x, m2d.y, m2d.z, m2d.w}, m3q[4] = {m3d.x, m3d.y, m3d.z, m3d.w};
       float da[4], dg[4], df[4];
+      // mix_bwd4<kMixAll> (mix_terms.hpp) written out: through the call <1,1,512> / <2,1,512> need 98 VGPRs, not 94 (occupancy 5 -> 4)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const float va = fmaf(uaq[t], csc[k][0], csh[k][0]), vg = fmaf(ugq[t], csc[k][1], csh[k][1]),
-                    vf = fmaf(ufq[t], csc[k][2], csh[k][2]);
+        const float va = fmaf(uaq[t], bn[k].sc[0], bn[k].sh[0]), vg = fmaf(ugq[t], bn[k].sc[1], bn[k].sh[1]),
+                    vf = fmaf(ufq[t], bn[k].sc[2], bn[k].sh[2]);
         const float sg = sigmoidf(vg);
         dgam[0] += gq[t] * xq[t];
         dgam[1] += gq[t] * pq[t];
@@ -559,17 +504,15 @@ __global__ __launch_bounds__(BS) void node_mix_ln_bwd_k(
         da[t] = gm2 * sg;
         dg[t] = gm2 * va * sg * (1.f - sg);
         df[t] = (vf > 0.f) ? g3 * gq[t] * m3q[t] : 0.f;
-        sw[0] += da[t] * (uaq[t] - cmu[k][0]) * crs[k][0];
-        sw[1] += dg[t] * (ugq[t] - cmu[k][1]) * crs[k][1];
-        sw[2] += df[t] * (ufq[t] - cmu[k][2]) * crs[k][2];
+        sw[0] += da[t] * (uaq[t] - bn[k].mu[0]) * bn[k].rs[0];
+        sw[1] += dg[t] * (ugq[t] - bn[k].mu[1]) * bn[k].rs[1];
+        sw[2] += df[t] * (ufq[t] - bn[k].mu[2]) * bn[k].rs[2];
         sb[0] += da[t]; sb[1] += dg[t]; sb[2] += df[t];
       }
       st4_wtg<2>(dV + ub, make_float4(da[0], da[1], da[2], da[3]));
       st4_wtg<2>(dV + ub + (int64_t)C * L, make_float4(dg[0], dg[1], dg[2], dg[3]));
       st4_wtg<2>(dV + ub + (int64_t)2 * C * L, make_float4(df[0], df[1], df[2], df[3]));
-      const float4 d0 = f4_scale(gv, g0);
-      if (dx != nullptr) st4_wtg<2>(dx + e, f4_add((dy == nullptr) ? f4_scale(d0, 2.f) : d0, oldx[k]));
-      if (dy != nullptr) st4_wtg<2>(dy + e, f4_add(d0, oldy[k]));
+      mix_dxy_store([](float* p, float4 v) { st4_wtg<2>(p, v); }, dx, dy, e, gv, g0, oldx[k], oldy[k]);
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -615,8 +558,8 @@ __global__ __launch_bounds__(256) void bn_glu_fwd_k(const float* __restrict__ U,
     const float4 va = affine4(ld4(U + ub), sc[c], sh[c]);
     const float4 vg = affine4(ld4(U + ub + (int64_t)C * L), sc[C + c], sh[C + c]);
     const float4 m = drop_mult4(dr, (uint64_t)(i * 4));
-    st4_wtg<2>(out + i * 4, make_float4(va.x * sigmoidf(vg.x) * m.x, va.y * sigmoidf(vg.y) * m.y,
-                                  va.z * sigmoidf(vg.z) * m.z, va.w * sigmoidf(vg.w) * m.w));
+    st4_wtg<2>(out + i * 4, make_float4(glu_term(va.x, sigmoidf(vg.x), m.x), glu_term(va.y, sigmoidf(vg.y), m.y),
+                                        glu_term(va.z, sigmoidf(vg.z), m.z), glu_term(va.w, sigmoidf(vg.w), m.w)));
   }
 }
 
@@ -632,14 +575,7 @@ __global__ __launch_bounds__(256) void bn_glu_bwd_k(const float* __restrict__ g,
   const int r = blockIdx.x * 64 + col;
   const bool active = r < cl4;
   const int c = active ? r / l4n : 0;
-  float sc[2], sh[2], mu[2], rs[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    mu[k] = chan[k * C + c];
-    rs[k] = chan[M + k * C + c];
-    sc[k] = chan[2 * M + k * C + c];
-    sh[k] = chan[3 * M + k * C + c];
-  }
+  const ChanBn<2> bn = chan_load<2>(chan, M, C, c);
   float sw[2] = {0.f, 0.f}, sb[2] = {0.f, 0.f};
   const int s_beg = blockIdx.y * chunk;
   int s_end = s_beg + chunk;
@@ -650,22 +586,13 @@ __global__ __launch_bounds__(256) void bn_glu_bwd_k(const float* __restrict__ g,
       const int64_t ub = ((int64_t)s * M) * L + (int64_t)r * 4;
       const float4 ua = ld4(U + ub), ug = ld4(U + ub + (int64_t)C * L), gv = ld4(g + e);
       const float4 m = drop_mult4(dr, (uint64_t)e);
-      const float uaq[4] = {ua.x, ua.y, ua.z, ua.w}, ugq[4] = {ug.x, ug.y, ug.z, ug.w},
-                  gq[4] = {gv.x, gv.y, gv.z, gv.w}, mq[4] = {m.x, m.y, m.z, m.w};
-      float da[4], dg[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float va = fmaf(uaq[t], sc[0], sh[0]), vg = fmaf(ugq[t], sc[1], sh[1]);
-        const float sg = sigmoidf(vg);
-        const float gm = gq[t] * mq[t];
-        da[t] = gm * sg;
-        dg[t] = gm * va * sg * (1.f - sg);
-        sw[0] += da[t] * (uaq[t] - mu[0]) * rs[0];
-        sw[1] += dg[t] * (ugq[t] - mu[1]) * rs[1];
-        sb[0] += da[t]; sb[1] += dg[t];
-      }
-      st4_wtg<2>(dV + ub, make_float4(da[0], da[1], da[2], da[3]));
-      st4_wtg<2>(dV + ub + (int64_t)C * L, make_float4(dg[0], dg[1], dg[2], dg[3]));
+      // the mix backward with LinearGLU alone and weight 1 (its dgamma sum has no reader and compiles to nothing)
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      float unused[4] = {0.f, 0.f, 0.f, 0.f};
+      float4 da, dg, df;
+      mix_bwd4<kGlu>(1.f, 0.f, gv, zero, zero, ua, ug, zero, m, zero, bn, unused, da, dg, df, sw, sb);
+      st4_wtg<2>(dV + ub, da);
+      st4_wtg<2>(dV + ub + (int64_t)C * L, dg);
     }
   }
   float cs[4];

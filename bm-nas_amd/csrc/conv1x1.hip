@@ -10,6 +10,7 @@
 // The k-permutation is legal because A and B use the same one.
 // FLOPs: 2*M*K*b*L each; bound: fp32 MFMA (157 TFLOP/s dense).
 #include "sdpa_body.hpp"
+#include "mix_terms.hpp"
 #ifndef BMNAS_FWD_LA2
 #define BMNAS_FWD_LA2 1
 #endif
@@ -132,8 +133,6 @@ struct MixEp {
   DropCfg dglu, dfc;
 };
 
-__device__ __forceinline__ float sigmoid_ep(float v) { return 1.f / (1.f + __expf(-v)); }
-
 // lane = (channel cj = .. + lo, four consecutive l of sample `so`); gv = gradient of the mixed output there
 // (zero for padded samples: vo false).  All 64 lanes of the wave call it (shuffles).
 __device__ __forceinline__ void mix_ep_tile(const MixEp& m, const float4 gv, const int so, const int cj,
@@ -147,44 +146,17 @@ __device__ __forceinline__ void mix_ep_tile(const MixEp& m, const float4 gv, con
   const float4 xv = ld4(m.x + e), pv = ld4(m.p1 + e);
   float4 oldx = make_float4(0.f, 0.f, 0.f, 0.f);
   if (m.acc_dx) oldx = ld4(m.dx + e);
-  float mu[3], rs[3], sc[3], sh[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    mu[k] = m.chan[k * C + cj];
-    rs[k] = m.chan[M + k * C + cj];
-    sc[k] = m.chan[2 * M + k * C + cj];
-    sh[k] = m.chan[3 * M + k * C + cj];
-  }
+  const ChanBn<3> bn = chan_load<3>(m.chan, M, C, cj);
   const float g0 = m.gamma[0], g2 = m.gamma[2], g3 = m.gamma[3];
   const DropRt rglu = drop_begin(m.dglu), rfc = drop_begin(m.dfc);
   const float4 m2 = drop_mult4(rglu, (uint64_t)e), m3 = drop_mult4(rfc, (uint64_t)e);
-  const float gq[4] = {gv.x, gv.y, gv.z, gv.w};
-  const float uaq[4] = {ua.x, ua.y, ua.z, ua.w}, ugq[4] = {ug.x, ug.y, ug.z, ug.w}, ufq[4] = {uf.x, uf.y, uf.z, uf.w};
-  const float xq[4] = {2.f * xv.x, 2.f * xv.y, 2.f * xv.z, 2.f * xv.w};       // x + y, x is y
-  const float pq[4] = {pv.x, pv.y, pv.z, pv.w};
-  const float m2q[4] = {m2.x, m2.y, m2.z, m2.w}, m3q[4] = {m3.x, m3.y, m3.z, m3.w};
-  float da[4], dg[4], df[4], dgam[4] = {0.f, 0.f, 0.f, 0.f}, sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {                                // the arithmetic of node_mix_bwd_k, term for term
-    const float va = fmaf(uaq[t], sc[0], sh[0]), vg = fmaf(ugq[t], sc[1], sh[1]), vf = fmaf(ufq[t], sc[2], sh[2]);
-    const float sg = sigmoid_ep(vg);
-    dgam[0] += gq[t] * xq[t];
-    dgam[1] += gq[t] * pq[t];
-    dgam[2] += gq[t] * (va * sg * m2q[t]);
-    dgam[3] += gq[t] * (fmaxf(vf, 0.f) * m3q[t]);
-    const float gm2 = g2 * gq[t] * m2q[t];
-    da[t] = gm2 * sg;
-    dg[t] = gm2 * va * sg * (1.f - sg);
-    df[t] = (vf > 0.f) ? g3 * gq[t] * m3q[t] : 0.f;
-    sw[0] += da[t] * (uaq[t] - mu[0]) * rs[0];
-    sw[1] += dg[t] * (ugq[t] - mu[1]) * rs[1];
-    sw[2] += df[t] * (ufq[t] - mu[2]) * rs[2];
-    sb[0] += da[t]; sb[1] += dg[t]; sb[2] += df[t];
-  }
+  float4 da, dg, df;
+  float dgam[4] = {0.f, 0.f, 0.f, 0.f}, sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
+  mix_bwd4<kMixAll>(g2, g3, gv, f4_scale(xv, 2.f), pv, ua, ug, uf, m2, m3, bn, dgam, da, dg, df, sw, sb);   // x is y
   if (vo) {
-    st4(m.dV + ub, make_float4(da[0], da[1], da[2], da[3]));
-    st4(m.dV + ub + (int64_t)C * L, make_float4(dg[0], dg[1], dg[2], dg[3]));
-    st4(m.dV + ub + (int64_t)2 * C * L, make_float4(df[0], df[1], df[2], df[3]));
+    st4(m.dV + ub, da);
+    st4(m.dV + ub + (int64_t)C * L, dg);
+    st4(m.dV + ub + (int64_t)2 * C * L, df);
     st4(m.dx + e, f4_add(f4_scale(gv, 2.f * g0), oldx));      // dy == NULL: both halves into dx
   }
   // BatchNorm reductions over the tile's 16 columns: the four lanes h of a channel (xor 16 / 32), then one

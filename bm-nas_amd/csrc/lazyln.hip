@@ -16,7 +16,7 @@
 //             also leaves per-workgroup partials of the two sums the LayerNorm backward needs —
 //             S(gy w) and S(gy w xhat) are linear in gy — as plain stores;
 //             bmnas_node_mix_lnp_bwd      sums the partials of its samples, applies the LayerNorm backward
-//             elementwise and continues into the mix backward (the arithmetic of node_mix_bwd_k), streaming.
+//             elementwise and continues into the mix backward (mix_bwd4, mix_terms.hpp), streaming.
 //
 // No atomics on any of the new per-sample quantities: the records and partials are plain stores combined in a fixed
 // order (run-to-run deterministic).
@@ -30,8 +30,8 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------ forward: producer
 // grid = (P parts, b samples), 256 threads, one float4 per thread.
-// pre = g0 (x + y) + g1 p1 + g2 drop(va sigmoid(vg)) + g3 drop(relu(vf)) + resid   (same expression order as
-// node_mix_ln_fwd_k, so `pre` is bit-identical to that kernel's)
+// pre = g0 (x + y) + g1 p1 + g2 drop(va sigmoid(vg)) + g3 drop(relu(vf)) + resid   (mix_fwd4, mix_terms.hpp: the
+// expression node_mix_ln_fwd_k compiles, so `pre` is bit-identical to that kernel's)
 __global__ __launch_bounds__(256) void node_mix_pre_fwd_k(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ p1,
     const float* __restrict__ U, float* __restrict__ chan, BnFin fin, const float* __restrict__ gamma,
@@ -71,11 +71,7 @@ __global__ __launch_bounds__(256) void node_mix_pre_fwd_k(
   const float4 vg = affine4(ug, sc[C + c], sh[C + c]);
   const float4 vf = affine4(uf, sc[2 * C + c], sh[2 * C + c]);
   const float4 m2 = drop_mult4(rglu, (uint64_t)e), m3 = drop_mult4(rfc, (uint64_t)e);
-  float4 o;
-  o.x = g0 * (xv.x + yv.x) + g1 * pv.x + g2 * (va.x * sigmoidf(vg.x) * m2.x) + g3 * (fmaxf(vf.x, 0.f) * m3.x);
-  o.y = g0 * (xv.y + yv.y) + g1 * pv.y + g2 * (va.y * sigmoidf(vg.y) * m2.y) + g3 * (fmaxf(vf.y, 0.f) * m3.y);
-  o.z = g0 * (xv.z + yv.z) + g1 * pv.z + g2 * (va.z * sigmoidf(vg.z) * m2.z) + g3 * (fmaxf(vf.z, 0.f) * m3.z);
-  o.w = g0 * (xv.w + yv.w) + g1 * pv.w + g2 * (va.w * sigmoidf(vg.w) * m2.w) + g3 * (fmaxf(vf.w, 0.f) * m3.w);
+  const float4 o = mix_fwd4<kMixAll>(g0, g1, g2, g3, f4_add(xv, yv), pv, va, vg, vf, m2, m3);
   const float4 v = f4_add(o, rv);
   if (act) st4_w0<3>(pre + e, v);
   STAMP(0, smp * P + part, 3);
@@ -322,7 +318,7 @@ __global__ __launch_bounds__(256) void mixsum_pair_bwd_lazy_k(
 // sample lanes = one wave each).  A wave first sums the partials of ITS sample (n0 pairs from lnp0, n1 from lnp1 —
 // the head's and / or the later cell steps' K1 backward), then
 //   g = rstd (gy w - m1 - xhat m2)          LayerNorm input gradient (= gradient of the mix output and of the residual)
-// and the mix backward of node_mix_bwd_k.  BatchNorm reductions: registers over the chunk, LDS over the 4 sample
+// and the mix backward (mix_bwd4).  BatchNorm reductions: registers over the chunk, LDS over the 4 sample
 // lanes, one atomic pair per channel per workgroup.
 __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
     const float* __restrict__ gy, const float* __restrict__ pre, const float* __restrict__ ln_w,
@@ -343,14 +339,7 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
   const int c = r / l4n;
   const float g0 = gamma[0], g2 = gamma[2], g3 = gamma[3];
   const DropRt rglu = drop_begin(dglu), rfc = drop_begin(dfc);
-  float sc[3], sh[3], mu[3], rs[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    mu[k] = chan[k * C + c];
-    rs[k] = chan[M + k * C + c];
-    sc[k] = chan[2 * M + k * C + c];
-    sh[k] = chan[3 * M + k * C + c];
-  }
+  const ChanBn<3> bn = chan_load<3>(chan, M, C, c);
   const float4 lw = ld4(ln_w + (int64_t)r * 4);
   const float inv_d = 1.f / (float)(cl4 * 4);
   float dgam[4] = {0.f, 0.f, 0.f, 0.f};
@@ -394,36 +383,12 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
       if (gbuf != nullptr) st4_w0<6>(gbuf + e, gv);
       if (dresid != nullptr) st4_w0<6>(dresid + e, f4_add(gv, oldr));
       const float4 m2d = drop_mult4(rglu, (uint64_t)e), m3d = drop_mult4(rfc, (uint64_t)e);
-      const float gq[4] = {gv.x, gv.y, gv.z, gv.w};
-      const float uaq[4] = {ua.x, ua.y, ua.z, ua.w}, ugq[4] = {ug.x, ug.y, ug.z, ug.w},
-                  ufq[4] = {uf.x, uf.y, uf.z, uf.w};
-      const float xq[4] = {xv.x + yv.x, xv.y + yv.y, xv.z + yv.z, xv.w + yv.w};
-      const float pq[4] = {pv.x, pv.y, pv.z, pv.w};
-      const float m2q[4] = {m2d.x, m2d.y, m2d.z, m2d.w}, m3q[4] = {m3d.x, m3d.y, m3d.z, m3d.w};
-      float da[4], dg[4], df[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float va = fmaf(uaq[t], sc[0], sh[0]), vg = fmaf(ugq[t], sc[1], sh[1]), vf = fmaf(ufq[t], sc[2], sh[2]);
-        const float sg = sigmoidf(vg);
-        dgam[0] += gq[t] * xq[t];
-        dgam[1] += gq[t] * pq[t];
-        dgam[2] += gq[t] * (va * sg * m2q[t]);
-        dgam[3] += gq[t] * (fmaxf(vf, 0.f) * m3q[t]);
-        const float gm2 = g2 * gq[t] * m2q[t];
-        da[t] = gm2 * sg;
-        dg[t] = gm2 * va * sg * (1.f - sg);
-        df[t] = (vf > 0.f) ? g3 * gq[t] * m3q[t] : 0.f;
-        sw[0] += da[t] * (uaq[t] - mu[0]) * rs[0];
-        sw[1] += dg[t] * (ugq[t] - mu[1]) * rs[1];
-        sw[2] += df[t] * (ufq[t] - mu[2]) * rs[2];
-        sb[0] += da[t]; sb[1] += dg[t]; sb[2] += df[t];
-      }
-      st4_w0<6>(dV + ub, make_float4(da[0], da[1], da[2], da[3]));
-      st4_w0<6>(dV + ub + (int64_t)C * L, make_float4(dg[0], dg[1], dg[2], dg[3]));
-      st4_w0<6>(dV + ub + (int64_t)2 * C * L, make_float4(df[0], df[1], df[2], df[3]));
-      const float4 d0 = f4_scale(gv, g0);
-      if (dx != nullptr) st4_w0<6>(dx + e, f4_add((dy == nullptr) ? f4_scale(d0, 2.f) : d0, oldx));
-      if (dy != nullptr) st4_w0<6>(dy + e, f4_add(d0, oldy));
+      float4 da, dg, df;
+      mix_bwd4<kMixAll>(g2, g3, gv, f4_add(xv, yv), pv, ua, ug, uf, m2d, m3d, bn, dgam, da, dg, df, sw, sb);
+      st4_w0<6>(dV + ub, da);
+      st4_w0<6>(dV + ub + (int64_t)C * L, dg);
+      st4_w0<6>(dV + ub + (int64_t)2 * C * L, df);
+      mix_dxy_store([](float* p, float4 v) { st4_w0<6>(p, v); }, dx, dy, e, gv, g0, oldx, oldy);
     }
   }
   STAMP(3, blockIdx.y * gridDim.x + blockIdx.x, 2);

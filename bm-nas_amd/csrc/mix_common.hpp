@@ -1,15 +1,13 @@
-// Helpers shared by the sources that apply / differentiate the NodeMixedOp mix (bnmix.hip, lazyln.hip).
+// Helpers shared by the sources that apply / differentiate the NodeMixedOp mix as a launch of its own (bnmix.hip,
+// lazyln.hip, nodemix_sel.hip): row reductions, descriptor conversion, launch geometry.  The per-element arithmetic is
+// in mix_terms.hpp, which mixconv.hip and conv1x1.hip include on its own.
 #pragma once
 #include "common.hpp"
 #include "bn_fin.hpp"
+#include "mix_terms.hpp"
 #include "../../include/bmnas_hip.h"
 
 namespace {
-
-__device__ __forceinline__ float4 affine4(float4 u, float sc, float sh) {
-  return make_float4(fmaf(u.x, sc, sh), fmaf(u.y, sc, sh), fmaf(u.z, sc, sh), fmaf(u.w, sc, sh));
-}
-__device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + __expf(-v)); }
 
 // reduce v over the l4n adjacent lanes that share a channel row (l4n in {1, 2, 4})
 __device__ __forceinline__ float row_sum(float v, int l4n) {

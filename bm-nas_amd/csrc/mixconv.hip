@@ -12,6 +12,7 @@
 // out (the backward pass and later states read it).  The (C / 16)-fold recomputation of the slice across the
 // output tiles is 2 K elements each — nothing against a launch.
 #include "bn_fin.hpp"
+#include "mix_terms.hpp"
 #include "../../include/bmnas_hip.h"
 
 namespace {
@@ -31,11 +32,6 @@ struct MixConvArgs {
   float *V, *stat;
   int stat_shards, ldw, nsrc, b, C, L, Lb, spw, n_groups;
 };
-
-__device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + __expf(-v)); }
-__device__ __forceinline__ float4 aff4(float4 u, float sc, float sh) {
-  return make_float4(fmaf(u.x, sc, sh), fmaf(u.y, sc, sh), fmaf(u.z, sc, sh), fmaf(u.w, sc, sh));
-}
 
 template <int KPW>
 __global__ __launch_bounds__(256) void mix_conv_fwd_k(MixConvArgs a) {
@@ -92,7 +88,7 @@ __global__ __launch_bounds__(256) void mix_conv_fwd_k(MixConvArgs a) {
   }
   bn_fin_fill<256>(a.fin, a.chan, M3, a.b * L, sc, sh, blockIdx.x == 0);
 
-  // ---- s = g0 (x + y) + g1 p1 + g2 drop(glu) + g3 drop(relu(fc))  (the arithmetic of node_mix_fwd_k, bnmix.hip)
+  // ---- s = g0 (x + y) + g1 p1 + g2 drop(glu) + g3 drop(relu(fc))  (mix_fwd4, mix_terms.hpp)
 #pragma unroll
   for (int k = 0; k < kNv; ++k) {
     const int idx = t + 256 * k;
@@ -102,15 +98,11 @@ __global__ __launch_bounds__(256) void mix_conv_fwd_k(MixConvArgs a) {
       const int sg = bx * a.spw + sl;
       const bool valid = sg < a.b;
       const int64_t e = (int64_t)sg * C * L + (int64_t)rem * 4;
-      const float4 va = aff4(ua[k], sc[c], sh[c]);
-      const float4 vg = aff4(ug[k], sc[C + c], sh[C + c]);
-      const float4 vf = aff4(uf[k], sc[2 * C + c], sh[2 * C + c]);
+      const float4 va = affine4(ua[k], sc[c], sh[c]);
+      const float4 vg = affine4(ug[k], sc[C + c], sh[C + c]);
+      const float4 vf = affine4(uf[k], sc[2 * C + c], sh[2 * C + c]);
       const float4 m2 = drop_mult4(rglu, (uint64_t)e), m3 = drop_mult4(rfc, (uint64_t)e);
-      float4 o;
-      o.x = g0 * (xv[k].x + yv[k].x) + g1 * pv[k].x + g2 * (va.x * sigm(vg.x) * m2.x) + g3 * (fmaxf(vf.x, 0.f) * m3.x);
-      o.y = g0 * (xv[k].y + yv[k].y) + g1 * pv[k].y + g2 * (va.y * sigm(vg.y) * m2.y) + g3 * (fmaxf(vf.y, 0.f) * m3.y);
-      o.z = g0 * (xv[k].z + yv[k].z) + g1 * pv[k].z + g2 * (va.z * sigm(vg.z) * m2.z) + g3 * (fmaxf(vf.z, 0.f) * m3.z);
-      o.w = g0 * (xv[k].w + yv[k].w) + g1 * pv[k].w + g2 * (va.w * sigm(vg.w) * m2.w) + g3 * (fmaxf(vf.w, 0.f) * m3.w);
+      const float4 o = mix_fwd4<kMixAll>(g0, g1, g2, g3, f4_add(xv[k], yv[k]), pv[k], va, vg, vf, m2, m3);
       st4(Af + c * kLd + sl * L + 4 * l4, valid ? o : make_float4(0.f, 0.f, 0.f, 0.f));
       if (by == 0 && valid) st4_wtg<4>(a.mix_out + e, o);
     }

@@ -5,8 +5,9 @@
 //   s = sum_{p present} gamma[col(p)] * term_p,   term_Sum = x + y,  term_Attn = p1,
 //       term_GLU = drop(glu(BN(U[:, glu rows]))),  term_FC = drop(relu(BN(U[:, fc rows])))
 //
-// The arithmetic is that of node_mix_fwd_k / node_mix_bwd_k (bnmix.hip) for the default list; here the kernels are
-// specialised at compile time on the presence mask (bit 0 Sum, 1 ScaleDotAttn, 2 LinearGLU, 3 ConcatFC), so that an
+// The arithmetic is mix_fwd4 / mix_bwd4 of mix_terms.hpp, which node_mix_fwd_k / node_mix_bwd_k (bnmix.hip) compile for
+// the default list (mask 15); here the kernels are specialised at compile time on the presence mask (bit 0 Sum,
+// 1 ScaleDotAttn, 2 LinearGLU, 3 ConcatFC), so that an
 // absent term costs no load, no store, no reduction and no LDS, and U holds only the present conv rows
 // (M = 2C [GLU] + C [FC], GLU rows first).  Which gamma column belongs to which kind comes with the launch (Sel).
 #include "common.hpp"
@@ -15,8 +16,6 @@
 #include "mix_common.hpp"
 
 namespace {
-
-enum { kSum = 1, kAttn = 2, kGlu = 4, kFc = 8 };
 
 struct Sel {
   int col[4];      // gamma column of Sum | ScaleDotAttn | LinearGLU | ConcatFC (unused where absent)
@@ -28,7 +27,7 @@ __global__ __launch_bounds__(256) void node_mix_sel_fwd_k(
     const float* __restrict__ U, float* __restrict__ chan, BnFin fin, const float* __restrict__ gamma, Sel sel,
     float* __restrict__ out, int b, int C, int L, DropCfg dglu, DropCfg dfc) {
   constexpr bool hS = MASK & kSum, hA = MASK & kAttn, hG = MASK & kGlu, hF = MASK & kFc;
-  constexpr int MC = (hG ? 2 : 0) + (hF ? 1 : 0), FO = hG ? 2 : 0;     // U rows / C; first ConcatFC row / C
+  constexpr int MC = MixRows<MASK>::kMc, FO = MixRows<MASK>::kFo;      // U rows / C; first ConcatFC row / C
   extern __shared__ float fin_lds[];
   const int cl4 = C * L / 4, l4n = L / 4, M = MC * C;
   float* sc = fin_lds;
@@ -49,30 +48,20 @@ __global__ __launch_bounds__(256) void node_mix_sel_fwd_k(
     const int c = r / l4n;
     const int64_t e = i * 4;
     const int64_t ub = ((int64_t)s * M) * L + (int64_t)r * 4;      // (s, c, l) inside U's first C block
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (hS) o = f4_scale(f4_add(ld4(x + e), ld4(y + e)), gS);
-    if constexpr (hA) {
-      const float4 pv = ld4(p1 + e);
-      o.x = fmaf(gA, pv.x, o.x); o.y = fmaf(gA, pv.y, o.y); o.z = fmaf(gA, pv.z, o.z); o.w = fmaf(gA, pv.w, o.w);
-    }
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 xy = zero, pv = zero, va = zero, vg = zero, vf = zero, m2 = zero, m3 = zero;
+    if constexpr (hS) xy = f4_add(ld4(x + e), ld4(y + e));
+    if constexpr (hA) pv = ld4(p1 + e);
     if constexpr (hG) {
-      const float4 va = affine4(ld4(U + ub), sc[c], sh[c]);
-      const float4 vg = affine4(ld4(U + ub + (int64_t)C * L), sc[C + c], sh[C + c]);
-      const float4 m2 = drop_mult4(rglu, (uint64_t)e);
-      o.x += gG * (va.x * sigmoidf(vg.x) * m2.x);
-      o.y += gG * (va.y * sigmoidf(vg.y) * m2.y);
-      o.z += gG * (va.z * sigmoidf(vg.z) * m2.z);
-      o.w += gG * (va.w * sigmoidf(vg.w) * m2.w);
+      va = affine4(ld4(U + ub), sc[c], sh[c]);
+      vg = affine4(ld4(U + ub + (int64_t)C * L), sc[C + c], sh[C + c]);
+      m2 = drop_mult4(rglu, (uint64_t)e);
     }
     if constexpr (hF) {
-      const float4 vf = affine4(ld4(U + ub + (int64_t)FO * C * L), sc[FO * C + c], sh[FO * C + c]);
-      const float4 m3 = drop_mult4(rfc, (uint64_t)e);
-      o.x += gF * (fmaxf(vf.x, 0.f) * m3.x);
-      o.y += gF * (fmaxf(vf.y, 0.f) * m3.y);
-      o.z += gF * (fmaxf(vf.z, 0.f) * m3.z);
-      o.w += gF * (fmaxf(vf.w, 0.f) * m3.w);
+      vf = affine4(ld4(U + ub + (int64_t)FO * C * L), sc[FO * C + c], sh[FO * C + c]);
+      m3 = drop_mult4(rfc, (uint64_t)e);
     }
-    st4_wtg<2>(out + e, o);
+    st4_wtg<2>(out + e, mix_fwd4<MASK>(gS, gA, gG, gF, xy, pv, va, vg, vf, m2, m3));
   }
 }
 
@@ -87,8 +76,8 @@ __global__ __launch_bounds__(256) void node_mix_sel_bwd_k(
     uint32_t acc_mask, float* __restrict__ dV, float* bn_grad, int b, int C, int L, int chunk, DropCfg dglu,
     DropCfg dfc) {
   constexpr bool hS = MASK & kSum, hA = MASK & kAttn, hG = MASK & kGlu, hF = MASK & kFc;
-  constexpr int MC = (hG ? 2 : 0) + (hF ? 1 : 0), FO = hG ? 2 : 0;
-  constexpr int NB = MC > 0 ? MC : 1;                  // (array extents; nothing of them is touched when MC == 0)
+  constexpr int MC = MixRows<MASK>::kMc, FO = MixRows<MASK>::kFo;
+  constexpr int NB = MixRows<MASK>::kNb;               // (array extents; nothing of them is touched when MC == 0)
   __shared__ float red16[16];
   __shared__ float csum[3][2 * NB][64];
   const int cl4 = C * L / 4, l4n = L / 4, M = MC * C;
@@ -103,19 +92,9 @@ __global__ __launch_bounds__(256) void node_mix_sel_bwd_k(
   DropRt rglu{}, rfc{};
   if constexpr (hG) rglu = drop_begin(dglu);
   if constexpr (hF) rfc = drop_begin(dfc);
-  float sc[NB], sh[NB], mu[NB], rs[NB], sw[NB], sb[NB];
-#pragma unroll
-  for (int k = 0; k < NB; ++k) {
-    sw[k] = sb[k] = 0.f;
-    if constexpr (MC > 0) {
-      mu[k] = chan[k * C + c];
-      rs[k] = chan[M + k * C + c];
-      sc[k] = chan[2 * M + k * C + c];
-      sh[k] = chan[3 * M + k * C + c];
-    } else {
-      mu[k] = rs[k] = sc[k] = sh[k] = 0.f;
-    }
-  }
+  ChanBn<NB> bn{};
+  if constexpr (MC > 0) bn = chan_load<NB>(chan, M, C, c);
+  float sw[NB] = {}, sb[NB] = {};
   float dgam[4] = {0.f, 0.f, 0.f, 0.f};
   const int s_beg = blockIdx.y * chunk;
   int s_end = s_beg + chunk;
@@ -125,64 +104,31 @@ __global__ __launch_bounds__(256) void node_mix_sel_bwd_k(
       const int64_t e = ((int64_t)s * cl4 + r) * 4;
       const int64_t ub = ((int64_t)s * M) * L + (int64_t)r * 4;
       const float4 gv = ld4(g + e);
-      const float gq[4] = {gv.x, gv.y, gv.z, gv.w};
-      if constexpr (hS) {
-        const float4 xy = f4_add(ld4(x + e), ld4(y + e));
-        dgam[0] += f4_dot(gv, xy);
-      }
-      if constexpr (hA) dgam[1] += f4_dot(gv, ld4(p1 + e));
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 xy = zero, pv = zero, ua = zero, ug = zero, uf = zero, m2 = zero, m3 = zero;
+      if constexpr (hS) xy = f4_add(ld4(x + e), ld4(y + e));
+      if constexpr (hA) pv = ld4(p1 + e);
       if constexpr (hG) {
-        const float4 ua = ld4(U + ub), ug = ld4(U + ub + (int64_t)C * L);
-        const float4 m2 = drop_mult4(rglu, (uint64_t)e);
-        const float uaq[4] = {ua.x, ua.y, ua.z, ua.w}, ugq[4] = {ug.x, ug.y, ug.z, ug.w};
-        const float m2q[4] = {m2.x, m2.y, m2.z, m2.w};
-        float da[4], dg[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const float va = fmaf(uaq[t], sc[0], sh[0]), vg = fmaf(ugq[t], sc[1], sh[1]);
-          const float sg = sigmoidf(vg);
-          dgam[2] += gq[t] * (va * sg * m2q[t]);
-          const float gm2 = gG * gq[t] * m2q[t];
-          da[t] = gm2 * sg;
-          dg[t] = gm2 * va * sg * (1.f - sg);
-          sw[0] += da[t] * (uaq[t] - mu[0]) * rs[0];
-          sw[1] += dg[t] * (ugq[t] - mu[1]) * rs[1];
-          sb[0] += da[t]; sb[1] += dg[t];
-        }
-        st4_wtg<2>(dV + ub, make_float4(da[0], da[1], da[2], da[3]));
-        st4_wtg<2>(dV + ub + (int64_t)C * L, make_float4(dg[0], dg[1], dg[2], dg[3]));
+        ua = ld4(U + ub);
+        ug = ld4(U + ub + (int64_t)C * L);
+        m2 = drop_mult4(rglu, (uint64_t)e);
       }
       if constexpr (hF) {
-        const float4 uf = ld4(U + ub + (int64_t)FO * C * L);
-        const float4 m3 = drop_mult4(rfc, (uint64_t)e);
-        const float ufq[4] = {uf.x, uf.y, uf.z, uf.w}, m3q[4] = {m3.x, m3.y, m3.z, m3.w};
-        float df[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const float vf = fmaf(ufq[t], sc[FO], sh[FO]);
-          dgam[3] += gq[t] * (fmaxf(vf, 0.f) * m3q[t]);
-          df[t] = (vf > 0.f) ? gF * gq[t] * m3q[t] : 0.f;
-          sw[FO] += df[t] * (ufq[t] - mu[FO]) * rs[FO];
-          sb[FO] += df[t];
-        }
-        st4_wtg<2>(dV + ub + (int64_t)FO * C * L, make_float4(df[0], df[1], df[2], df[3]));
+        uf = ld4(U + ub + (int64_t)FO * C * L);
+        m3 = drop_mult4(rfc, (uint64_t)e);
       }
+      float4 da, dg, df;
+      mix_bwd4<MASK>(gG, gF, gv, xy, pv, ua, ug, uf, m2, m3, bn, dgam, da, dg, df, sw, sb);
+      if constexpr (hG) {
+        st4_wtg<2>(dV + ub, da);
+        st4_wtg<2>(dV + ub + (int64_t)C * L, dg);
+      }
+      if constexpr (hF) st4_wtg<2>(dV + ub + (int64_t)FO * C * L, df);
       if constexpr (hS) {
-        const float4 d0 = f4_scale(gv, gS);
-        if (dx != nullptr) {
-          float4 v = (dy == nullptr) ? f4_scale(d0, 2.f) : d0;
-          if (acc_mask & 1u) v = f4_add(v, ld4(dx + e));
-          st4_wtg<2>(dx + e, v);
-        }
-        if (dy != nullptr) {
-          float4 v = d0;
-          if (acc_mask & 2u) v = f4_add(v, ld4(dy + e));
-          st4_wtg<2>(dy + e, v);
-        }
+        mix_dxy_store([](float* p, float4 v) { st4_wtg<2>(p, v); }, dx, dy, e, gv, gS, acc_mask);
       } else {
         // no Sum term: this launch contributes nothing to dx / dy — a destination that nobody wrote yet is
         // cleared, so that the conv / attention gradients behind it can accumulate
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
         if (dx != nullptr && !(acc_mask & 1u)) st4_wtg<2>(dx + e, zero);
         if (dy != nullptr && !(acc_mask & 2u)) st4_wtg<2>(dy + e, zero);
       }
