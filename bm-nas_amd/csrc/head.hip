@@ -655,10 +655,10 @@ static int head_fwd_impl(const float* const* srcs, const float* const* sums, int
   if (hb_part != nullptr) {
     // the k-slices in order (padding floats of a slice are never written: sum exactly 3 b O, rounded down to a
     // multiple of four, and the tail by hand)
+    // (n = 3: b = 1, O = 1 — no float4 at all, the tail alone; workgroup 0 sums it, so there is always one)
     const long long n = (long long)3 * b * O, n4 = n / 4 * 4;
-    if (n4 > 0)
-      hipLaunchKernelGGL(sum_chunks_strided_k, dim3((unsigned)std::min<long long>((n4 / 4 + 255) / 256, 2048)), dim3(256),
-                         0, st, hb_part, hb, a.KS, n4 / 4, a.hb_stride, n - n4);
+    hipLaunchKernelGGL(sum_chunks_strided_k, dim3((unsigned)std::max<long long>(1, std::min<long long>((n4 / 4 + 255) / 256, 2048))),
+                       dim3(256), 0, st, hb_part, hb, a.KS, n4 / 4, a.hb_stride, n - n4);
     BMNAS_CHECK_LAUNCH();
   }
   return 0;
@@ -707,6 +707,7 @@ static int head_bwd_impl(const float* const* srcs, const float* const* sums, flo
   HeadBwdArgs a{};
   if (!srcs || n_src < 1) return BMNAS_E_ARG;
   if (n_src > kHeadSrc) return BMNAS_E_LIMIT;
+  if (part && O > n_src * C * L) return BMNAS_E_SHAPE;          // dbias lives in ONE row of part (D floats): O <= D
   for (int q = 0; q < n_src; ++q) {
     if (!srcs[q] || (!lazy && (!sums || !sums[q]))) return BMNAS_E_ARG;
     a.src.p[q] = srcs[q];
@@ -765,6 +766,7 @@ extern "C" int bmnas_head_bwd_lazy(const bmnas_lazy_ln_t* lazy, float* const* ln
                                    int L, int O, float* scrub, int64_t scrub_n, float* loss_part, void* stream) {
   if (!lazy || !lnpart || n_src < 1) return BMNAS_E_ARG;
   if (n_src > kHeadSrc) return BMNAS_E_LIMIT;
+  if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;             // (as the forward half: the sources are its family's)
   HeadLazy z{};
   const float* srcs[kHeadSrc] = {nullptr, nullptr, nullptr, nullptr};
   for (int q = 0; q < n_src; ++q) {

@@ -445,7 +445,7 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
 BMNAS_DEFINE_STAMP_SETTER(bmnas_debug_stamps)
 
 extern "C" int bmnas_lazy_ln_ok(int C, int L) {
-  return C >= 1 && L >= 4 && L % 4 == 0 && L <= 16 && lazy_parts(C * L / 4) <= kLazyMaxParts;
+  return C >= 1 && (L == 4 || L == 8 || L == 16) && lazy_parts(C * L / 4) <= kLazyMaxParts;
 }
 
 extern "C" int bmnas_lazy_ln_parts(int C, int L) {
@@ -459,7 +459,7 @@ extern "C" int bmnas_node_mix_pre_fwd(const float* x, const float* y, const floa
                                       bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream) {
   if (!x || !y || !p1 || !U || !chan || !gamma || !resid || !ln_w || !ln_b || !pre || !rec || !prm || b < 0 || C < 1)
     return BMNAS_E_ARG;
-  if (L % 4 || L > 16 || L < 4) return BMNAS_E_SHAPE;
+  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
   if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;
   BnFin f;
   if (int e = to_fin(fin, &f)) return e;
@@ -589,6 +589,7 @@ extern "C" int bmnas_node_mix_lnp_bwd(const float* g, const float* pre, const fl
     return BMNAS_E_ARG;
   if (accumulate_resid && !dresid) return BMNAS_E_ARG;
   if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;             // (pre / stats come from the producer's family)
   if (b == 0) return 0;
   const int cl4 = C * L / 4;
   // one sample per thread while that still leaves the BatchNorm sums <= ~64 adds per address; longer walks above

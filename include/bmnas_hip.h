@@ -627,7 +627,7 @@ int bmnas_head_fwd(const float* const* srcs, const float* const* sums, int n_src
  *   gscale (nullable): device scalar multiplying dlogits.
  * Batch reductions leave as per-sample-chunk partials (16 or 32 samples; n_chunk = bmnas_head_chunks(b)):
  *   part [n_chunk][O + 3][D]: rows 0..O-1 = dW, row O = dln_w, row O+1 = dln_b, row O+2 = dbias in its
- *   first O entries (the rest of that row is never written);
+ *   first O entries (the rest of that row is never written; hence O <= D when part is given, BMNAS_E_SHAPE otherwise);
  * sum them with bmnas_backward_epilogue(n_sums ...) or bmnas_sum_chunks.
  * scrub: optional zero-fill side job (the caller's backward accumulation arena). */
 int bmnas_head_chunks(int b);
@@ -665,7 +665,8 @@ int bmnas_sum_chunks(const float* part, float* out, int n_chunk, int64_t n, void
  *   bmnas_node_mix_lnp_bwd       bmnas_node_mix_ln_bwd for any batch size: g = gradient of the node output, m1 / m2
  *                                of the LayerNorm backward from the partials lnp0 (b, n0, 2) and lnp1 (b, n1, 2)
  *                                (either may be absent: n = 0), then the mix backward of bmnas_node_mix_bwd.
- * bmnas_lazy_ln_ok: L in {4, 8, 16} and C*L <= 4096. */
+ * bmnas_lazy_ln_ok: L in {4, 8, 16} and C*L <= 4096.  Outside it every entry point of the family refuses: BMNAS_E_LIMIT,
+ * except that bmnas_node_mix_pre_fwd and bmnas_node_mix_lnp_bwd answer an L outside {4, 8, 16} with BMNAS_E_SHAPE. */
 typedef struct {
   const float* pre;    /* (b, C, L) mix + x, before the LayerNorm */
   const float* rec;    /* (b, P, 8) moment records (forward consumers) */
