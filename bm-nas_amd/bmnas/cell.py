@@ -665,7 +665,7 @@ def node_mixed_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_stride=
 # ------------------------------------------- NodeMixedOp over an edited STEP_STEP_PRIMITIVES list (csrc/nodemix_sel.hip)
 def node_mixed_sel_fwd(x, y, gamma_row, P, training):
     """NodeMixedOp.forward (node_operations.py:118-120) for a list P.prims that is a subset / permutation of the four
-    built-in primitives: the launches of node_mixed_fwd over the PRESENT terms — the attention branch (inside the
+    built-in primitives ('ConcatFC' names the FC slot: with P.fc_act = lib.FC_ACT_MISH it is CatConvMish): the launches of node_mixed_fwd over the PRESENT terms — the attention branch (inside the
     conv GEMM launch when x is y and a conv is present), ONE conv GEMM over the present conv rows (P.M of them; the
     x-is-y weight fold at that M), bn_finalize, and the selected-term combine.  No conv: no GEMM and no BatchNorm
     launch; ['Sum'] alone: the combine only.  One dropout site per primitive that owns one, issued in LIST order."""
@@ -711,7 +711,7 @@ def node_mixed_sel_fwd(x, y, gamma_row, P, training):
         lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, b, C, L, sv.d_attn)
     out = torch.empty_like(x)
     lib.node_mix_sel_fwd(x if has_sum else None, y if has_sum else None, sv.p1, U, chan, gamma_row, sv.sel, out,
-                         b, C, L, sv.d_glu, sv.d_fc, fin)
+                         b, C, L, sv.d_glu, sv.d_fc, fin, fc_act=P.fc_act)
     return out, sv
 
 
@@ -735,7 +735,8 @@ def node_mixed_sel_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_str
             dyb = y_slot.buf()
             acc |= y_slot.acc_bit() << 1
     lib.node_mix_sel_bwd(g, x if has_sum else None, y if has_sum else None, sv.p1, U, chan, sv.gamma, sv.sel,
-                         dgamma_row, dxb, dyb, acc, dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride)
+                         dgamma_row, dxb, dyb, acc, dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride,
+                         fc_act=P.fc_act)
     slots = [x_slot] if sv.same else [x_slot, y_slot]
     if has_attn:
         gcol = sv.gamma[sv.attn_col:sv.attn_col + 1]

@@ -391,6 +391,43 @@ class SdpaLnFn(Function):
         return dx, dy, dw, db, None, None
 
 
+class SdpaLnThruFn(Function):
+    """SdpaLnFn whose two inputs are ALSO handed back as outputs: -> (out, x', y'), for a discrete step node that reads
+    an inner state again after this op (Found_NodeCell.forward: a later inner step, the out_conv tail, the residual).
+    The later readers take the alias, their gradient arrives here as the grad_output of it, and the backward launch
+    ACCUMULATES onto that tensor in place (the kernel's accumulate mask) instead of leaving an `at::add` launch to the
+    engine — ConvBnActThruFn's arrangement, under the same condition (the arriving gradient is the fresh result of the
+    later reader's backward; no retain_grad / hooks on these inner tensors)."""
+
+    @staticmethod
+    def forward(ctx, x, y, ln_w, ln_b, p, training):
+        out = SdpaLnFn.forward(ctx, x, y, ln_w, ln_b, p, training)
+        ctx.set_materialize_grads(False)
+        return out, x.view_as(x), y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, g, gx, gy):
+        if g is None:                       # only the handed-back inputs were differentiated: identity
+            return gx, gy, None, None, None, None
+        x, y = ctx.x, ctx.y
+        b, C, L = x.shape
+        onto = lambda t: (t is not None and t.shape == x.shape and t.is_contiguous() and t.dtype == torch.float32
+                          and t.device == x.device and t.data_ptr() % 16 == 0)
+        dx = gx if onto(gx) else torch.empty_like(x)
+        dy = gy if onto(gy) and gy is not gx else torch.empty_like(y)
+        acc = (1 if dx is gx else 0) | (2 if dy is gy else 0)
+        dw, db = _zero_pair(ctx.lw)
+        g = _c(g)
+        lib.sdpa_ln_bwd(g, None, x, y, ctx.lw, ctx.xhat, ctx.stats, dx, dy, acc, b, C, L, ctx.drop)
+        _ln_affine(g, [ctx.xhat], None, None, None, None, dw, db, b, C, L, False, True,
+                   key=ctx.lw.data_ptr(), leaf=ctx.leaf)
+        if gx is not None and dx is not gx:
+            dx = dx + gx                    # (an arrival that cannot be accumulated onto: the engine's way)
+        if gy is not None and dy is not gy:
+            dy = dy + gy
+        return dx, dy, dw, db, None, None
+
+
 # ------------------------------------------------- conv1x1 + BN + {GLU | ReLU} + dropout
 class _ZeroPool:
     """Zero-filled scratch for the gradients that the standalone conv + BatchNorm modules accumulate with
@@ -490,13 +527,15 @@ FUSE_STANDALONE_BN = K.FUSE_BN_FINALIZE
 
 
 class ConvBnActFn(Function):
-    """cat(srcs) -> Conv1d(k=1) -> BatchNorm1d -> glu(dim=1) | relu -> Dropout(p).
-    LinearGLU (node_operations.py:30-39), ConcatFC (:49-56), NodeCell out_conv
+    """cat(srcs) -> Conv1d(k=1) -> BatchNorm1d -> glu(dim=1) | relu | mish -> Dropout(p).
+    LinearGLU (node_operations.py:30-39), ConcatFC (:49-56), CatConvMish (:74-82), NodeCell out_conv
     (node_search.py:59-64).  bn buffers are updated in place in training mode."""
 
     @staticmethod
     def forward(ctx, act, p, training, rm, rv, nbt, conv_w, conv_b, bn_w, bn_b, *srcs):
         _require_gpu(srcs[0], 'conv1x1 + BatchNorm')
+        if act not in ('glu', 'relu', 'mish'):               # before anything is launched or a buffer is updated
+            raise ValueError(f'conv1x1 + BatchNorm: no kernel for the activation {act!r}')
         srcs = [_c(_f32(s)) for s in srcs]
         b, C_src, L = srcs[0].shape
         M = conv_w.shape[0]
@@ -516,7 +555,7 @@ class ConvBnActFn(Function):
         else:
             out = torch.empty((b, M, L), device=U.device, dtype=torch.float32)
             drop = K.DROP.make(p, out.numel(), training)
-            lib.bn_relu_fwd(U, chan, out, b, M, L, drop, sv.fin)
+            (lib.bn_mish_fwd if act == 'mish' else lib.bn_relu_fwd)(U, chan, out, b, M, L, drop, sv.fin)
         ctx.act, ctx.sv, ctx.drop, ctx.wshape = act, sv, drop, tuple(conv_w.shape)
         if any(ctx.needs_input_grad):
             ZERO_POOL.announce(2 * M + M * sv.ldw + M)
@@ -537,6 +576,8 @@ class ConvBnActFn(Function):
         dbias = zero[2 * M + M * sv.ldw:]
         if act == 'glu':
             lib.bn_glu_bwd(g, U, sv.chan, dV, bn_grad, b, M // 2, L, ctx.drop)
+        elif act == 'mish':
+            lib.bn_mish_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
         else:
             lib.bn_relu_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
         slots = [K.GradSlot(s) if ctx.needs_input_grad[10 + q] else None for q, s in enumerate(sv.srcs)]
@@ -577,6 +618,8 @@ class ConvBnActThruFn(Function):
         dbias = zero[2 * M + M * sv.ldw:]
         if act == 'glu':
             lib.bn_glu_bwd(g, U, sv.chan, dV, bn_grad, b, M // 2, L, ctx.drop)
+        elif act == 'mish':
+            lib.bn_mish_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
         else:
             lib.bn_relu_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
         slots = []
@@ -919,7 +962,7 @@ class NodeMixedFn(Function):
 
 class NodeMixedSelFn(Function):
     """NodeMixedOp.forward(x, y, weights) (node_operations.py:118-120) over an edited STEP_STEP_PRIMITIVES list — a
-    subset / permutation of Sum, ScaleDotAttn, LinearGLU, ConcatFC (op._prims) — as the fused sequence of NodeMixedFn
+    subset / permutation of Sum, ScaleDotAttn, LinearGLU, ConcatFC | CatConvMish (op._prims) — as the fused sequence of NodeMixedFn
     restricted to the present terms (bmnas.cell.node_mixed_sel_fwd).  gamma_row / its gradient: len(op._prims)."""
 
     @staticmethod

@@ -187,6 +187,10 @@ SIGNATURES = {
     'bmnas_node_mix_sel_fwd': ([_P, _P, _P, _P, _P, BnFin, _P, NodeSel, _P, _I, _I, _I, Dropout, Dropout, _P], _I),
     'bmnas_node_mix_sel_bwd': ([_P, _P, _P, _P, _P, _P, _P, NodeSel, _P, _I, _I64, _P, _P, _U32, _P, _P, _I, _I, _I,
                                 Dropout, Dropout, _P], _I),
+    'bmnas_node_mix_sel_act_fwd': ([_P, _P, _P, _P, _P, BnFin, _P, NodeSel, _P, _I, _I, _I, Dropout, Dropout, _I,
+                                    _P], _I),
+    'bmnas_node_mix_sel_act_bwd': ([_P, _P, _P, _P, _P, _P, _P, NodeSel, _P, _I, _I64, _P, _P, _U32, _P, _P, _I, _I,
+                                    _I, Dropout, Dropout, _I, _P], _I),
     'bmnas_node_mix_ln_bwd_ok': ([_I, _I, _I], _I),
     'bmnas_node_mix_ln_bwd': ([_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _P, _P, _U32,
                                _P, _P, _I, _I, _I, Dropout, Dropout, _P], _I),
@@ -194,6 +198,8 @@ SIGNATURES = {
     'bmnas_bn_glu_bwd': ([_P, _P, _P, _P, _P, _I, _I, _I, Dropout, _P], _I),
     'bmnas_bn_relu_fwd': ([_P, _P, BnFin, _P, _I, _I, _I, Dropout, _P], _I),
     'bmnas_bn_relu_bwd': ([_P, _P, _P, _P, _P, _I, _I, _I, Dropout, _P], _I),
+    'bmnas_bn_mish_fwd': ([_P, _P, BnFin, _P, _I, _I, _I, Dropout, _P], _I),
+    'bmnas_bn_mish_bwd': ([_P, _P, _P, _P, _P, _I, _I, _I, Dropout, _P], _I),
     'bmnas_adaptive_maxpool_fwd_group': ([C.POINTER(PoolProb), _I, _I, _P], _I),
     'bmnas_adaptive_maxpool_bwd_group': ([C.POINTER(PoolProb), _I, _I, _P], _I),
     'bmnas_conv1x1_group_ok': ([_I, C.POINTER(C.c_int), _I, _I, _I], _I),
@@ -863,6 +869,9 @@ def node_mix_bwd(g, x, y, p1, U, chan, gamma, dgamma, dx, dy, acc_mask, dV, bn_g
 # ------------------------------------------------- NodeMixedOp over an edited primitive list (csrc/nodemix_sel.hip)
 NODE_SEL_LAUNCHES = {'fwd': 0, 'bwd': 0}     # launches issued by the two wrappers below (tests/test_node_prims_gpu.py)
 NODE_KINDS = ('Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC')
+# fc_act of the two wrappers: what the FC slot (ConcatFC's column, rows and dropout site) applies behind its BatchNorm.
+# CatConvMish takes the slot under ConcatFC's name in the descriptor, with FC_ACT_MISH beside it.
+FC_ACT_RELU, FC_ACT_MISH = 0, 1
 
 
 def make_node_sel(prims):
@@ -882,18 +891,21 @@ def node_mix_sel_ok(mask, b, Cc, L):
     return bool(load().bmnas_node_mix_sel_ok(int(mask), int(b), int(Cc), int(L)))
 
 
-def node_mix_sel_fwd(x, y, p1, U, chan, gamma, sel, out, b, Cc, L, dglu=NO_DROP, dfc=NO_DROP, fin=NO_FIN):
-    _check(load().bmnas_node_mix_sel_fwd(_ptr(x), _ptr(y), _ptr(p1), _ptr(U), _ptr(chan), fin, gamma.data_ptr(), sel,
-                                         _ptr(out), b, Cc, L, dglu, dfc, _stream()), 'node_mix_sel_fwd')
+def node_mix_sel_fwd(x, y, p1, U, chan, gamma, sel, out, b, Cc, L, dglu=NO_DROP, dfc=NO_DROP, fin=NO_FIN,
+                     fc_act=FC_ACT_RELU):
+    _check(load().bmnas_node_mix_sel_act_fwd(_ptr(x), _ptr(y), _ptr(p1), _ptr(U), _ptr(chan), fin, gamma.data_ptr(),
+                                             sel, _ptr(out), b, Cc, L, dglu, dfc, int(fc_act), _stream()),
+           'node_mix_sel_fwd')
     NODE_SEL_LAUNCHES['fwd'] += 1
 
 
 def node_mix_sel_bwd(g, x, y, p1, U, chan, gamma, sel, dgamma, dx, dy, acc_mask, dV, bn_grad, b, Cc, L,
-                     dglu=NO_DROP, dfc=NO_DROP, dg_shards=1, dg_stride=0):
-    _check(load().bmnas_node_mix_sel_bwd(_ptr(g), _ptr(x), _ptr(y), _ptr(p1), _ptr(U), _ptr(chan), gamma.data_ptr(),
-                                         sel, None if dgamma is None else dgamma.data_ptr(), dg_shards, dg_stride,
-                                         _ptr(dx), _ptr(dy), acc_mask, _ptr(dV), _ptr(bn_grad), b, Cc, L, dglu, dfc,
-                                         _stream()), 'node_mix_sel_bwd')
+                     dglu=NO_DROP, dfc=NO_DROP, dg_shards=1, dg_stride=0, fc_act=FC_ACT_RELU):
+    _check(load().bmnas_node_mix_sel_act_bwd(_ptr(g), _ptr(x), _ptr(y), _ptr(p1), _ptr(U), _ptr(chan),
+                                             gamma.data_ptr(), sel, None if dgamma is None else dgamma.data_ptr(),
+                                             dg_shards, dg_stride, _ptr(dx), _ptr(dy), acc_mask, _ptr(dV),
+                                             _ptr(bn_grad), b, Cc, L, dglu, dfc, int(fc_act), _stream()),
+           'node_mix_sel_bwd')
     NODE_SEL_LAUNCHES['bwd'] += 1
 
 
@@ -928,6 +940,16 @@ def bn_relu_fwd(U, chan, out, b, M, L, drop, fin=NO_FIN):
 def bn_relu_bwd(g, U, chan, dV, bn_grad, b, M, L, drop):
     _check(load().bmnas_bn_relu_bwd(_ptr(g), _ptr(U), _ptr(chan), _ptr(dV), _ptr(bn_grad), b, M, L, drop,
                                     _stream()), 'bn_relu_bwd')
+
+
+def bn_mish_fwd(U, chan, out, b, M, L, drop, fin=NO_FIN):
+    _check(load().bmnas_bn_mish_fwd(_ptr(U), _ptr(chan), fin, _ptr(out), b, M, L, drop, _stream()),
+           'bn_mish_fwd')
+
+
+def bn_mish_bwd(g, U, chan, dV, bn_grad, b, M, L, drop):
+    _check(load().bmnas_bn_mish_bwd(_ptr(g), _ptr(U), _ptr(chan), _ptr(dV), _ptr(bn_grad), b, M, L, drop,
+                                    _stream()), 'bn_mish_bwd')
 
 
 def bn_relu_ln_fwd_pair_ok(b, Cc, L, n_prev):

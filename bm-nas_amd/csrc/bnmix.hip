@@ -9,6 +9,7 @@
 #include "arch_body.hpp"
 #include "bn_fin.hpp"
 #include "mix_common.hpp"
+#include "mish.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -617,6 +618,9 @@ __global__ __launch_bounds__(256) void bn_glu_bwd_k(const float* __restrict__ g,
   }
 }
 
+// standalone BatchNorm + activation + dropout tail: ACT = kActRelu (ConcatFC, out_conv, the reshape layers) |
+// kActMish (CatConvMish, reference node_operations.py:58-82)
+template <int ACT = kActRelu>
 __device__ __forceinline__ void bn_relu_fwd_body(const float* __restrict__ U, float* __restrict__ chan,
                                                  const BnFin& fin, float* __restrict__ out, int b, int M, int L,
                                                  const DropCfg& d, const int bx, const int nbx, float* fin_lds) {
@@ -631,8 +635,13 @@ __device__ __forceinline__ void bn_relu_fwd_body(const float* __restrict__ U, fl
     const int c = r / l4n;
     const float4 v = affine4(ld4(U + i * 4), sc[c], sh[c]);
     const float4 m = drop_mult4(dr, (uint64_t)(i * 4));
-    st4_wtg<2>(out + i * 4, make_float4(fmaxf(v.x, 0.f) * m.x, fmaxf(v.y, 0.f) * m.y,
-                                  fmaxf(v.z, 0.f) * m.z, fmaxf(v.w, 0.f) * m.w));
+    if constexpr (ACT == kActMish) {
+      const float4 a = act4(v, 1);
+      st4_wtg<2>(out + i * 4, make_float4(a.x * m.x, a.y * m.y, a.z * m.z, a.w * m.w));
+    } else {
+      st4_wtg<2>(out + i * 4, make_float4(fmaxf(v.x, 0.f) * m.x, fmaxf(v.y, 0.f) * m.y,
+                                    fmaxf(v.z, 0.f) * m.z, fmaxf(v.w, 0.f) * m.w));
+    }
   }
 }
 
@@ -642,6 +651,14 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_k(const float* __restrict__ U
                                                      DropCfg d) {
   extern __shared__ float fin_lds[];
   bn_relu_fwd_body(U, chan, fin, out, b, M, L, d, blockIdx.x, gridDim.x, fin_lds);
+}
+
+__global__ __launch_bounds__(256) void bn_mish_fwd_k(const float* __restrict__ U,
+                                                     float* __restrict__ chan, BnFin fin,
+                                                     float* __restrict__ out, int b, int M, int L,
+                                                     DropCfg d) {
+  extern __shared__ float fin_lds[];
+  bn_relu_fwd_body<kActMish>(U, chan, fin, out, b, M, L, d, blockIdx.x, gridDim.x, fin_lds);
 }
 
 // The same for up to kBnGroup convs of one shape in ONE launch (the N reshape layers in front of the fusion
@@ -670,6 +687,7 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_group_k(BnReluFwdGroup G, int
   bn_relu_fwd_body(U, chan, fin, out, b, M, L, d, blockIdx.x, gridDim.x, fin_lds);
 }
 
+template <int ACT = kActRelu>
 __device__ __forceinline__ void bn_relu_bwd_body(const float* __restrict__ g, const float* __restrict__ U,
                                                  const float* __restrict__ chan, float* __restrict__ dV,
                                                  float* bn_grad, int b, int M, int L, int chunk, const DropCfg& d,
@@ -696,7 +714,8 @@ __device__ __forceinline__ void bn_relu_bwd_body(const float* __restrict__ g, co
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const float v = fmaf(uq[t], sc, sh);
-        dv[t] = (v > 0.f) ? gq[t] * mq[t] : 0.f;
+        if constexpr (ACT == kActMish) dv[t] = gq[t] * mq[t] * dact_f(v, 1);
+        else dv[t] = (v > 0.f) ? gq[t] * mq[t] : 0.f;
         sw += dv[t] * (uq[t] - mu) * rs;
         sb += dv[t];
       }
@@ -724,6 +743,15 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_k(const float* __restrict__ g
                                                      int M, int L, int chunk, DropCfg d) {
   __shared__ float csum[3][2][64];
   bn_relu_bwd_body(g, U, chan, dV, bn_grad, b, M, L, chunk, d, blockIdx.x, blockIdx.y, csum);
+}
+
+__global__ __launch_bounds__(256) void bn_mish_bwd_k(const float* __restrict__ g,
+                                                     const float* __restrict__ U,
+                                                     const float* __restrict__ chan,
+                                                     float* __restrict__ dV, float* bn_grad, int b,
+                                                     int M, int L, int chunk, DropCfg d) {
+  __shared__ float csum[3][2][64];
+  bn_relu_bwd_body<kActMish>(g, U, chan, dV, bn_grad, b, M, L, chunk, d, blockIdx.x, blockIdx.y, csum);
 }
 
 // ... and its backward for the whole group: blockIdx.z = problem
@@ -1484,8 +1512,9 @@ extern "C" int bmnas_bn_glu_bwd(const float* g, const float* U, const float* cha
   return 0;
 }
 
-extern "C" int bmnas_bn_relu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b,
-                                 int M, int L, bmnas_dropout_t drop, void* stream) {
+template <typename Kern>
+static int bn_act_fwd(Kern kern, const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b, int M, int L,
+                      bmnas_dropout_t drop, void* stream) {
   if (!U || !chan || !out || b < 0 || M < 1) return BMNAS_E_ARG;
   if (L % 4 || L > 16) return BMNAS_E_SHAPE;
   if (M > 4096) return BMNAS_E_LIMIT;                    // scale | shift of every channel sit in LDS
@@ -1494,8 +1523,33 @@ extern "C" int bmnas_bn_relu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin
   if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * M * L / 4;
-  hipLaunchKernelGGL(bn_relu_fwd_k, dim3(stream_grid(total)), dim3(256), (size_t)2 * M * sizeof(float),
+  hipLaunchKernelGGL(kern, dim3(stream_grid(total)), dim3(256), (size_t)2 * M * sizeof(float),
                      (hipStream_t)stream, U, chan, f, out, b, M, L, to_cfg(drop));
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_bn_relu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b,
+                                 int M, int L, bmnas_dropout_t drop, void* stream) {
+  return bn_act_fwd(bn_relu_fwd_k, U, chan, fin, out, b, M, L, drop, stream);
+}
+
+extern "C" int bmnas_bn_mish_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b,
+                                 int M, int L, bmnas_dropout_t drop, void* stream) {
+  return bn_act_fwd(bn_mish_fwd_k, U, chan, fin, out, b, M, L, drop, stream);
+}
+
+template <typename Kern>
+static int bn_act_bwd(Kern kern, const float* g, const float* U, const float* chan, float* dV, float* bn_grad, int b,
+                      int M, int L, bmnas_dropout_t drop, void* stream) {
+  if (!g || !U || !chan || !dV || !bn_grad || b < 0 || M < 1) return BMNAS_E_ARG;
+  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (b == 0) return 0;
+  const int ml4 = M * L / 4;
+  const int chunk = pick_chunk(b, ml4);
+  dim3 grid((ml4 + 63) / 64, (b + chunk - 1) / chunk);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, g, U, chan, dV, bn_grad,
+                     b, M, L, chunk, to_cfg(drop));
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -1503,16 +1557,13 @@ extern "C" int bmnas_bn_relu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin
 extern "C" int bmnas_bn_relu_bwd(const float* g, const float* U, const float* chan, float* dV,
                                  float* bn_grad, int b, int M, int L, bmnas_dropout_t drop,
                                  void* stream) {
-  if (!g || !U || !chan || !dV || !bn_grad || b < 0 || M < 1) return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
-  if (b == 0) return 0;
-  const int ml4 = M * L / 4;
-  const int chunk = pick_chunk(b, ml4);
-  dim3 grid((ml4 + 63) / 64, (b + chunk - 1) / chunk);
-  hipLaunchKernelGGL(bn_relu_bwd_k, grid, dim3(256), 0, (hipStream_t)stream, g, U, chan, dV, bn_grad,
-                     b, M, L, chunk, to_cfg(drop));
-  BMNAS_CHECK_LAUNCH();
-  return 0;
+  return bn_act_bwd(bn_relu_bwd_k, g, U, chan, dV, bn_grad, b, M, L, drop, stream);
+}
+
+extern "C" int bmnas_bn_mish_bwd(const float* g, const float* U, const float* chan, float* dV,
+                                 float* bn_grad, int b, int M, int L, bmnas_dropout_t drop,
+                                 void* stream) {
+  return bn_act_bwd(bn_mish_bwd_k, g, U, chan, dV, bn_grad, b, M, L, drop, stream);
 }
 
 extern "C" int bmnas_bn_relu_fwd_group(const bmnas_bn_relu_fwd_prob_t* probs, int n, int b, int M, int L,

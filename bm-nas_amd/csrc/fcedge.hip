@@ -12,6 +12,7 @@
 // The per-edge pointers travel by value in the kernel arguments (uniform index -> scalar loads).
 #include "common.hpp"
 #include "../../include/bmnas_hip.h"
+#include "mish.hpp"
 
 namespace {
 
@@ -19,35 +20,7 @@ constexpr int FC_E = BMNAS_FC_MAX_EDGES;
 constexpr float FC_EPS = 1e-5f;
 constexpr float FC_MOMENTUM = 0.1f;
 
-// mish(u) = u tanh(softplus(u)); with n = e^u: tanh(log(1 + n)) = q / (q + 2), q = n (n + 2) — no cancellation for
-// u -> -inf.  torch's softplus returns u itself above 20, where tanh is 1 in fp32.
-__device__ __forceinline__ float mish_t(float u, float& q) {
-  const float n = expf(fminf(u, 20.f));
-  q = n * (n + 2.f);
-  return u > 20.f ? 1.f : q / (q + 2.f);
-}
-__device__ __forceinline__ float act_f(float u, int mish) {
-  if (!mish) return fmaxf(u, 0.f);
-  float q;
-  return u * mish_t(u, q);
-}
-// act'(u): [u > 0] | tanh(sp) + u sigmoid(u) (1 - tanh(sp)^2), 1 - t^2 = 4 (q + 1) / (q + 2)^2
-__device__ __forceinline__ float dact_f(float u, int mish) {
-  if (!mish) return u > 0.f ? 1.f : 0.f;
-  if (u > 20.f) return 1.f;
-  float q;
-  const float t = mish_t(u, q);
-  const float n = expf(u);
-  const float sg = n / (1.f + n);
-  const float r = 1.f / (q + 2.f);
-  return t + u * sg * 4.f * (q + 1.f) * r * r;
-}
-__device__ __forceinline__ float4 act4(float4 u, int mish) {
-  return make_float4(act_f(u.x, mish), act_f(u.y, mish), act_f(u.z, mish), act_f(u.w, mish));
-}
-__device__ __forceinline__ float4 dact4(float4 u, int mish) {
-  return make_float4(dact_f(u.x, mish), dact_f(u.y, mish), dact_f(u.z, mish), dact_f(u.w, mish));
-}
+// the activations act_f / dact_f / act4 / dact4 (ReLU | Mish): mish.hpp
 
 __device__ __forceinline__ float skip_weight(const float* __restrict__ w, int j, int P, uint32_t skip_cols) {
   float s = 0.f;

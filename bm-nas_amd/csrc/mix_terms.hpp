@@ -1,6 +1,9 @@
 // The NodeMixedOp mix, per element — the ONE definition every mix kernel compiles:
 //
-//   s = g0 (x + y) + g1 p1 + g2 drop(va sigmoid(vg)) + g3 drop(relu(vf))      va | vg | vf = BatchNorm(U rows)
+//   s = g0 (x + y) + g1 p1 + g2 drop(va sigmoid(vg)) + g3 drop(act(vf))       va | vg | vf = BatchNorm(U rows)
+//
+// act = relu: ConcatFC.  act = mish (ACT = kActMish; nodemix_sel.hip alone instantiates it): CatConvMish, which takes
+// ConcatFC's slot — mask bit 3, the C rows behind the GLU rows, gamma column 3, the drop_fc site.
 //
 // and its backward: dgamma, the gamma-weighted gradients da | dg | df of the BatchNorm outputs, their per-channel
 // BatchNorm sums sw = sum d xhat, sb = sum d, and the dx / dy write.  Both directions are specialised on the presence
@@ -12,6 +15,7 @@
 // mix_ep_tile in conv1x1.hip; node_mix_sel_fwd_k / node_mix_sel_bwd_k in nodemix_sel.hip.
 #pragma once
 #include "common.hpp"
+#include "mish.hpp"
 
 namespace {
 
@@ -28,11 +32,15 @@ __device__ __forceinline__ void glu_grad(float gm, float va, float sg, float& da
   da = gm * sg;
   dg = gm * va * sg * (1.f - sg);
 }
-// ConcatFC: drop(relu(vf))
-__device__ __forceinline__ float fc_term(float vf, float m) { return fmaxf(vf, 0.f) * m; }
+// ConcatFC: drop(relu(vf)); CatConvMish (reference node_operations.py:58-82), in the same slot: drop(mish(vf))
+template <int ACT = kActRelu>
+__device__ __forceinline__ float fc_term(float vf, float m) {
+  if constexpr (ACT == kActMish) return act_f(vf, 1) * m;
+  else return fmaxf(vf, 0.f) * m;
+}
 
 // ---- forward.  Association order of the present terms: ((g0 s + g1 p) + g2 t2) + g3 t3  (s = x + y)
-template <int MASK>
+template <int MASK, int ACT = kActRelu>
 __device__ __forceinline__ float mix_fwd(float g0, float g1, float g2, float g3, float s, float p, float va, float vg,
                                          float vf, float m2, float m3) {
   float o = 0.f;
@@ -40,16 +48,17 @@ __device__ __forceinline__ float mix_fwd(float g0, float g1, float g2, float g3,
   if constexpr (MASK & kAttn) o = (MASK & kSum) ? o + g1 * p : g1 * p;
   if constexpr (MASK & kGlu)
     o = (MASK & (kSum | kAttn)) ? o + g2 * glu_term(va, sigmoidf(vg), m2) : g2 * glu_term(va, sigmoidf(vg), m2);
-  if constexpr (MASK & kFc) o = (MASK & (kSum | kAttn | kGlu)) ? o + g3 * fc_term(vf, m3) : g3 * fc_term(vf, m3);
+  if constexpr (MASK & kFc)
+    o = (MASK & (kSum | kAttn | kGlu)) ? o + g3 * fc_term<ACT>(vf, m3) : g3 * fc_term<ACT>(vf, m3);
   return o;
 }
-template <int MASK>
+template <int MASK, int ACT = kActRelu>
 __device__ __forceinline__ float4 mix_fwd4(float g0, float g1, float g2, float g3, float4 s, float4 p, float4 va,
                                            float4 vg, float4 vf, float4 m2, float4 m3) {
-  return make_float4(mix_fwd<MASK>(g0, g1, g2, g3, s.x, p.x, va.x, vg.x, vf.x, m2.x, m3.x),
-                     mix_fwd<MASK>(g0, g1, g2, g3, s.y, p.y, va.y, vg.y, vf.y, m2.y, m3.y),
-                     mix_fwd<MASK>(g0, g1, g2, g3, s.z, p.z, va.z, vg.z, vf.z, m2.z, m3.z),
-                     mix_fwd<MASK>(g0, g1, g2, g3, s.w, p.w, va.w, vg.w, vf.w, m2.w, m3.w));
+  return make_float4(mix_fwd<MASK, ACT>(g0, g1, g2, g3, s.x, p.x, va.x, vg.x, vf.x, m2.x, m3.x),
+                     mix_fwd<MASK, ACT>(g0, g1, g2, g3, s.y, p.y, va.y, vg.y, vf.y, m2.y, m3.y),
+                     mix_fwd<MASK, ACT>(g0, g1, g2, g3, s.z, p.z, va.z, vg.z, vf.z, m2.z, m3.z),
+                     mix_fwd<MASK, ACT>(g0, g1, g2, g3, s.w, p.w, va.w, vg.w, vf.w, m2.w, m3.w));
 }
 
 // ---- backward.  The BatchNorm constants of one channel's NB conv blocks (chan = mean | rstd | scale | shift, M each)
@@ -80,7 +89,7 @@ struct MixRows {
 
 // One float4 of the mix backward: gv = gradient of the mix output, xy = x + y, ua | ug | uf = RAW conv outputs.
 // dgam[q], sw[k], sb[k] accumulate; da | dg | df are the gradients of the present blocks' BatchNorm outputs.
-template <int MASK>
+template <int MASK, int ACT = kActRelu>
 __device__ __forceinline__ void mix_bwd4(float g2, float g3, float4 gv, float4 xy, float4 pv, float4 ua, float4 ug,
                                          float4 uf, float4 m2, float4 m3, const ChanBn<MixRows<MASK>::kNb>& bn,
                                          float (&dgam)[4], float4& da4, float4& dg4, float4& df4,
@@ -106,8 +115,13 @@ __device__ __forceinline__ void mix_bwd4(float g2, float g3, float4 gv, float4 x
     }
     if constexpr (MASK & kFc) {
       const float vf = fmaf(ufq[t], bn.sc[FO], bn.sh[FO]);
-      dgam[3] += gq[t] * fc_term(vf, m3q[t]);
-      df[t] = (vf > 0.f) ? g3 * gq[t] * m3q[t] : 0.f;
+      if constexpr (ACT == kActMish) {
+        dgam[3] += gq[t] * fc_term<ACT>(vf, m3q[t]);
+        df[t] = g3 * gq[t] * m3q[t] * dact_f(vf, 1);
+      } else {
+        dgam[3] += gq[t] * fc_term(vf, m3q[t]);
+        df[t] = (vf > 0.f) ? g3 * gq[t] * m3q[t] : 0.f;
+      }
       sw[FO] += df[t] * (ufq[t] - bn.mu[FO]) * bn.rs[FO];
       sb[FO] += df[t];
     }

@@ -10,6 +10,10 @@
 // 1 ScaleDotAttn, 2 LinearGLU, 3 ConcatFC), so that an
 // absent term costs no load, no store, no reduction and no LDS, and U holds only the present conv rows
 // (M = 2C [GLU] + C [FC], GLU rows first).  Which gamma column belongs to which kind comes with the launch (Sel).
+//
+// CatConvMish (reference node_operations.py:58-82: cat -> Conv1d(2C, C, 1) -> BatchNorm1d -> Mish -> Dropout) is ConcatFC
+// with another activation: it takes ConcatFC's slot (bit 3, the C rows behind the GLU rows, col[3], drop_fc) and the
+// kernels' second template parameter ACT = kActMish, instantiated for the 8 masks that hold bit 3.
 #include "common.hpp"
 #include "../../include/bmnas_hip.h"
 #include "bn_fin.hpp"
@@ -21,7 +25,7 @@ struct Sel {
   int col[4];      // gamma column of Sum | ScaleDotAttn | LinearGLU | ConcatFC (unused where absent)
 };
 
-template <int MASK>
+template <int MASK, int ACT>
 __global__ __launch_bounds__(256) void node_mix_sel_fwd_k(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ p1,
     const float* __restrict__ U, float* __restrict__ chan, BnFin fin, const float* __restrict__ gamma, Sel sel,
@@ -61,14 +65,14 @@ __global__ __launch_bounds__(256) void node_mix_sel_fwd_k(
       vf = affine4(ld4(U + ub + (int64_t)FO * C * L), sc[FO * C + c], sh[FO * C + c]);
       m3 = drop_mult4(rfc, (uint64_t)e);
     }
-    st4_wtg<2>(out + e, mix_fwd4<MASK>(gS, gA, gG, gF, xy, pv, va, vg, vf, m2, m3));
+    st4_wtg<2>(out + e, mix_fwd4<MASK, ACT>(gS, gA, gG, gF, xy, pv, va, vg, vf, m2, m3));
   }
 }
 
 
 // Phase A of the backward, as node_mix_bwd_k: a thread owns one float4 slot of a sample's (C, L) tile and walks a chunk
 // of samples (4 sample lanes per slot), so the per-channel BatchNorm sums and the dgamma sums stay in registers.
-template <int MASK>
+template <int MASK, int ACT>
 __global__ __launch_bounds__(256) void node_mix_sel_bwd_k(
     const float* __restrict__ g, const float* __restrict__ x, const float* __restrict__ y,
     const float* __restrict__ p1, const float* __restrict__ U, const float* __restrict__ chan,
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void node_mix_sel_bwd_k(
         m3 = drop_mult4(rfc, (uint64_t)e);
       }
       float4 da, dg, df;
-      mix_bwd4<MASK>(gG, gF, gv, xy, pv, ua, ug, uf, m2, m3, bn, dgam, da, dg, df, sw, sb);
+      mix_bwd4<MASK, ACT>(gG, gF, gv, xy, pv, ua, ug, uf, m2, m3, bn, dgam, da, dg, df, sw, sb);
       if constexpr (hG) {
         st4_wtg<2>(dV + ub, da);
         st4_wtg<2>(dV + ub + (int64_t)C * L, dg);
@@ -210,20 +214,26 @@ extern "C" int bmnas_node_mix_sel_ok(int mask, int b, int C, int L) {
   return 1;
 }
 
+// ReLU: all 15 masks; Mish: the 8 masks with the FC slot (mask | 16 in the switch)
 #define SEL_SWITCH(CASE)                                                                                    \
-  switch (mask) {                                                                                           \
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12)      \
-    CASE(13) CASE(14) CASE(15)                                                                              \
+  switch (fc_act == kActMish ? (mask | 16) : mask) {                                                        \
+    CASE(1, kActRelu) CASE(2, kActRelu) CASE(3, kActRelu) CASE(4, kActRelu) CASE(5, kActRelu)               \
+    CASE(6, kActRelu) CASE(7, kActRelu) CASE(8, kActRelu) CASE(9, kActRelu) CASE(10, kActRelu)              \
+    CASE(11, kActRelu) CASE(12, kActRelu) CASE(13, kActRelu) CASE(14, kActRelu) CASE(15, kActRelu)          \
+    CASE(8, kActMish) CASE(9, kActMish) CASE(10, kActMish) CASE(11, kActMish) CASE(12, kActMish)            \
+    CASE(13, kActMish) CASE(14, kActMish) CASE(15, kActMish)                                                \
     default: return BMNAS_E_ARG;                                                                            \
   }
 
-extern "C" int bmnas_node_mix_sel_fwd(const float* x, const float* y, const float* p1, const float* U, float* chan,
-                                      bmnas_bn_fin_t fin, const float* gamma, bmnas_node_sel_t sel, float* out,
-                                      int b, int C, int L, bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc,
-                                      void* stream) {
+extern "C" int bmnas_node_mix_sel_act_fwd(const float* x, const float* y, const float* p1, const float* U,
+                                          float* chan, bmnas_bn_fin_t fin, const float* gamma, bmnas_node_sel_t sel,
+                                          float* out, int b, int C, int L, bmnas_dropout_t drop_glu,
+                                          bmnas_dropout_t drop_fc, int fc_act, void* stream) {
   Sel s;
   const int mask = sel_mask(sel, &s);
   if (mask < 0) return mask;
+  if (fc_act != kActRelu && fc_act != kActMish) return BMNAS_E_ARG;
+  if (!(mask & kFc)) fc_act = kActRelu;                   // no FC slot: nothing to activate
   if (!gamma || !out || b < 0 || C < 1) return BMNAS_E_ARG;
   if (!bmnas_node_mix_sel_ok(mask, b > 0 ? b : 1, C, L)) return BMNAS_E_LIMIT;
   const int M = sel_rows(mask) * C;
@@ -237,11 +247,53 @@ extern "C" int bmnas_node_mix_sel_fwd(const float* x, const float* y, const floa
   }
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * C * L / 4;
-#define CASE(Mv)                                                                                            \
-  case Mv:                                                                                                  \
-    hipLaunchKernelGGL(node_mix_sel_fwd_k<Mv>, dim3(stream_grid(total)), dim3(256), (size_t)2 * M * sizeof(float), \
-                       (hipStream_t)stream, x, y, p1, U, chan, f, gamma, s, out, b, C, L, to_cfg(drop_glu),  \
-                       to_cfg(drop_fc));                                                                    \
+#define CASE(Mv, Av)                                                                                        \
+  case Mv | (Av << 4):                                                                                      \
+    hipLaunchKernelGGL((node_mix_sel_fwd_k<Mv, Av>), dim3(stream_grid(total)), dim3(256),                   \
+                       (size_t)2 * M * sizeof(float), (hipStream_t)stream, x, y, p1, U, chan, f, gamma, s, out, b, \
+                       C, L, to_cfg(drop_glu), to_cfg(drop_fc));                                            \
+    break;
+  SEL_SWITCH(CASE)
+#undef CASE
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_node_mix_sel_fwd(const float* x, const float* y, const float* p1, const float* U, float* chan,
+                                      bmnas_bn_fin_t fin, const float* gamma, bmnas_node_sel_t sel, float* out,
+                                      int b, int C, int L, bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc,
+                                      void* stream) {
+  return bmnas_node_mix_sel_act_fwd(x, y, p1, U, chan, fin, gamma, sel, out, b, C, L, drop_glu, drop_fc, kActRelu,
+                                    stream);
+}
+
+extern "C" int bmnas_node_mix_sel_act_bwd(const float* g, const float* x, const float* y, const float* p1,
+                                          const float* U, const float* chan, const float* gamma,
+                                          bmnas_node_sel_t sel, float* dgamma, int dgamma_shards,
+                                          int64_t dgamma_shard_stride, float* dx, float* dy,
+                                          uint32_t accumulate_mask, float* dV, float* bn_grad, int b, int C, int L,
+                                          bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, int fc_act,
+                                          void* stream) {
+  Sel s;
+  const int mask = sel_mask(sel, &s);
+  if (mask < 0) return mask;
+  if (fc_act != kActRelu && fc_act != kActMish) return BMNAS_E_ARG;
+  if (!(mask & kFc)) fc_act = kActRelu;
+  if (!g || !gamma || b < 0 || C < 1 || dgamma_shards < 1) return BMNAS_E_ARG;
+  if (!bmnas_node_mix_sel_ok(mask, b > 0 ? b : 1, C, L)) return BMNAS_E_LIMIT;
+  const int M = sel_rows(mask) * C;
+  if ((mask & kSum) && (!x || !y)) return BMNAS_E_ARG;
+  if ((mask & kAttn) && !p1) return BMNAS_E_ARG;
+  if (M > 0 && (!U || !chan || !dV || !bn_grad)) return BMNAS_E_ARG;
+  if (b == 0) return 0;
+  const int cl4 = C * L / 4;
+  const int chunk = pick_chunk(b, cl4);
+  dim3 grid((cl4 + 63) / 64, (b + chunk - 1) / chunk);
+#define CASE(Mv, Av)                                                                                        \
+  case Mv | (Av << 4):                                                                                      \
+    hipLaunchKernelGGL((node_mix_sel_bwd_k<Mv, Av>), grid, dim3(256), 0, (hipStream_t)stream, g, x, y, p1, U, chan, \
+                       gamma, s, dgamma, dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV,    \
+                       bn_grad, b, C, L, chunk, to_cfg(drop_glu), to_cfg(drop_fc));                         \
     break;
   SEL_SWITCH(CASE)
 #undef CASE
@@ -254,27 +306,6 @@ extern "C" int bmnas_node_mix_sel_bwd(const float* g, const float* x, const floa
                                       float* dgamma, int dgamma_shards, int64_t dgamma_shard_stride, float* dx,
                                       float* dy, uint32_t accumulate_mask, float* dV, float* bn_grad, int b, int C,
                                       int L, bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream) {
-  Sel s;
-  const int mask = sel_mask(sel, &s);
-  if (mask < 0) return mask;
-  if (!g || !gamma || b < 0 || C < 1 || dgamma_shards < 1) return BMNAS_E_ARG;
-  if (!bmnas_node_mix_sel_ok(mask, b > 0 ? b : 1, C, L)) return BMNAS_E_LIMIT;
-  const int M = sel_rows(mask) * C;
-  if ((mask & kSum) && (!x || !y)) return BMNAS_E_ARG;
-  if ((mask & kAttn) && !p1) return BMNAS_E_ARG;
-  if (M > 0 && (!U || !chan || !dV || !bn_grad)) return BMNAS_E_ARG;
-  if (b == 0) return 0;
-  const int cl4 = C * L / 4;
-  const int chunk = pick_chunk(b, cl4);
-  dim3 grid((cl4 + 63) / 64, (b + chunk - 1) / chunk);
-#define CASE(Mv)                                                                                            \
-  case Mv:                                                                                                  \
-    hipLaunchKernelGGL(node_mix_sel_bwd_k<Mv>, grid, dim3(256), 0, (hipStream_t)stream, g, x, y, p1, U, chan, \
-                       gamma, s, dgamma, dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV,    \
-                       bn_grad, b, C, L, chunk, to_cfg(drop_glu), to_cfg(drop_fc));                         \
-    break;
-  SEL_SWITCH(CASE)
-#undef CASE
-  BMNAS_CHECK_LAUNCH();
-  return 0;
+  return bmnas_node_mix_sel_act_bwd(g, x, y, p1, U, chan, gamma, sel, dgamma, dgamma_shards, dgamma_shard_stride, dx,
+                                    dy, accumulate_mask, dV, bn_grad, b, C, L, drop_glu, drop_fc, kActRelu, stream);
 }

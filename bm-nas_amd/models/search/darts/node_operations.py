@@ -1,22 +1,25 @@
 """Fusion primitives of a step node and the gamma-weighted NodeMixedOp.
 
 Mirror of the reference's models/search/darts/node_operations.py (STEP_STEP_OPS :9-14,
-Sum :16-20, LinearGLU :22-39, ConcatFC :41-56, ScaledDotAttn :84-108, NodeMixedOp :110-120):
+Sum :16-20, LinearGLU :22-39, ConcatFC :41-56, Mish / CatConvMish :58-82, ScaledDotAttn :84-108, NodeMixedOp :110-120):
 same class names, constructor/forward signatures and state_dict keys, but every forward
 runs on the gfx950 kernels of libbmnas_hip.so (no eager-PyTorch math on the hot path).
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from bmnas.cell import Arena, Pack
 from bmnas import lib as _lib
 from bmnas.functions import (ConvBnActFn, ConvBnActThruFn, MixSumFn, NodeMixedFn, NodeMixedSelFn,
-                             SdpaLnFn)
+                             SdpaLnFn, SdpaLnThruFn)
 
 from .genotypes import *  # noqa: F401,F403
 from .genotypes import STEP_STEP_PRIMITIVES
 
 # every node operation takes two (b, C, L) inputs and returns one (b, C, L) output
+# (CatConvMish is not registered, as in the reference: `STEP_STEP_OPS['CatConvMish'] = lambda C, L, args:
+# CatConvMish(C, args)` adds it)
 STEP_STEP_OPS = {
     'Sum': lambda C, L, args: Sum(),
     'ScaleDotAttn': lambda C, L, args: ScaledDotAttn(C, L),
@@ -84,6 +87,23 @@ class ConcatFC(_CatConvBn):
         super().__init__(C, C, args)
 
 
+class Mish(nn.Module):
+    """x tanh(softplus(x)) (reference :58-63).  CatConvMish holds one for the module tree; its forward applies the
+    activation inside the BatchNorm tail kernel (csrc/mish.hpp) instead of calling it."""
+
+    def forward(self, x):
+        return x * torch.tanh(F.softplus(x))
+
+
+class CatConvMish(_CatConvBn):
+    """reference :65-82: ConcatFC with Mish in place of ReLU; state_dict keys as ConcatFC (Mish has no state)."""
+    _act = 'mish'
+
+    def __init__(self, C, args):
+        super().__init__(C, C, args)
+        self.mish = Mish()
+
+
 class ScaledDotAttn(nn.Module):
     """Scaled dot-product attention without projections (reference :84-108):
     q = x^T, k = y, v = y^T; softmax(q k / sqrt(C)) v, Dropout(0.1), LayerNorm([C, L])."""
@@ -96,20 +116,38 @@ class ScaledDotAttn(nn.Module):
     def forward(self, x, y):
         return SdpaLnFn.apply(x, y, self.ln.weight, self.ln.bias, self.dropout.p, self.training)
 
+    def forward_thru(self, x, y):
+        """-> (out, x', y'): the same, with the two inputs handed back for their LATER readers (bmnas.functions
+        SdpaLnThruFn: those readers' gradients are then accumulated by this op's backward launch, not by autograd
+        `add` launches)."""
+        return SdpaLnThruFn.apply(x, y, self.ln.weight, self.ln.bias, self.dropout.p, self.training)
+
 
 _DEFAULT_PRIMS = ['Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC']
-_BUILTIN = {'Sum': Sum, 'ScaleDotAttn': ScaledDotAttn, 'LinearGLU': LinearGLU, 'ConcatFC': ConcatFC}
+_BUILTIN = {'Sum': Sum, 'ScaleDotAttn': ScaledDotAttn, 'LinearGLU': LinearGLU, 'ConcatFC': ConcatFC,
+            'CatConvMish': CatConvMish}
+# the primitives of the mix kernels' FC slot (mask bit 3, the C conv rows behind LinearGLU's, the drop_fc site): a list
+# holds at most one of them natively
+_FC_SLOT = ('ConcatFC', 'CatConvMish')
+_FC_ACT = {'ConcatFC': _lib.FC_ACT_RELU, 'CatConvMish': _lib.FC_ACT_MISH}
 
-# An edited STEP_STEP_PRIMITIVES list made of the four built-in primitives runs on the selected-term kernels
-# (csrc/nodemix_sel.hip); False forces the composed sum `sum(w * op(x, y))` for A/B timing and tests (the cell-level
+
+def _slot_name(p):
+    """The kind a primitive name has in the selection descriptor (lib.NODE_KINDS)."""
+    return 'ConcatFC' if p in _FC_SLOT else p
+
+
+# An edited STEP_STEP_PRIMITIVES list made of the built-in primitives (the four of STEP_STEP_OPS and CatConvMish, with
+# at most one of ConcatFC / CatConvMish) runs on the selected-term kernels (csrc/nodemix_sel.hip); False forces the composed sum `sum(w * op(x, y))` for A/B timing and tests (the cell-level
 # counterpart is operations.FC_EDGES_NATIVE).  The default list is not affected either way.
 NODE_PRIMS_NATIVE = True
 
 
 def node_mix_route(op, x, y, weights):
     """Which path NodeMixedOp.forward(x, y, weights) takes: 'default' (the unedited list: NodeMixedFn), 'selected'
-    (a subset / permutation of the built-in primitives: NodeMixedSelFn) or 'composed' (everything else: the
-    reference's own sum over the primitive modules, node_operations.py:118-120).  Host logic only."""
+    (a subset / permutation of the built-in primitives, CatConvMish in ConcatFC's place included: NodeMixedSelFn) or
+    'composed' (everything else, a list with both ConcatFC and CatConvMish among it: the reference's own sum over the
+    primitive modules, node_operations.py:118-120).  Host logic only."""
     if op._default:
         return 'default'
     if not NODE_PRIMS_NATIVE:
@@ -117,6 +155,8 @@ def node_mix_route(op, x, y, weights):
     prims = op._prims
     if not prims or len(set(prims)) != len(prims) or any(p not in _BUILTIN for p in prims):
         return 'composed'
+    if sum(p in _FC_SLOT for p in prims) > 1:
+        return 'composed'                    # one FC slot in the kernels
     if len(op._ops) != len(prims) or any(type(m) is not _BUILTIN[p] for p, m in zip(prims, op._ops)):
         return 'composed'                    # an edited STEP_STEP_OPS registry: somebody else's module
     for t in (x, y):
@@ -138,7 +178,7 @@ def node_mix_route(op, x, y, weights):
         elif isinstance(m, ScaledDotAttn):
             if not (m.ln.eps == 1e-5 and m.ln.elementwise_affine and m.ln.weight.is_cuda):
                 return 'composed'
-    mask = sum(1 << _DEFAULT_PRIMS.index(p) for p in prims)
+    mask = sum(1 << _DEFAULT_PRIMS.index(_slot_name(p)) for p in prims)
     if not _lib.node_mix_sel_ok(mask, x.shape[0], op.C, op.L):
         return 'composed'
     return 'selected'
@@ -149,9 +189,10 @@ class NodeMixedOp(nn.Module):
 
     With the default primitive list the whole mixed op is one fused kernel sequence
     (bmnas.functions.NodeMixedFn); with a subset / permutation of the four built-in primitives it is the same
-    sequence over the present terms (bmnas.functions.NodeMixedSelFn, see node_mix_route).  To feed ONE stacked GEMM,
-    the LinearGLU and ConcatFC conv / BatchNorm parameters and buffers — when both are in the list — are kept as
-    views into stacked tensors (rows [0, 2C) = LinearGLU, rows [2C, 3C) = ConcatFC, whatever their list order);
+    sequence over the present terms (bmnas.functions.NodeMixedSelFn, see node_mix_route); CatConvMish may stand where
+    ConcatFC does ("the FC slot").  To feed ONE stacked GEMM, the LinearGLU and FC-slot conv / BatchNorm parameters and
+    buffers — when both are in the list — are kept as views into stacked tensors (rows [0, 2C) = LinearGLU, rows
+    [2C, 3C) = ConcatFC | CatConvMish, whatever their list order);
     names, shapes and state_dict keys are exactly the reference's (`_ops.<list position>.…`)."""
 
     def __init__(self, C, L, args):
@@ -166,12 +207,21 @@ class NodeMixedOp(nn.Module):
         """The module of built-in primitive `name`, or None when the list does not hold it."""
         return self._ops[self._prims.index(name)] if name in self._prims else None
 
+    def _fc_name(self):
+        """The name of the list's FC-slot primitive (ConcatFC | CatConvMish; the first, should a composed list hold
+        both), or None."""
+        return next((p for p in self._prims if p in _FC_SLOT), None)
+
+    def _fc(self):
+        name = self._fc_name()
+        return None if name is None else self._kind(name)
+
     # -- stacked storage ---------------------------------------------------------------
     def _stack_ok(self):
         st = self._stack
         if st is None:
             return False
-        glu, cfc = self._kind('LinearGLU'), self._kind('ConcatFC')
+        glu, cfc = self._kind('LinearGLU'), self._fc()
         C = self.C
         return (glu.conv.weight.data_ptr() == st.W.data_ptr()
                 and cfc.conv.weight.data_ptr() == st.W[2 * C:].data_ptr()
@@ -182,7 +232,7 @@ class NodeMixedOp(nn.Module):
 
     @torch.no_grad()
     def _restack(self):
-        glu, cfc = self._kind('LinearGLU'), self._kind('ConcatFC')
+        glu, cfc = self._kind('LinearGLU'), self._fc()
         C = self.C
         dev = glu.conv.weight.device
 
@@ -207,15 +257,17 @@ class NodeMixedOp(nn.Module):
         self._stack = Pack(W=W, bias=bias, bn_w=bn_w, bn_b=bn_b, rm=rm, rv=rv, nbt=nbt)
 
     def conv_rows(self):
-        """M: rows of the one conv GEMM of this op (2C LinearGLU + C ConcatFC, as present)."""
-        return (2 * self.C if 'LinearGLU' in self._prims else 0) + (self.C if 'ConcatFC' in self._prims else 0)
+        """M: rows of the one conv GEMM of this op (2C LinearGLU + C ConcatFC | CatConvMish, as present)."""
+        return (2 * self.C if 'LinearGLU' in self._prims else 0) + (self.C if self._fc_name() else 0)
 
     def pack(self):
         """Parameter pack consumed by bmnas.cell.node_mixed_fwd / node_mixed_sel_fwd: by kind and presence (absent:
         None / p = 0).  stack_*: the conv + BatchNorm storage of the present conv rows — the stacked tensors when
-        both convs are in the list, else the one conv's own tensors."""
-        attn, glu, cfc = self._kind('ScaleDotAttn'), self._kind('LinearGLU'), self._kind('ConcatFC')
-        P = Pack(prims=self._prims, M=self.conv_rows(),
+        both convs are in the list, else the one conv's own tensors.  prims names the FC-slot primitive 'ConcatFC'
+        (the kind of the selection descriptor), with what it applies behind its BatchNorm in fc_act."""
+        attn, glu, cfc = self._kind('ScaleDotAttn'), self._kind('LinearGLU'), self._fc()
+        P = Pack(prims=[_slot_name(p) for p in self._prims], M=self.conv_rows(),
+                 fc_act=_FC_ACT.get(self._fc_name(), _lib.FC_ACT_RELU),
                  ln_w=None if attn is None else attn.ln.weight.detach(),
                  ln_b=None if attn is None else attn.ln.bias.detach(),
                  attn_p=0.0 if attn is None else attn.dropout.p,
@@ -263,14 +315,14 @@ class NodeMixedOp(nn.Module):
     def grads_in_param_order(self, G):
         C, M = self.C, self.conv_rows()
         dW, db, bn = G.stack_dW, G.stack_dbias, G.stack_bn_grad
-        fo = 2 * C if 'LinearGLU' in self._prims else 0          # first ConcatFC row
+        fo = 2 * C if 'LinearGLU' in self._prims else 0          # first FC-slot row
         out = []
         for p in self._prims:
             if p == 'ScaleDotAttn':
                 out += [G.dln_w, G.dln_b]
             elif p == 'LinearGLU':
                 out += [dW[:2 * C].view(2 * C, 2 * C, 1), db[:2 * C], bn[0:2 * C], bn[M:M + 2 * C]]
-            elif p == 'ConcatFC':
+            elif p in _FC_SLOT:
                 out += [dW[fo:fo + C].view(C, 2 * C, 1), db[fo:fo + C], bn[fo:fo + C], bn[M + fo:M + fo + C]]
         return out
 

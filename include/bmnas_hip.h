@@ -374,6 +374,21 @@ int bmnas_node_mix_sel_bwd(const float* g, const float* x, const float* y, const
                            int dgamma_shards, int64_t dgamma_shard_stride, float* dx, float* dy,
                            uint32_t accumulate_mask, float* dV, float* bn_grad, int b, int C, int L,
                            bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream);
+/* The same two calls with the activation of the FC slot as an argument: fc_act = 0 ReLU — ConcatFC, exactly the two
+ * calls above — | 1 Mish: CatConvMish, node_operations.py:58-82 (cat -> Conv1d(2C, C, 1) -> BatchNorm1d(C) -> Mish ->
+ * Dropout), which takes ConcatFC's place: col[3], the C rows behind the LinearGLU rows, drop_fc.
+ *   term_FC = drop_fc(mish(vf)),  dV_FC = gamma[col[3]] g m mish'(vf),  dgamma[col[3]] += <g, term_FC>
+ * with mish(v) = v tanh(softplus(v)) (csrc/mish.hpp).  Any other fc_act: BMNAS_E_ARG; without the FC slot fc_act has
+ * no effect.  Limits: bmnas_node_mix_sel_ok. */
+int bmnas_node_mix_sel_act_fwd(const float* x, const float* y, const float* p1, const float* U, float* chan,
+                               bmnas_bn_fin_t fin, const float* gamma, bmnas_node_sel_t sel, float* out, int b,
+                               int C, int L, bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, int fc_act,
+                               void* stream);
+int bmnas_node_mix_sel_act_bwd(const float* g, const float* x, const float* y, const float* p1, const float* U,
+                               const float* chan, const float* gamma, bmnas_node_sel_t sel, float* dgamma,
+                               int dgamma_shards, int64_t dgamma_shard_stride, float* dx, float* dy,
+                               uint32_t accumulate_mask, float* dV, float* bn_grad, int b, int C, int L,
+                               bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, int fc_act, void* stream);
 
 /* K6 backward + K2 backward in one launch (node_multiplier == 1; reference node_search.py:55,67-68 run
  * backwards): g = grad of out = LayerNorm_[C, L](pre), pre / stats as saved by bmnas_node_mix_ln_fwd.
@@ -430,6 +445,14 @@ int bmnas_bn_glu_bwd(const float* g, const float* U, const float* chan, float* d
 int bmnas_bn_relu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b, int M, int L,
                       bmnas_dropout_t drop, void* stream);
 int bmnas_bn_relu_bwd(const float* g, const float* U, const float* chan, float* dV, float* bn_grad,
+                      int b, int M, int L, bmnas_dropout_t drop, void* stream);
+
+/* ---- BN + Mish + dropout: the CatConvMish tail (node_operations.py:58-82, Mish :58-63) -------
+ * out = mish(v) m,  dV = g m mish'(v),  v = fma(U, scale, shift),  mish(v) = v tanh(softplus(v)) (csrc/mish.hpp);
+ * arguments, BatchNorm finalisation, BatchNorm sums and limits exactly as bmnas_bn_relu_fwd / _bwd. */
+int bmnas_bn_mish_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b, int M, int L,
+                      bmnas_dropout_t drop, void* stream);
+int bmnas_bn_mish_bwd(const float* g, const float* U, const float* chan, float* dV, float* bn_grad,
                       int b, int M, int L, bmnas_dropout_t drop, void* stream);
 
 /* ---- the N reshape layers in front of the fusion cell as ONE launch per stage ----------

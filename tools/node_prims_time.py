@@ -13,6 +13,12 @@ bmnas.functions.NodeMixedSelFn) against the composed sum (NodeMixedOp primitive 
     python tools/node_prims_time.py --stats DIR/.../np_results.db --trace mmimdb:128 --list Sum,LinearGLU,ConcatFC
                                                        # moved bytes / duration of the two new kernels from that trace
 
+Lists with CatConvMish (reference node_operations.py:58-82; registered here the way a user registers it): "composed" is
+what a user had before the primitive was mirrored — a plain-torch CatConvMish defined in this file, which routes
+composed in any checkout — and "native" the project's class in the mix kernels' FC slot; the two models are built from
+the same seed and timed alternating.  With --composed-only --tree PARENT the same plain-torch baseline runs on the parent
+commit; --default-list times the unedited list's step alone (on either tree: it must not have moved).
+
 Without --leg / --trace / --stats the tool is a driver: every (list, configuration) leg runs as a child process of its
 own under a time limit, one after the other, and the first leg that fails (or runs out of time) ends the run.
 
@@ -32,25 +38,52 @@ if '--tree' in sys.argv:                   # another checkout of the project (th
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'bm-nas_amd'))
 
-LISTS = [['Sum', 'ScaleDotAttn'], ['Sum', 'LinearGLU', 'ConcatFC'], ['ScaleDotAttn', 'ConcatFC', 'Sum'], ['ConcatFC']]
+MISH = 'CatConvMish'
+DEFAULT = ['Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC']
+LISTS = [['Sum', 'ScaleDotAttn'], ['Sum', 'LinearGLU', 'ConcatFC'], ['ScaleDotAttn', 'ConcatFC', 'Sum'], ['ConcatFC'],
+         ['Sum', 'ScaleDotAttn', 'LinearGLU', MISH], [MISH]]
 CASES = [('mmimdb', 128), ('ntu', 64), ('ntu', 8)]
 PEAK_HBM = 8.0e12                          # bytes / s
 LEG_SECONDS = 240
 
 
-def build(cname, batch, prims):
+def plain_cat_conv_mish():
+    """The module a user of the reference writes in plain torch (node_operations.py:58-82)."""
+    import torch
+    import torch.nn as nn
+    import torch.nn.functional as F
+
+    class CatConvMish(nn.Module):
+        def __init__(self, C, args):
+            super().__init__()
+            self.conv = nn.Conv1d(2 * C, C, 1, 1)
+            self.bn = nn.BatchNorm1d(C)
+            self.dropout = nn.Dropout(args.drpt)
+
+        def forward(self, x, y):
+            out = self.bn(self.conv(torch.cat([x, y], dim=1)))
+            return self.dropout(out * torch.tanh(F.softplus(out)))
+    return CatConvMish
+
+
+def build(cname, batch, prims, plain=False):
     import torch
     import bench as B
     import models.search.darts.genotypes as gt
+    import models.search.darts.node_operations as no
     from bmnas import nn as bnn
     c = B.CONFIGS[cname]
     saved = list(gt.STEP_STEP_PRIMITIVES)
     gt.STEP_STEP_PRIMITIVES[:] = prims
+    if MISH in prims:
+        cls = plain_cat_conv_mish() if plain else no.CatConvMish
+        no.STEP_STEP_OPS[MISH] = lambda C, L, args: cls(C, args)
     try:
         torch.manual_seed(2)
         model = B.HyperNet(c, 'F', cname).to('cuda:0').train()
     finally:
         gt.STEP_STEP_PRIMITIVES[:] = saved
+        no.STEP_STEP_OPS.pop(MISH, None)
     crit = bnn.BCEWithLogitsLoss() if c['loss'] == 'bce' else bnn.CrossEntropyLoss()
     xs, y = B.synth_batch(c, batch, torch.device('cuda:0'), 0)
     params = [p for p in model.parameters()] + list(model.arch_parameters()) + xs
@@ -92,35 +125,40 @@ def timed(step):
 
 
 def measure_composed(cname, batch, prims, regions=5, warmup=3):
+    """One path alone: the composed sum of an edited list (CatConvMish in plain torch), or the default list's step."""
     import torch
-    c, step = build(cname, batch, prims)
-    set_native(False)
+    c, step = build(cname, batch, prims, plain=True)
+    what = 'default list alone' if prims == DEFAULT else 'composed alone'
+    if prims != DEFAULT:
+        set_native(False)
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
     t = [timed(step) for _ in range(regions)]
-    print(f'{"+".join(prims)} {cname} b{batch}: composed alone, tree {ROOT}: median {statistics.median(t):.1f} us '
+    print(f'{"+".join(prims)} {cname} b{batch}: {what}, tree {os.path.basename(ROOT)}: median {statistics.median(t):.1f} us '
           f'(spread {max(t) - min(t):.1f}, {launches(step)} launches)', flush=True)
     return True
 
 
 def measure(cname, batch, prims, regions=5, warmup=3):
     import torch
-    c, step = build(cname, batch, prims)
+    c, native_step = build(cname, batch, prims)
+    # the baseline of a CatConvMish list: the plain-torch module (a model of its own, same seed)
+    steps = {True: native_step, False: build(cname, batch, prims, plain=True)[1] if MISH in prims else native_step}
     for on in (True, False):
         set_native(on)
         for _ in range(warmup):
-            step()
+            steps[on]()
     torch.cuda.synchronize()
     t = {True: [], False: []}
     for _ in range(regions):
         for on in (True, False):
             set_native(on)
-            t[on].append(timed(step))
+            t[on].append(timed(steps[on]))
     n = {}
     for on in (True, False):
         set_native(on)
-        n[on] = launches(step)
+        n[on] = launches(steps[on])
     set_native(True)
     med = {k: statistics.median(v) for k, v in t.items()}
     spr = {k: max(v) - min(v) for k, v in t.items()}
@@ -146,7 +184,7 @@ def moved_bytes(c, batch, prims):
     forward: reads z (Sum; x is y in a search step), p1 (attention), U (conv rows / C tensors), writes out;
     backward: reads g and the same operands, writes dV (conv rows / C tensors) and dx (Sum)."""
     T = batch * c['C'] * c['L'] * 4
-    rows = (2 if 'LinearGLU' in prims else 0) + (1 if 'ConcatFC' in prims else 0)
+    rows = (2 if 'LinearGLU' in prims else 0) + (1 if 'ConcatFC' in prims or MISH in prims else 0)
     ops = ('Sum' in prims) + ('ScaleDotAttn' in prims) + rows
     return (ops + 1) * T, (1 + ops + rows + ('Sum' in prims)) * T
 
@@ -181,17 +219,15 @@ def stats(path, cname, batch, prims):
 
 def drive(a):
     """Every leg as a child process under its own time limit; the first failure ends the run."""
-    for prims in LISTS:
+    lists = [DEFAULT] if a.default_list else [p for p in LISTS if not a.only or a.only in p]
+    for prims in lists:
         for cname, batch in CASES:
             cmd = [sys.executable, HERE, '--leg', f'{cname}:{batch}', '--list', ','.join(prims)]
-            if a.composed_only:
+            if a.composed_only or a.default_list:
                 cmd.append('--composed-only')
             if a.tree:
                 cmd += ['--tree', a.tree]
-            try:
-                rc = subprocess.run(cmd, timeout=LEG_SECONDS).returncode
-            except subprocess.TimeoutExpired:
-                rc = 124
+            rc = subprocess.run(['timeout', '-k', '10', str(LEG_SECONDS)] + cmd).returncode
             if rc != 0:
                 print(f'leg {" ".join(cmd[2:])} ended with status {rc}: stopping here', flush=True)
                 return rc
@@ -206,6 +242,8 @@ def main():
     ap.add_argument('--stats', help='results of such a run: moved bytes over duration of the two new kernels')
     ap.add_argument('--tree', help='import the project from this checkout instead of the one the tool lies in')
     ap.add_argument('--composed-only', action='store_true', help='time the composed path alone')
+    ap.add_argument('--default-list', action='store_true', help='driver: time the default list\'s step alone')
+    ap.add_argument('--only', help='driver: only the lists that hold this primitive')
     a = ap.parse_args()
     prims = a.list.split(',') if a.list else None
     if a.trace:
