@@ -924,6 +924,96 @@ class FcEdgeSumFn(Function):
         return (None, None, None, None, None, dw, *dxs, *grads)
 
 
+class FoundFcEdgesFn(Function):
+    """The E fc_relu / fc_mish edges of a found cell (Found_FusionCell.forward model.py:140-148 calling FC_Relu /
+    FC_Mish.forward operations.py:22-65), every edge with an output of its own:
+        h_e = Dropout(BatchNorm1d(act_e(Linear_e(x_e)))),   act_e ReLU (kinds[e] = 0) | Mish (1).
+    Forward: zero-fill of the BatchNorm batch sums (training only), the grouped GEMM once per kind present (one or
+    two launches), finalise + activation + dropout of all edges in one launch.  Backward — called once by autograd,
+    when all E output gradients exist —: zero-fill, reductions, dU, grouped GEMMs: four launches whatever E is.
+    tensors: the E sources, then per edge linear.weight, linear.bias, bn.weight, bn.bias; buffers[e] =
+    (running_mean, running_var, num_batches_tracked), updated in place in training mode.  Sources that are the same
+    tensor object share one gradient (returned for the first of them); sources that need no gradient get no
+    data-gradient tiles.  The pre-activations stay reachable as `out.grad_fn.fc_U` (E, b, C, L).
+
+    Dropout sites: one per edge, made edge by edge in the order of `tensors` (genotype order).  Found_FusionCell
+    evaluates every FC edge that reads a cell input in ONE call in front of its step loop, so the sites of those
+    edges all precede the step nodes' sites; the reference runs step i's two edge sites, then step i's node sites.
+    The masks are as good as any — nothing depends on the order — but a comparison that injects exported masks into a
+    restatement of the reference's execution order has to permute them accordingly."""
+
+    @staticmethod
+    def forward(ctx, E, kinds, training, p, buffers, *tensors):
+        xs_in = tensors[:E]
+        _require_gpu(xs_in[0], 'FC edges of a found network')
+        xs = [_c(_f32(t)) for t in xs_in]
+        b, Cc, L = xs[0].shape
+        if len(kinds) != E or any(k not in (0, 1) for k in kinds) or any(x.shape != xs[0].shape for x in xs) \
+                or not lib.fc_edges_ok(E, 1, 1, b, Cc, L):
+            raise lib.BmnasError(f'FoundFcEdgesFn: unsupported group (E={E}, kinds={kinds}, '
+                                 f'x {[tuple(x.shape) for x in xs]})')
+        if training and b * L < 2:
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {[b, Cc, L]}')
+        dev = xs[0].device
+        prm = [[_c(_f32(t)) for t in tensors[E + 4 * e:E + 4 * e + 4]] for e in range(E)]
+        U = torch.empty((E, b, Cc, L), device=dev, dtype=torch.float32)
+        chan = torch.empty((E, 4 * Cc), device=dev, dtype=torch.float32)
+        stat = None
+        if training:
+            adv = K.DROP.take_advance() if p > 0.0 else None
+            stat = torch.empty((E, 2 * Cc), device=dev, dtype=torch.float32)
+            lib.fc_edges_zero(stat.view(-1), 'fwd', adv)
+        drops = [K.DROP.make(p, b * Cc * L, training) for _ in range(E)]
+        edges = [dict(x=xs[e], U=U[e],
+                      fc=[dict(W=prm[e][0], bias=prm[e][1], bn_w=prm[e][2], bn_b=prm[e][3],
+                               running_mean=buffers[e][0], running_var=buffers[e][1],
+                               num_batches_tracked=buffers[e][2], stat=None if stat is None else stat[e],
+                               chan=chan[e], drop=drops[e], col=0, mish=kinds[e])]) for e in range(E)]
+        # the GEMM's batch-sum epilogue takes one activation per launch: one launch per kind present
+        for kind in (0, 1):
+            sub = [edges[e] for e in range(E) if kinds[e] == kind]
+            if sub:
+                lib.fc_edges_gemm_fwd(lib.make_fc_edges(sub), 1, training, b, Cc, L)
+        outs = [torch.empty_like(xs[0]) for _ in range(E)]
+        lib.fc_found_fwd(lib.make_fc_edges(edges), training, outs, b, Cc, L)
+        first = [next(i for i in range(e + 1) if xs_in[i] is xs_in[e]) for e in range(E)]
+        ctx.E, ctx.training, ctx.edges, ctx.first = E, training, edges, first
+        ctx.fc_U, ctx.fc_chan, ctx.fc_drops = U, chan, drops
+        ctx.wshapes = [[tuple(t.shape) for t in tensors[E + 4 * e:E + 4 * e + 2]] for e in range(E)]
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        E, edges, U = ctx.E, ctx.edges, ctx.fc_U
+        _, b, Cc, L = U.shape
+        dev = U.device
+        gs = [torch.zeros_like(U[e]) if g is None else _c(g) for e, g in enumerate(gs)]
+        per = 2 * Cc + Cc * Cc + Cc                    # bn_grad | dW | dbias of one edge
+        pool = torch.empty(E * per, device=dev, dtype=torch.float32)
+        lib.fc_edges_zero(pool, 'bwd')
+        dU = torch.empty_like(U)
+        grads = []
+        for e in range(E):
+            o = e * per
+            q = edges[e]['fc'][0]
+            edges[e]['dU'] = dU[e]
+            q['bn_grad'], q['dW'], q['dbias'] = pool[o:o + 2 * Cc], pool[o + 2 * Cc:o + 2 * Cc + Cc * Cc], \
+                pool[o + 2 * Cc + Cc * Cc:o + per]
+            ws, bs = ctx.wshapes[e]
+            grads += [q['dW'].view(ws), q['dbias'].view(bs), q['bn_grad'][:Cc], q['bn_grad'][Cc:]]
+        arr = lib.make_fc_edges(edges)
+        lib.fc_found_bwd_reduce(arr, gs, b, Cc, L)
+        lib.fc_found_bwd_du(arr, gs, ctx.training, b, Cc, L)
+        dxs, targets, masks = [None] * E, [], []
+        for e in range(E):
+            if ctx.first[e] == e and ctx.needs_input_grad[5 + e]:
+                dxs[e] = torch.empty_like(gs[0])
+                targets.append(dxs[e])
+                masks.append(sum(1 << i for i in range(E) if ctx.first[i] == e))
+        lib.fc_found_bwd_gemm(arr, targets, masks, b, Cc, L)
+        return (None, None, None, None, None, *dxs, *grads)
+
+
 # ---------------------------------------------------------------- search NodeMixedOp
 class NodeMixedFn(Function):
     """NodeMixedOp.forward(x, y, weights) (node_operations.py:118-120) as one fused

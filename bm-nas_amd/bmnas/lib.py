@@ -276,6 +276,10 @@ SIGNATURES = {
     'bmnas_fc_edges_bwd_du': ([C.POINTER(FcEdge), _I, _I, _P, _I, _P, _I, _I, _I, _I, _P], _I),
     'bmnas_fc_edges_bwd_gemm': ([C.POINTER(FcEdge), _I, _I, _P, _I, _U32, _P, _PP, C.POINTER(C.c_uint32), _I, _I,
                                  _I, _I, _P], _I),
+    'bmnas_fc_found_fwd': ([C.POINTER(FcEdge), _I, _I, _PP, _I, _I, _I, _P], _I),
+    'bmnas_fc_found_bwd_reduce': ([C.POINTER(FcEdge), _I, _PP, _I, _I, _I, _P], _I),
+    'bmnas_fc_found_bwd_du': ([C.POINTER(FcEdge), _I, _PP, _I, _I, _I, _I, _P], _I),
+    'bmnas_fc_found_bwd_gemm': ([C.POINTER(FcEdge), _I, _PP, C.POINTER(C.c_uint32), _I, _I, _I, _I, _P], _I),
 }
 
 _lib = None
@@ -1320,4 +1324,29 @@ def fc_edges_bwd_gemm(arr, F, w, P, skip_cols, g, dxs, dx_edges, b, Cc, L):
     masks = (C.c_uint32 * max(1, len(dx_edges)))(*[int(m) for m in dx_edges])
     _check(load().bmnas_fc_edges_bwd_gemm(arr, len(arr), F, _ptr(w), P, skip_cols, _ptr(g), _ptrs(dxs), masks,
                                           len(dxs), b, Cc, L, _stream()), 'fc_edges_bwd_gemm')
+    FC_EDGE_LAUNCHES['bwd'] += 1
+
+
+# ------------------------------------------------------------- FC edges of a found network (csrc/fcedge.hip)
+def fc_found_fwd(arr, training, outs, b, Cc, L):
+    """outs[e] = drop_e(BatchNorm(act_e(U_e))) for the E edges of `arr` (make_fc_edges, one FC primitive each)."""
+    _check(load().bmnas_fc_found_fwd(arr, len(arr), int(training), _ptrs(outs), b, Cc, L, _stream()), 'fc_found_fwd')
+    FC_EDGE_LAUNCHES['fwd'] += 1
+
+
+def fc_found_bwd_reduce(arr, gs, b, Cc, L):
+    _check(load().bmnas_fc_found_bwd_reduce(arr, len(arr), _ptrs(gs), b, Cc, L, _stream()), 'fc_found_bwd_reduce')
+    FC_EDGE_LAUNCHES['bwd'] += 1
+
+
+def fc_found_bwd_du(arr, gs, training, b, Cc, L):
+    _check(load().bmnas_fc_found_bwd_du(arr, len(arr), _ptrs(gs), int(training), b, Cc, L, _stream()),
+           'fc_found_bwd_du')
+    FC_EDGE_LAUNCHES['bwd'] += 1
+
+
+def fc_found_bwd_gemm(arr, dxs, dx_edges, b, Cc, L):
+    masks = (C.c_uint32 * max(1, len(dx_edges)))(*[int(m) for m in dx_edges])
+    _check(load().bmnas_fc_found_bwd_gemm(arr, len(arr), _ptrs(dxs), masks, len(dxs), b, Cc, L, _stream()),
+           'fc_found_bwd_gemm')
     FC_EDGE_LAUNCHES['bwd'] += 1

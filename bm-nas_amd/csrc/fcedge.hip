@@ -10,6 +10,14 @@
 //             fc_bwd_gemm_k   dx = W^T dU + wskip g (edges reading one tensor share the destination: their K ranges are
 //                             concatenated) and dW = dU x^T (split over the batch columns, atomics) as two block classes
 // The per-edge pointers travel by value in the kernel arguments (uniform index -> scalar loads).
+//
+// FC edges of a FOUND network (reference models/search/darts/model.py:140-148 with operations.py:22-65): every edge keeps
+// its own output, h_e = Dropout(BatchNorm1d(act_e(Linear_e(x_e)))) — no weight row, no skip term, no sum over edges,
+// and the kind (ReLU | Mish) is per edge.  The two GEMM kernels above serve as they are (F = 1); the elementwise
+// kernels come in "separate outputs" form with the edge as blockIdx.z:
+//   forward   fc_sep_fwd_k         BatchNorm finalisation in the launch, out_e = drop_e(scale act_e(U_e) + shift)
+//   backward  fc_sep_bwd_reduce_k  dBN.weight / dBN.bias of every edge from its own incoming gradient
+//             fc_sep_bwd_du_k      dU_e = BatchNorm input gradient * act_e'(U_e), dbias_e
 #include "common.hpp"
 #include "../../include/bmnas_hip.h"
 #include "mish.hpp"
@@ -478,6 +486,144 @@ __global__ __launch_bounds__(256) void fc_bwd_gemm_k(const GemmBwdArgs a, int n,
   }
 }
 
+// ------------------------------------------------------------------------------------------ found networks
+// One output per edge: edge = blockIdx.z, kind / output / incoming gradient / dropout offset per edge.
+struct SepFwdArgs {
+  const float* U[FC_E];
+  float* out[FC_E];
+  MixPrim p[FC_E];
+  uint64_t doff[FC_E];
+  int mish[FC_E];
+  DropCfg drop;
+};
+
+// grid (C / 16, ceil(b / nsub), edge)
+__global__ __launch_bounds__(256) void fc_sep_fwd_k(const SepFwdArgs a, int training, int b, int C, int lgL) {
+  const Slab sl = slab_of(lgL);
+  const int L = 1 << lgL, j = blockIdx.z;
+  DropRt dr = drop_begin(a.drop);
+  dr.off += a.doff[j] - a.drop.offset;                 // the step counter plus the edge's own site
+  const int s = blockIdx.y * sl.nsub + sl.sub;
+  const bool valid = s < b;
+  const int sc = valid ? s : 0;
+  const int c = sl.c;
+  const int64_t e = ((int64_t)sc * C + c) * L + sl.l0;
+  const bool writer = blockIdx.y == 0 && sl.sub == 0 && sl.l0 == 0;
+  const float nN = (float)b * (float)L;
+  const MixPrim& p = a.p[j];
+  const int mish = a.mish[j];
+  const float4 u4 = ld4(a.U[j] + e);
+  float mean, var;
+  if (training) {
+    const float md = p.stat[c] / nN;
+    mean = act_f(p.bias[c], mish) + md;
+    var = fmaxf(p.stat[C + c] / nN - md * md, 0.f);
+  } else {
+    mean = p.rm[c];
+    var = p.rv[c];
+  }
+  const float rstd = rsqrtf(var + FC_EPS);
+  const float scale = p.bn_w[c] * rstd, shift = p.bn_b[c] - mean * scale;
+  if (writer) {
+    p.chan[c] = mean;
+    p.chan[C + c] = rstd;
+    p.chan[2 * C + c] = scale;
+    p.chan[3 * C + c] = shift;
+    if (training) {
+      p.rm[c] = (1.f - FC_MOMENTUM) * p.rm[c] + FC_MOMENTUM * mean;
+      p.rv[c] = (1.f - FC_MOMENTUM) * p.rv[c] + FC_MOMENTUM * var * (nN / (nN - 1.f));
+      if (blockIdx.x == 0 && threadIdx.x == 0 && p.nbt != nullptr) p.nbt[0] += 1;
+    }
+  }
+  const float4 a4 = act4(u4, mish);
+  const float4 dm = drop_mult4(dr, (uint64_t)e);
+  const float4 o = make_float4(dm.x * (scale * a4.x + shift), dm.y * (scale * a4.y + shift),
+                               dm.z * (scale * a4.z + shift), dm.w * (scale * a4.w + shift));
+  if (valid) st4(a.out[j] + e, o);
+}
+
+struct SepBwdArgs {
+  const float* U[FC_E];
+  const float* g[FC_E];
+  float* dU[FC_E];
+  const float* chan[FC_E];
+  float* bn_grad[FC_E];
+  float* dbias[FC_E];
+  uint64_t doff[FC_E];
+  int mish[FC_E];
+  DropCfg drop;
+};
+
+// grid (C / 16, ceil(b / FC_SPC), edge)
+__global__ __launch_bounds__(256) void fc_sep_bwd_reduce_k(const SepBwdArgs a, int b, int C, int lgL) {
+  __shared__ float red[256];
+  const Slab sl = slab_of(lgL);
+  const int L = 1 << lgL, j = blockIdx.z, c = sl.c;
+  DropRt dr = drop_begin(a.drop);
+  dr.off += a.doff[j] - a.drop.offset;
+  const int s_end = min(b, (int)(blockIdx.y + 1) * FC_SPC);
+  const float* __restrict__ ch = a.chan[j];
+  const float* __restrict__ g = a.g[j];
+  const float* __restrict__ U = a.U[j];
+  const float mean = ch[c], rstd = ch[C + c];
+  const int mish = a.mish[j];
+  float sdy = 0.f, sda = 0.f;
+  for (int s = blockIdx.y * FC_SPC + sl.sub; s < s_end; s += sl.nsub) {
+    const int64_t e = ((int64_t)s * C + c) * L + sl.l0;
+    const float4 g4 = ld4(g + e);
+    const float4 a4 = act4(ld4(U + e), mish);
+    const float4 gm = f4_mul(g4, drop_mult4(dr, (uint64_t)e));       // dy = mask * g
+    const float4 ah = make_float4((a4.x - mean) * rstd, (a4.y - mean) * rstd, (a4.z - mean) * rstd,
+                                  (a4.w - mean) * rstd);
+    sdy += f4_hsum(gm);
+    sda += f4_dot(gm, ah);
+  }
+  const bool lead = sl.sub == 0 && sl.l0 == 0;
+  const float t1 = channel_sum(sda, sl, lgL, red);
+  const float t2 = channel_sum(sdy, sl, lgL, red);
+  if (lead) {
+    atomicAdd(a.bn_grad[j] + c, t1);
+    atomicAdd(a.bn_grad[j] + C + c, t2);
+  }
+}
+
+// grid as fc_sep_bwd_reduce_k
+__global__ __launch_bounds__(256) void fc_sep_bwd_du_k(const SepBwdArgs a, int training, int b, int C, int lgL) {
+  __shared__ float red[256];
+  const Slab sl = slab_of(lgL);
+  const int L = 1 << lgL, j = blockIdx.z, c = sl.c;
+  DropRt dr = drop_begin(a.drop);
+  dr.off += a.doff[j] - a.drop.offset;
+  const int s_end = min(b, (int)(blockIdx.y + 1) * FC_SPC);
+  const float inv = 1.f / ((float)b * (float)L);
+  const float* __restrict__ ch = a.chan[j];
+  const float* __restrict__ g = a.g[j];
+  const float* __restrict__ U = a.U[j];
+  float* __restrict__ dU = a.dU[j];
+  const float mean = ch[c], rstd = ch[C + c], scale = ch[2 * C + c];
+  const float k0 = training ? a.bn_grad[j][C + c] * inv : 0.f;      // dBN.bias / (b L)
+  const float k1 = training ? a.bn_grad[j][c] * inv : 0.f;          // dBN.weight / (b L)
+  const int mish = a.mish[j];
+  float sdu = 0.f;
+  for (int s = blockIdx.y * FC_SPC + sl.sub; s < s_end; s += sl.nsub) {
+    const int64_t e = ((int64_t)s * C + c) * L + sl.l0;
+    const float4 g4 = ld4(g + e);
+    const float4 u4 = ld4(U + e);
+    const float4 a4 = act4(u4, mish), d4 = dact4(u4, mish);
+    const float4 dy = f4_mul(g4, drop_mult4(dr, (uint64_t)e));
+    float4 du;
+    du.x = scale * (dy.x - k0 - (a4.x - mean) * rstd * k1) * d4.x;
+    du.y = scale * (dy.y - k0 - (a4.y - mean) * rstd * k1) * d4.y;
+    du.z = scale * (dy.z - k0 - (a4.z - mean) * rstd * k1) * d4.z;
+    du.w = scale * (dy.w - k0 - (a4.w - mean) * rstd * k1) * d4.w;
+    st4(dU + e, du);
+    sdu += f4_hsum(du);
+  }
+  const bool lead = sl.sub == 0 && sl.l0 == 0;
+  const float t = channel_sum(sdu, sl, lgL, red);
+  if (lead) atomicAdd(a.dbias[j] + c, t);
+}
+
 int check_common(const bmnas_fc_edge_t* edges, int n, int F, int P, int b, int C, int L) {
   if (!edges || n <= 0 || b <= 0) return BMNAS_E_ARG;
   if (!bmnas_fc_edges_ok(n, F, P, b, C, L)) return (n > FC_E || P > 8) ? BMNAS_E_LIMIT : BMNAS_E_SHAPE;
@@ -630,6 +776,107 @@ extern "C" int bmnas_fc_edges_bwd_gemm(const bmnas_fc_edge_t* edges, int n, int 
   if (blocks > 0x7fffffff) return BMNAS_E_LIMIT;
   hipLaunchKernelGGL(fc_bwd_gemm_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, n, F, w, P, skip_cols,
                      g, n_dx, b, C, lg_of(L));
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ found networks
+namespace {
+
+// arguments first, then shape, then limit; the edges' one FC primitive is fc[0]
+int check_found(const bmnas_fc_edge_t* edges, int E, int b, int C, int L) {
+  if (!edges || E <= 0 || b <= 0) return BMNAS_E_ARG;
+  if (!bmnas_fc_edges_ok(E, 1, 1, b, C, L)) return E > FC_E ? BMNAS_E_LIMIT : BMNAS_E_SHAPE;
+  for (int j = 0; j < E; ++j) {
+    const bmnas_fc_prim_t& p = edges[j].fc[0];
+    if (!edges[j].U || !p.chan || (p.mish != 0 && p.mish != 1)) return BMNAS_E_ARG;
+    // one dropout configuration per group: the sites differ in their offsets only
+    if (p.drop.thr != edges[0].fc[0].drop.thr || p.drop.seed != edges[0].fc[0].drop.seed ||
+        p.drop.step != edges[0].fc[0].drop.step)
+      return BMNAS_E_ARG;
+  }
+  return 0;
+}
+
+int fill_sep_bwd(SepBwdArgs& a, const bmnas_fc_edge_t* edges, int E, const float* const* gs) {
+  if (!gs) return BMNAS_E_ARG;
+  a.drop = common_drop(edges);
+  for (int j = 0; j < E; ++j) {
+    const bmnas_fc_prim_t& p = edges[j].fc[0];
+    if (!gs[j] || !p.bn_grad) return BMNAS_E_ARG;
+    a.U[j] = edges[j].U; a.g[j] = gs[j]; a.dU[j] = edges[j].dU; a.chan[j] = p.chan; a.bn_grad[j] = p.bn_grad;
+    a.dbias[j] = p.dbias; a.doff[j] = p.drop.offset; a.mish[j] = p.mish;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int bmnas_fc_found_fwd(const bmnas_fc_edge_t* edges, int E, int training, float* const* outs, int b, int C,
+                                  int L, void* stream) {
+  if (int rc = check_found(edges, E, b, C, L)) return rc;
+  if (!outs) return BMNAS_E_ARG;
+  SepFwdArgs a = {};
+  a.drop = common_drop(edges);
+  for (int j = 0; j < E; ++j) {
+    const bmnas_fc_prim_t& p = edges[j].fc[0];
+    if (!outs[j] || !p.bias || !p.bn_w || !p.bn_b || !p.running_mean || !p.running_var || (training && !p.stat))
+      return BMNAS_E_ARG;
+    a.U[j] = edges[j].U; a.out[j] = outs[j];
+    a.p[j] = MixPrim{p.stat, p.bias, p.bn_w, p.bn_b, p.running_mean, p.running_var,
+                     (long long*)p.num_batches_tracked, p.chan};
+    a.doff[j] = p.drop.offset; a.mish[j] = p.mish;
+  }
+  const int nsub = 256 / (4 * L);
+  const dim3 grid(C / 16, (b + nsub - 1) / nsub, E);
+  hipLaunchKernelGGL(fc_sep_fwd_k, grid, dim3(256), 0, (hipStream_t)stream, a, training, b, C, lg_of(L));
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_fc_found_bwd_reduce(const bmnas_fc_edge_t* edges, int E, const float* const* gs, int b, int C,
+                                         int L, void* stream) {
+  if (int rc = check_found(edges, E, b, C, L)) return rc;
+  SepBwdArgs a = {};
+  if (int rc = fill_sep_bwd(a, edges, E, gs)) return rc;
+  const dim3 grid(C / 16, (b + FC_SPC - 1) / FC_SPC, E);
+  hipLaunchKernelGGL(fc_sep_bwd_reduce_k, grid, dim3(256), 0, (hipStream_t)stream, a, b, C, lg_of(L));
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_fc_found_bwd_du(const bmnas_fc_edge_t* edges, int E, const float* const* gs, int training, int b,
+                                     int C, int L, void* stream) {
+  if (int rc = check_found(edges, E, b, C, L)) return rc;
+  SepBwdArgs a = {};
+  if (int rc = fill_sep_bwd(a, edges, E, gs)) return rc;
+  for (int j = 0; j < E; ++j)
+    if (!edges[j].dU || !edges[j].fc[0].dbias) return BMNAS_E_ARG;
+  const dim3 grid(C / 16, (b + FC_SPC - 1) / FC_SPC, E);
+  hipLaunchKernelGGL(fc_sep_bwd_du_k, grid, dim3(256), 0, (hipStream_t)stream, a, training, b, C, lg_of(L));
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+// fc_bwd_gemm_k is kind-agnostic: one launch for edges of both kinds (F = 1, no skip term, no weight row)
+extern "C" int bmnas_fc_found_bwd_gemm(const bmnas_fc_edge_t* edges, int E, float* const* dxs,
+                                       const uint32_t* dx_edges, int n_dx, int b, int C, int L, void* stream) {
+  if (!edges || E <= 0 || b <= 0 || n_dx < 0 || n_dx > FC_E || (n_dx > 0 && (!dxs || !dx_edges))) return BMNAS_E_ARG;
+  if (!bmnas_fc_edges_ok(E, 1, 1, b, C, L)) return E > FC_E ? BMNAS_E_LIMIT : BMNAS_E_SHAPE;
+  GemmBwdArgs a = {};
+  for (int j = 0; j < E; ++j) {
+    if (!edges[j].x || !edges[j].dU || !edges[j].fc[0].W || !edges[j].fc[0].dW) return BMNAS_E_ARG;
+    a.x[j] = edges[j].x; a.dU[j] = edges[j].dU; a.W[j][0] = edges[j].fc[0].W; a.dW[j][0] = edges[j].fc[0].dW;
+  }
+  for (int q = 0; q < n_dx; ++q) {
+    if (!dxs[q] || dx_edges[q] == 0u || (dx_edges[q] >> E)) return BMNAS_E_ARG;
+    a.dx[q] = dxs[q]; a.qmask[q] = dx_edges[q];
+  }
+  const int N = b * L, rt = (C + 63) / 64, ctl = (N + 63) / 64, kch = (N + FC_KCH - 1) / FC_KCH;
+  const int64_t blocks = (int64_t)n_dx * rt * ctl + (int64_t)E * rt * rt * kch;
+  if (blocks > 0x7fffffff) return BMNAS_E_LIMIT;
+  hipLaunchKernelGGL(fc_bwd_gemm_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, E, 1,
+                     (const float*)nullptr, 1, 0u, (const float*)nullptr, n_dx, b, C, lg_of(L));
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

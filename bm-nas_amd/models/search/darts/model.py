@@ -9,7 +9,7 @@ from bmnas.functions import CatLnFn, FoundHeadFn
 
 from .genotypes import *  # noqa: F401,F403
 from .node import Found_FusionNode
-from .operations import OPS
+from .operations import FC_Mish, FC_Relu, OPS, found_fc_apply, found_fc_route
 
 
 class Found_FusionCell(nn.Module):
@@ -48,13 +48,35 @@ class Found_FusionCell(nn.Module):
                 and states[0].is_cuda and states[0].dtype == classifier.weight.dtype
                 and all(getattr(s, '_bmnas_sums', None) is not None for s in states[-M:]))
 
+    def fc_groups(self, num_inputs):
+        """The fc_relu / fc_mish edges by where they can run: (group 0, late).  Group 0 — every FC edge that reads a
+        cell input (source index < num_inputs; a searched genotype has no other, reference model_search.py:130) —
+        runs as ONE FoundFcEdgesFn call in front of the step loop; an FC edge that reads a step output (hand-written
+        genotypes only) gets a call of its own right before its step."""
+        fc = [e for e, op in enumerate(self._ops) if isinstance(op, (FC_Relu, FC_Mish))]
+        return [e for e in fc if self._indices[e] < num_inputs], [e for e in fc if self._indices[e] >= num_inputs]
+
+    def _fc_edges(self, ids, states):
+        """{edge: output} for the FC edges `ids` on the grouped kernels, or {} where found_fc_route says 'composed'
+        (the edges are then evaluated op by op at their usual place in the step loop)."""
+        ops = [self._ops[e] for e in ids]
+        xs = [states[self._indices[e]] for e in ids]
+        if found_fc_route(ops, xs) != 'fc':
+            return {}
+        return dict(zip(ids, found_fc_apply(ops, xs)))
+
     def forward(self, input_features, classifier=None):
         """classifier (Found_FusionNetwork.forward_classified): the bmnas.nn.Linear the cell's output feeds — the call
         then returns ITS output."""
         states = list(input_features)
+        group0, late = self.fc_groups(len(states))
+        done = self._fc_edges(group0, states)
         for i in range(self._steps):
-            h1 = self._ops[2 * i](states[self._indices[2 * i]])
-            h2 = self._ops[2 * i + 1](states[self._indices[2 * i + 1]])
+            for e in (2 * i, 2 * i + 1):
+                if e in late:
+                    done.update(self._fc_edges([e], states))
+            h1, h2 = (done.pop(e) if e in done else self._ops[e](states[self._indices[e]])
+                      for e in (2 * i, 2 * i + 1))
             states.append(self._step_nodes[i](h1, h2))
         M = self._multiplier
         if classifier is not None and self.head_fusable(classifier, states):

@@ -6,14 +6,16 @@ kernels: with the default PRIMITIVES ['none', 'skip'] the mixed edge is the HIP 
 kernel (bmnas_mixsum_fwd/bwd).  FC_Relu / FC_Mish are not in the default search space
 (SURVEY.md a14): they stay ordinary PyTorch modules (same state_dict keys, usable alone), and the
 sum over the incoming edges of a cell / node step runs them on the grouped kernels of
-csrc/fcedge.hip (bmnas.functions.FcEdgeSumFn) — general_edge_sum below.
+csrc/fcedge.hip (bmnas.functions.FcEdgeSumFn) — general_edge_sum below.  The fc_relu / fc_mish edges of a FOUND
+cell (each with an output of its own) run on the same file's grouped kernels through found_fc_route /
+found_fc_apply (bmnas.functions.FoundFcEdgesFn).
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from bmnas import lib
-from bmnas.functions import FC_KINDS, FcEdgeSumFn, MixSumFn
+from bmnas.functions import FC_KINDS, FcEdgeSumFn, FoundFcEdgesFn, MixSumFn
 
 from .genotypes import *  # noqa: F401,F403
 from .genotypes import PRIMITIVES
@@ -97,7 +99,7 @@ def mixed_edge_sum(states, weights, offset):
     return MixSumFn.apply(w[offset:offset + n, 1], *states)
 
 
-FC_EDGES_NATIVE = True      # False: general_edge_sum always composes (A/B timing, tests of the fallback)
+FC_EDGES_NATIVE = True      # False: general_edge_sum and the found cell's FC edges always compose (A/B timing, tests)
 _BUILTIN = {'none': Zero, 'skip': Identity, 'fc_relu': FC_Relu, 'fc_mish': FC_Mish}
 
 
@@ -167,3 +169,36 @@ def fc_edge_sum_apply(ops, states, rows, prims, offset=0):
             params += [op.linear.weight, op.linear.bias, op.bn.weight, op.bn.bias]
         buffers.append([(op.bn.running_mean, op.bn.running_var, op.bn.num_batches_tracked) for op in row])
     return FcEdgeSumFn.apply(n, tuple(prims), fcs[0][0].training, fcs[0][0].dropout.p, buffers, rows, *states, *params)
+
+
+def found_fc_route(ops, xs):
+    """How a found cell evaluates the FC edges `ops` (FC_Relu / FC_Mish modules) over their sources `xs`: 'fc'
+    (FoundFcEdgesFn: one group of launches) or 'composed' (op(x) edge by edge — subclassed modules, shapes outside
+    the kernels' limits, CPU tensors, modules in different modes).  Host logic only."""
+    if not (FC_EDGES_NATIVE and len(ops) > 0 and len(ops) == len(xs)):
+        return 'composed'
+    if any(type(op) is not FC_Relu and type(op) is not FC_Mish for op in ops):
+        return 'composed'
+    x = xs[0]
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+            and all(h.is_cuda and h.dtype == x.dtype and h.shape == x.shape for h in xs)):
+        return 'composed'
+    t = ops[0].training
+    same_mode = all(op.training == t and op.bn.training == t and op.dropout.training == t
+                    and op.dropout.p == ops[0].dropout.p and op.bn.track_running_stats and op.bn.affine
+                    and op.bn.momentum == 0.1 and op.bn.eps == 1e-5 and op.bn.running_mean is not None
+                    for op in ops)
+    b, Cc, L = x.shape
+    if not same_mode or not lib.fc_edges_ok(len(ops), 1, 1, b, Cc, L):
+        return 'composed'
+    return 'fc'
+
+
+def found_fc_apply(ops, xs):
+    """FoundFcEdgesFn over the FC modules `ops` and their sources `xs` -> one output per edge."""
+    params, buffers = [], []
+    for op in ops:
+        params += [op.linear.weight, op.linear.bias, op.bn.weight, op.bn.bias]
+        buffers.append((op.bn.running_mean, op.bn.running_var, op.bn.num_batches_tracked))
+    kinds = tuple(1 if type(op) is FC_Mish else 0 for op in ops)
+    return FoundFcEdgesFn.apply(len(ops), kinds, ops[0].training, ops[0].dropout.p, buffers, *xs, *params)

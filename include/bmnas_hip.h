@@ -932,6 +932,36 @@ int bmnas_fc_edges_bwd_gemm(const bmnas_fc_edge_t* edges, int n, int F, const fl
                             const float* g, float* const* dxs, const uint32_t* dx_edges, int n_dx, int b, int C,
                             int L, void* stream);
 
+/* ---- FC edges of a found network (csrc/fcedge.hip) ------------------------------------------------
+ * A genotype found over an edited PRIMITIVES list names cell-level edges 'fc_relu' / 'fc_mish'; Found_FusionCell
+ * (model.py:140-148) evaluates each as h_e = OPS[name](C, L, args)(x_src(e)) with FC_Relu / FC_Mish
+ * (operations.py:22-65): h_e = Dropout(BatchNorm1d(act_e(Linear_e(x_e)))).  E such edges as one group of launches:
+ * every edge keeps its own output, incoming gradient, parameters, buffers and dropout site, and its own kind
+ * (fc[0].mish).  edges[e].fc[0] is the edge's one FC primitive (fc[1], col are not read); U / dU are (b, C, L).
+ * The pre-activations come from bmnas_fc_edges_gemm_fwd with F = 1, called once per kind present in the group
+ * (that launch takes one kind: its batch-sum epilogue applies it).  Limits: bmnas_fc_edges_ok(E, 1, 1, b, C, L);
+ * BMNAS_E_ARG, then BMNAS_E_SHAPE, then BMNAS_E_LIMIT (E > BMNAS_FC_MAX_EDGES) otherwise.  All edges of a group
+ * share one dropout configuration (thr, seed, step); the sites differ in their offsets. */
+/* BatchNorm finalisation inside the launch (training: from stat — variance about act(bias[c]) —, chan written,
+ * running statistics and num_batches_tracked updated; eval: from the running statistics), then
+ * outs[e] = drop_e(scale_e act_e(U_e) + shift_e)  (reference operations.py:22-65, model.py:140-148). */
+int bmnas_fc_found_fwd(const bmnas_fc_edge_t* edges, int E, int training, float* const* outs, int b, int C, int L,
+                       void* stream);
+/* gs[e]: gradient of outs[e].  bn_grad_e (ZERO-FILLED) += (sum dy a_hat | sum dy) per channel, dy = mask_e gs[e]
+ * (reference operations.py:22-65, model.py:140-148). */
+int bmnas_fc_found_bwd_reduce(const bmnas_fc_edge_t* edges, int E, const float* const* gs, int b, int C, int L,
+                              void* stream);
+/* dU_e = scale (dy - (dBN.bias + a_hat dBN.weight) / (b L)) act_e'(U_e) (training) | scale dy act_e'(U_e) (eval);
+ * dbias_e (ZERO-FILLED) += sum dU_e  (reference operations.py:22-65, model.py:140-148). */
+int bmnas_fc_found_bwd_du(const bmnas_fc_edge_t* edges, int E, const float* const* gs, int training, int b, int C,
+                          int L, void* stream);
+/* The data- and weight-gradient GEMMs of all E edges, whatever their kinds, in one grid (the kernel of
+ * bmnas_fc_edges_bwd_gemm without a skip term): dxs[q] = sum_{e in bits of dx_edges[q]} W_e^T dU_e — edges that read
+ * the same tensor share one destination; n_dx may be 0 — and dW_e (ZERO-FILLED) += dU_e x_e^T
+ * (reference operations.py:22-65, model.py:140-148). */
+int bmnas_fc_found_bwd_gemm(const bmnas_fc_edge_t* edges, int E, float* const* dxs, const uint32_t* dx_edges,
+                            int n_dx, int b, int C, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,12 +12,21 @@
                                                        # the composed path alone, imported from another checkout (the
                                                        # parent commit, whose only path it is): has the fallback got slower?
 
+    python tools/fc_edges_time.py --stage found        # the FOUND stage: a found network whose four cell-level edges are
+                                                       # fc_relu / fc_mish (both kinds, two edges reading one input;
+                                                       # bmnas.functions.FoundFcEdgesFn) at MM-IMDB b128 and NTU b64, one
+                                                       # eager and one captured training step (forward + criterion +
+                                                       # backward + Adam); native and composed alternate, five regions
+                                                       # each; every leg is a child process under its own time limit
+    python tools/fc_edges_time.py --stage found --composed-only --tree PARENT_CHECKOUT
+
 A step = forward + criterion + backward in train mode with dropout on, bench.CONFIGS shapes, bench.synth_batch data.
 """
 import argparse
 import csv
 import os
 import statistics
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -174,13 +183,118 @@ def stats(path, cname, batch):
               f'{PEAK_FP32_MFMA / 1e12:.1f} TF fp32-MFMA peak')
 
 
+# ------------------------------------------------------------------------------------------------- the found stage
+FOUND_CASES = [('mmimdb', 128), ('ntu', 64)]
+FOUND_EDGES = [('fc_relu', 0), ('fc_mish', 0), ('fc_mish', 1), ('fc_relu', 2)]      # both kinds, input 0 read twice
+LEG_SECONDS = 300
+
+
+def build_found(cname, batch):
+    """-> model, criterion, batch: bench.FoundNet's wiring over bench's fixed step nodes with FOUND_EDGES as the
+    cell-level edges."""
+    import bench as B
+    from bmnas import nn as bnn
+    from models.search.darts.genotypes import Genotype
+    from models.search.darts.model import Found_FusionNetwork
+    c = B.CONFIGS[cname]
+    base = B.found_genotype(cname)
+    geno = Genotype(edges=list(FOUND_EDGES), steps=base.steps, concat=base.concat)
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.fusion_net = Found_FusionNetwork(c['S'], c['M'], c['N'], 2, B.make_args(c), None, geno)
+            self.central_classifier = bnn.Linear(c['M'] * c['C'] * c['L'], c['nout'])
+
+        def forward(self, xs):
+            return self.fusion_net.forward_classified(list(xs), self.central_classifier)
+    torch.manual_seed(2)
+    model = Net().to('cuda:0').train()
+    crit = bnn.BCEWithLogitsLoss() if c['loss'] == 'bce' else bnn.CrossEntropyLoss()
+    xs, y = B.synth_batch(c, batch, torch.device('cuda:0'), 0)
+    return model, crit, [x.detach() for x in xs], y
+
+
+def found_leg(cname, batch, kind, composed_only, regions=5, warmup=3):
+    """One child: `kind` = 'eager' | 'captured'.  Both routes in this process, alternating region by region."""
+    from bmnas.graph import GraphedTrainStep
+    from bmnas.optim import Adam
+    routes = (False,) if composed_only else (True, False)
+    steps = {}
+    for on in routes:
+        set_native(on)
+        model, crit, xs, y = build_found(cname, batch)
+        opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)
+        if kind == 'captured':
+            g = GraphedTrainStep(model, crit, opt, xs, y)           # the route is taken at capture
+            steps[on] = (lambda g=g, xs=xs, y=y: g(xs, y))
+        else:
+            def eager(model=model, crit=crit, opt=opt, xs=xs, y=y, on=on):
+                set_native(on)
+                opt.zero_grad()
+                loss = crit(model(xs), y)
+                loss.backward()
+                opt.step()
+                return loss
+            steps[on] = eager
+    for on in routes:
+        for _ in range(warmup):
+            steps[on]()
+    torch.cuda.synchronize()
+    per = 200 if kind == 'captured' else 20                 # steps per timed region; times are per step
+    t = {on: [] for on in routes}
+    for _ in range(regions):
+        for on in routes:
+            step = steps[on]
+            t[on].append(timed(lambda: [step() for _ in range(per)]) / per)
+    out = []
+    for on in routes:
+        n = launches(steps[on])
+        out.append(f"{'native' if on else 'composed'} median {statistics.median(t[on]):.1f} us (spread "
+                   f'{max(t[on]) - min(t[on]):.1f}, {n} device events)')
+    line = f'found {cname} b{batch} {kind} ({per} steps per region), tree {ROOT}: ' + ' | '.join(out)
+    if not composed_only:
+        med = {on: statistics.median(v) for on, v in t.items()}
+        spread = max(max(v) - min(v) for v in t.values())
+        line += (f' | ratio {med[False] / med[True]:.2f}x | native below composed by more than the larger spread: '
+                 f'{med[True] < med[False] - spread}')
+    if not composed_only:
+        set_native(True)
+    print(line, flush=True)
+
+
+def found_stage(a):
+    """Every leg a child process under its own time limit; nothing more is started after a leg that did not end well."""
+    for cname, batch in FOUND_CASES:
+        for kind in ('eager', 'captured'):
+            cmd = [sys.executable, os.path.abspath(__file__), '--stage', 'found', '--leg', f'{cname}:{batch}:{kind}']
+            if a.composed_only:
+                cmd.append('--composed-only')
+            if a.tree:
+                cmd += ['--tree', a.tree]
+            try:
+                rc = subprocess.run(cmd, timeout=LEG_SECONDS).returncode
+            except subprocess.TimeoutExpired:
+                rc = 124
+            if rc != 0:
+                raise SystemExit(f'leg {cname}:{batch}:{kind} ended with {rc}: stopping')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--trace', help='CNAME:BATCH — run native steps only (for a rocprofv3 --kernel-trace --stats run)')
     ap.add_argument('--stats', help='kernel_stats.csv of such a run: FLOP/s of the GEMM launches')
     ap.add_argument('--tree', help='import the project from this checkout instead of the one the tool lies in')
     ap.add_argument('--composed-only', action='store_true', help='time the composed path alone')
+    ap.add_argument('--stage', choices=['search', 'found'], default='search',
+                    help="found: the FC edges of a found network (a training step, eager and captured)")
+    ap.add_argument('--leg', help='CNAME:BATCH:eager|captured — one leg of --stage found (what the children run)')
     a = ap.parse_args()
+    if a.stage == 'found':
+        if a.leg:
+            cname, batch, kind = a.leg.split(':')
+            return found_leg(cname, int(batch), kind, a.composed_only)
+        return found_stage(a)
     if a.composed_only:
         for cname, batch in CASES:
             measure_composed(cname, batch)
