@@ -581,8 +581,12 @@ int bmnas_bn_bwd_apply(float* dV, const float* U, const float* chan, const float
                        int M, int L, int training, void* stream);
 
 /* ---- architecture-parameter softmax (model_search.py:95, node_search.py:102-103) -----------
- * Row softmax of `rows` rows of `cols` (2 or 4) logits; backward:
- * dlogit[r,:] (=) w[r,:] * (dw[r,:] - sum_p w[r,p]*dw[r,p]). */
+ * Row softmax of `rows` rows of `cols` logits; backward:
+ * dlogit[r,:] (=) w[r,:] * (dw[r,:] - sum_p w[r,p]*dw[r,p]).
+ * cols: the reference's tensors have 2 or 4.  The two single-tensor entry points take any cols >= 1 (one lane
+ * loops over a row; an edited primitive list may give a tensor more than 4 columns).  Every packed form —
+ * bmnas_arch_softmax_multi, bmnas_cell_prologue(_pair), bmnas_backward_epilogue — takes 1 <= cols <= 4 per
+ * tensor and returns BMNAS_E_ARG otherwise (the backward gives a row's columns to four lanes). */
 int bmnas_arch_softmax_fwd(const float* logits, float* w, int rows, int cols, void* stream);
 int bmnas_arch_softmax_bwd(const float* w, const float* dw, float* dlogits, int rows, int cols,
                            void* stream);

@@ -50,6 +50,43 @@ def test_adam_matches_torch(betas, wd):
         assert float((a - b).abs().max()) <= 2e-6 * float(b.abs().max()) + 1e-12
 
 
+def test_adam_unaligned_parameters_take_the_scalar_path():
+    """Leaf parameters at storage offset 1: 4 bytes off the 16-byte alignment every torch allocation has, so every
+    workgroup of adam_multi_k takes its element-by-element branch — whole chunks (1024), the chunk edge on both sides,
+    a tail shorter than one lane's four elements, a second chunk of 3."""
+    from bmnas.optim import Adam
+    sizes = [1, 3, 1023, 1024, 1025, 4099]
+    shapes = [(n,) for n in sizes]
+    init = _make(5, shapes)
+    cpu = [t.clone().requires_grad_(True) for t in init]
+    gpu, stores = [], []
+    for t in init:
+        store = torch.full((t.numel() + 2,), float('nan'), device=dev())
+        store[1:-1].copy_(t)
+        p = store[1:-1].detach().requires_grad_()
+        assert p.is_leaf and p.storage_offset() == 1 and p.data_ptr() % 16 == 4
+        gpu.append(p)
+        stores.append(store)
+    ref = torch.optim.Adam(cpu, lr=1e-2, weight_decay=1e-4)
+    opt = Adam(gpu, lr=1e-2, weight_decay=1e-4)
+    for step in range(6):
+        for c, g_, gr in zip(cpu, gpu, _make(300 + step, shapes)):
+            c.grad, g_.grad = gr.clone(), gr.clone().to(dev())
+        ref.step()
+        opt.step()
+    for c, g_, store in zip(cpu, gpu, stores):
+        scale = float(c.detach().abs().max()) + 1e-3
+        assert float((g_.detach().cpu() - c.detach()).abs().max()) <= 2e-6 * scale + 1e-7
+        assert bool(torch.isnan(store[[0, -1]]).all())               # the floats around the view: untouched
+    sd_ref, sd = ref.state_dict(), opt.state_dict()
+    for k in sd_ref['state']:
+        assert float(sd['state'][k]['step']) == 6.0
+        a, b = sd['state'][k]['exp_avg_sq'].cpu(), sd_ref['state'][k]['exp_avg_sq']
+        assert float((a - b).abs().max()) <= 2e-6 * float(b.abs().max()) + 1e-12
+        a, b = sd['state'][k]['exp_avg'].cpu(), sd_ref['state'][k]['exp_avg']
+        assert float((a - b).abs().max()) <= 2e-6 * float(b.abs().max()) + 1e-12
+
+
 def test_adam_state_dict_roundtrip_with_torch():
     """A torch.optim.Adam checkpoint loads into bmnas.optim.Adam and training continues identically."""
     from bmnas.optim import Adam
