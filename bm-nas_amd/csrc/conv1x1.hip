@@ -102,15 +102,6 @@ __device__ __forceinline__ void bn_tile_stats(const ConvArgs& a, const float4 o,
   }
 }
 
-// ---- split-K variant: ONE memory round trip per wave ------------------------------------------
-// At these sizes (0.1-0.5 GFLOP per GEMM, every operand L2-resident) the kernels are bound
-// by exposed load latency, not by MFMA or bandwidth: a wave that alternates "load a slice /
-// multiply a slice" pays the (loaded) L2 latency once per slice.  Here the four waves of a
-// workgroup split the contraction dimension of ONE (16*TN x 16*TJ) output tile, each wave
-// issues ALL of its operand loads up front (KPW blocks of 16 channels = KPW*4*(TN+TJ) VGPRs),
-// waits once, runs its MFMAs back to back, and the four partial tiles are summed through
-// LDS.  Splitting K four ways also quadruples the number of waves, which is what hides the
-// latency at batch 128.
 // ---- K2 backward as the epilogue of a data-gradient tile (small grids) -------------------------------------
 // NodeCell's out_conv reads cat(states[-node_multiplier:]) (node_search.py:59-61); the last of those states is the
 // output of the last inner step's NodeMixedOp and feeds nothing else, so the out_conv data gradient for its
@@ -183,6 +174,15 @@ __device__ __forceinline__ void mix_ep_tile(const MixEp& m, const float4 gv, con
   }
 }
 
+// ---- split-K variant: ONE memory round trip per wave ------------------------------------------
+// At these sizes (0.1-0.5 GFLOP per GEMM, every operand L2-resident) the kernels are bound
+// by exposed load latency, not by MFMA or bandwidth: a wave that alternates "load a slice /
+// multiply a slice" pays the (loaded) L2 latency once per slice.  Here the four waves of a
+// workgroup split the contraction dimension of ONE (16*TN x 16*TJ) output tile, each wave
+// issues ALL of its operand loads up front (KPW blocks of 16 channels = KPW*4*(TN+TJ) VGPRs),
+// waits once, runs its MFMAs back to back, and the four partial tiles are summed through
+// LDS.  Splitting K four ways also quadruples the number of waves, which is what hides the
+// latency at batch 128.
 template <int TN, int TJ>
 constexpr size_t conv_ksplit_lds();
 
@@ -1492,8 +1492,8 @@ __global__ __launch_bounds__(256, BMNAS_MERGED_OCC) void conv_bwd_all_pipe_k(Con
   // data-gradient tiles) is resident all at once, three workgroups per CU, so the order decides only WHERE a block
   // lands — and a data-gradient tile's 12 chunk steps are the longest chain of the launch (~18 us of its ~19).  With
   // those tiles at the front of the grid the dispatcher gives each its own CU; at the back (rounds 2-3) they filled the
-  // last free slots, several to a CU: 20.95 -> 19.05 us (profiles/r04_bwd_block_order.txt; BMNAS_BWD_ORDER = 0 ... 5
-  // selects A W D / D A W / D W A / W D A / W A D / A D W for that table, default 2).
+  // last free slots, several to a CU: 20.95 -> 19.05 us (profiles/r04_bwd_block_order.txt: a.order = 0 ... 5 is
+  // A W D / D A W / D W A / W D A / W A D / A D W in that table; the host always passes 2).
   const int n_d = (int)gridDim.x - s.groups - n_w;
   int blk = (int)blockIdx.x;                 // -> logical index in [attention | weight gradient | data gradient]
   {
@@ -1714,13 +1714,24 @@ enum ConvFamily { F_KSPLIT, F_PIPE_FWD, F_PIPE_BWD, F_LDS, F_FWD_SDPA_PIPE, F_FW
 long g_family_calls[F_COUNT] = {0};
 #define BMNAS_COUNT(f) (++g_family_calls[f])
 
+// an integer environment switch (each caller keeps the value it read first)
+inline int getenv_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+
 inline int conv_probe() {
 #if BMNAS_BODY_PROBES || defined(BMNAS_CLASS_PROBE)   // (-DBMNAS_CLASS_PROBE: the class-drop bits without the in-body stamps)
-  static const int v = []() { const char* e = getenv("BMNAS_CONV_PROBE"); return e ? atoi(e) : 0; }();
+  static const int v = getenv_int("BMNAS_CONV_PROBE", 0);
   return v;
 #else
   return 0;       // production builds: a stray BMNAS_CONV_PROBE cannot drop gradient tiles (timing builds only)
 #endif
+}
+
+inline int conv_pipe_mode() {        // BMNAS_CONV_PIPE=0 falls back to the split-K kernels (A/B runs)
+  static const int v = getenv_int("BMNAS_CONV_PIPE", 1);
+  return v;
 }
 
 inline int check_shape(int b, int L, int* Lb, int* spw, int* n_groups) {
@@ -1729,6 +1740,125 @@ inline int check_shape(int b, int L, int* Lb, int* spw, int* n_groups) {
   *spw = 16 / L;
   *n_groups = (b + *spw - 1) / *spw;
   return 0;
+}
+
+// ---- argument checks and ConvArgs fill ---------------------------------------------------------------------------
+// The checks every conv entry point makes on the arguments they share, with the codes in the order they have always
+// come: BMNAS_E_ARG, BMNAS_E_SHAPE for the weight fold, BMNAS_E_LIMIT, BMNAS_E_SHAPE.  ok = the entry point's own
+// required pointers (and whatever else it refuses with BMNAS_E_ARG).  ldw4: the forward-shaped entry points refuse an
+// ldw that is no multiple of 4; the backward-shaped ones accept it (their float4 kernels are dispatched on it).
+inline int conv_check(bool ok, int n_src, int C_src, int b, int M, int ldw, int fold_cols, bool ldw4) {
+  if (!ok || n_src < 1 || C_src < 1 || b < 0 || M < 1 || fold_cols < 0) return BMNAS_E_ARG;
+  if (fold_cols % 4 || (fold_cols > 0 && ldw < n_src * C_src + fold_cols)) return BMNAS_E_SHAPE;
+  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
+  if (C_src % 16 || M % 16 || (ldw4 && ldw % 4) || ldw < n_src * C_src) return BMNAS_E_SHAPE;
+  return 0;
+}
+
+// bn_U != NULL asks for the BatchNorm input gradient folded into the launch: what that needs
+inline bool bn_fold_ok(const float* bn_U, const float* bn_chan, const float* bn_grad, int bn_training) {
+  return bn_U == nullptr || (bn_chan && (!bn_training || bn_grad));
+}
+
+// ... and where it goes: the data-gradient tiles (a) and / or the weight-gradient tiles (w) apply it while staging
+inline void set_bn_fold(ConvArgs* a, ConvWArgs* w, const float* bn_U, const float* bn_chan, const float* bn_grad,
+                        int bn_training) {
+  if (a) { a->bn_U = bn_U; a->bn_chan = bn_chan; a->bn_grad = bn_grad; a->bn_train = bn_training; }
+  if (w) { w->bn_U = bn_U; w->bn_chan = bn_chan; w->bn_grad = bn_grad; w->bn_train = bn_training; }
+}
+inline size_t bn_fold_lds(const ConvArgs& a) { return a.bn_U ? (size_t)a.I * sizeof(float4) : 0; }   // its coefficients
+
+// Forward-shaped problem (checked by conv_check): U (b, M, L) = W cat(srcs) + bias.  A NULL among srcs is refused by
+// the caller AFTER its b == 0 return (null_src), as it always has been.
+inline int conv_fwd_args(ConvArgs& a, const float* const* srcs, int n_src, int C_src, const float* W, int ldw,
+                         int fold_cols, const float* bias, float* U, float* part, int stat_shards, int b, int L,
+                         int M) {
+  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  for (int q = 0; q < n_src; ++q) a.act.p[q] = srcs[q];
+  a.dst.p[0] = U;
+  a.W = W; a.bias = bias; a.ldw = ldw;
+  a.part = stat_shards ? nullptr : part; a.stat = stat_shards ? part : nullptr; a.stat_shards = stat_shards;
+  a.Ci = C_src; a.I = n_src * C_src; a.Cj = M; a.J = M;
+  a.b = b; a.L = L; a.acc_mask = 0; a.n_part = a.n_groups; a.probe = conv_probe(); a.fold = fold_cols;
+  return 0;
+}
+inline bool null_src(const ConvIn& in, int n) {
+  for (int q = 0; q < n; ++q)
+    if (!in.p[q]) return true;
+  return false;
+}
+
+// Backward-data-shaped problem (checked by conv_check): dsrcs[q] (b, C_src, L) (=|+=) W^T dU; NULL entries are skipped
+inline int conv_bwd_args(ConvArgs& a, const float* dU, const float* W, int ldw, int fold_cols, float* const* dsrcs,
+                         int n_src, int C_src, uint32_t accumulate_mask, int b, int L, int M) {
+  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  a.act.p[0] = dU;
+  for (int q = 0; q < n_src; ++q) a.dst.p[q] = dsrcs[q];
+  a.W = W; a.bias = nullptr; a.part = nullptr; a.ldw = ldw;
+  a.Ci = M; a.I = M; a.Cj = C_src; a.J = n_src * C_src;
+  a.b = b; a.L = L; a.acc_mask = accumulate_mask; a.probe = conv_probe(); a.fold = fold_cols;
+  return 0;
+}
+
+// problems of a group, longest contraction first: its tiles run longest
+template <class Prob>
+void order_by_c_in(const Prob* probs, int n, int* order) {
+  for (int p = 0; p < n; ++p) order[p] = p;
+  for (int i = 1; i < n; ++i)
+    for (int j = i; j > 0 && probs[order[j]].C_in > probs[order[j - 1]].C_in; --j) std::swap(order[j], order[j - 1]);
+}
+
+// ---- dispatch rules: every threshold named once, every rule a function of the shape ------------------------------
+// fewest GEMM workgroups for which the pipelined tile kernels are used (tuned in round 2) ...
+constexpr int kPipeMinWgs = 96;
+// ... and for the data-gradient tiles inside the three-class merged backward (measured: pays from ~48 tiles up)
+constexpr int kPipeMinWgsMerged = kPipeMinWgs / 2;
+// Split-K tile choice.  Measured on MI355X: what costs time at batch 128 is the number of ROUNDS of workgroups a CU
+// has to run (each round pays launch + one memory round trip + the store drain, ~3 us), not MFMA or bytes.  So: the
+// largest output tile that still gives every CU a workgroup (>= 256), all of them resident at once.  Empirical
+// (MI355X, batch 128, K = 192 / 576): 2x2 tiles with at least this many workgroups 14.4 us, 1x1 tiles 14.6 us; fewer, fatter
+// workgroups were SLOWER (4x4: 22-26 us, 2x2 with 384 workgroups: 18-22 us) — more waves in flight beat operand reuse.
+constexpr int kKsplit2x2MinWgs = 1024;
+// operand + accumulator VGPRs a split-K wave may hold (all its loads are issued up front)
+constexpr int kKsplitVgprs = 232;
+// conv + attention forward: 64-column tiles only when they already give every CU two workgroups; else 32-column tiles
+// (MM-IMDB batch 128: 384 instead of 192 GEMM workgroups, 8 us per step faster; re-measured with the pipelined chunk
+// step: 64-column tiles 12.5-13.1 us against 11.2)
+constexpr int kSdpaWideMinWgs = 512;
+
+// "The pipelined data-gradient tiles (32 columns x kPipeBJ channels, 48-channel chunks) serve this problem": the shape
+// they cover, and at least min_wgs of them — the caller names the threshold of its launch.
+inline long pipe_bwd_tiles(int n_groups, int J) { return (long)((n_groups + 1) / 2) * ((J + kPipeBJ - 1) / kPipeBJ); }
+inline bool pipe_bwd_serves(int M, int J, int ldw, int fold, int n_groups, int min_wgs) {
+  return conv_pipe_mode() && fold == 0 && M % 48 == 0 && J % 16 == 0 && ldw % 4 == 0 &&
+         pipe_bwd_tiles(n_groups, J) >= min_wgs;
+}
+
+// n-groups per forward tile: 4 (64 columns) where that gives at least min64 workgroups, else 2 (32 columns, when 64
+// leave CUs idle: the reshape layers at batch 128, K = 512, ran at 14 % of the MFMA peak through the split-K kernel,
+// 18 us per layer); 0 where even those give fewer than kPipeMinWgs
+inline int pipe_fwd_ngv(int n_groups, int J, int min64) {
+  const int gy = (J + kPipeJ - 1) / kPipeJ;
+  if ((n_groups + 3) / 4 * gy >= min64) return 4;
+  return (n_groups + 1) / 2 * gy >= kPipeMinWgs ? 2 : 0;
+}
+
+// split-K: kpw 16-channel blocks per wave of a (16 TN) x (16 TJ) tile fit in registers (bn_fold: + the raw-output
+// registers of the BatchNorm fold), and the grid from which the 2x2 tiles are used
+inline bool ksplit_fits(int kpw, int tn, int tj, bool bn_fold = false) {
+  return kpw * 4 * (tn + tj + (bn_fold ? tn : 0)) + 4 * tn * tj <= kKsplitVgprs;
+}
+inline bool ksplit_2x2_grid(int n_groups, int J) {
+  return (long)((n_groups + 1) / 2) * ((J / 16 + 1) / 2) >= kKsplit2x2MinWgs;
+}
+
+// bmnas_conv1x1_bwd_all's one-launch form (conv_bwd_pair_k, the only one that can carry the mix epilogue): where
+// bmnas_conv1x1_bwd_data would take the 1x1-tile split-K kernel anyway (small grids: every launch there is at the
+// ~4.5 us floor, so two launches fewer is the whole gain)
+inline bool bwd_pair_serves(int M, int J, int ldw, int fold, int n_groups) {
+  const int kpw = (M / 16 + 3) / 4;
+  return !pipe_bwd_serves(M, J, ldw, fold, n_groups, kPipeMinWgs) && !ksplit_2x2_grid(n_groups, J) && kpw <= 4 &&
+         ksplit_fits(kpw, 1, 1, true);
 }
 
 }  // namespace
@@ -1740,7 +1870,8 @@ extern "C" int bmnas_conv1x1_num_partials(int b, int L) {
 }
 
 namespace {
-// wave tile = (16*TN) x (16*TJ); pick the largest tile that still gives >= ~1500 waves
+// ---- launchers ---------------------------------------------------------------------------------------------------
+// wave tile = (16*TN) x (16*TJ); false when the split-K kernels do not cover this shape
 template <bool TRANS, int TN, int TJ>
 bool launch_ksplit(const ConvArgs& a, hipStream_t st) {
   const int nblk = a.I / 16;
@@ -1754,7 +1885,7 @@ bool launch_ksplit(const ConvArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((conv_ksplit_multi_k<TRANS>), grid, dim3(256), 0, st, a);
     return true;
   }
-  if (kpw * 4 * (TN + TJ) + 4 * TN * TJ > 232) return false;       // operand + accumulator VGPRs
+  if (!ksplit_fits(kpw, TN, TJ)) return false;
 #define KS_CASE(K)                                                                                   \
   if (kpw <= K) {                                                                                    \
     BMNAS_COUNT(F_KSPLIT);                                                                           \
@@ -1772,7 +1903,7 @@ template <int TN, int TJ>
 bool launch_ksplit_sdpa_fwd(const ConvArgs& a, const SdpaFwdArgs& s, hipStream_t st) {
   const int kch = sdpa_kch(s.G.C);
   if (a.I != s.G.C || kch > 4) return false;                     // NodeMixedOp shape only
-  if (kch * 4 * (TN + TJ) + 4 * TN * TJ > 232) return false;
+  if (!ksplit_fits(kch, TN, TJ)) return false;
   const int gx = (a.n_groups + TN - 1) / TN, gy = (a.J / 16 + TJ - 1) / TJ;
   dim3 grid((unsigned)(s.groups + gx * gy));
 #define KS_CASE(K)                                                                                   \
@@ -1787,67 +1918,41 @@ bool launch_ksplit_sdpa_fwd(const ConvArgs& a, const SdpaFwdArgs& s, hipStream_t
   return false;
 }
 
-// fewest GEMM workgroups for which the tile kernels are used (tuned in round 2: 96; the data-gradient tiles pay
-// from half of that)
-inline int conv_pipe_min() { return 96; }
-
-inline int conv_pipe_mode() {        // BMNAS_CONV_PIPE=0 falls back to the split-K kernels (A/B runs)
-  static const int v = []() { const char* e = getenv("BMNAS_CONV_PIPE"); return e ? atoi(e) : 1; }();
-  return v;
+template <int KC, int NG>
+bool launch_pipe_fwd_tiles(const ConvArgs& a, int gx, int gy, hipStream_t st) {
+  BMNAS_COUNT(F_PIPE_FWD);
+  hipLaunchKernelGGL((conv_pipe_fwd_k<KC, NG>), dim3((unsigned)(gx * gy)), dim3(256), (conv_pipe_lds<KC, NG>(a.L)), st,
+                     a, gx);
+  return true;
 }
 
 // pipelined tile kernel (forward); false when the shape is not covered
 inline bool launch_pipe_fwd(const ConvArgs& a, hipStream_t st) {
   if (!conv_pipe_mode() || a.I != a.Ci || a.fold != 0 || a.acc_mask != 0 || a.ldw % 4) return false;
-  const int gy = (a.J + kPipeJ - 1) / kPipeJ;
-  int gx = (a.n_groups + 3) / 4;
-  if (gx * gy < 96) {
-    // 32-column tiles when 64-column ones leave CUs idle (reshape layers at batch 128: K = 512 through
-    // the split-K kernel ran at 14 % of the MFMA peak, 18 us per layer)
-    gx = (a.n_groups + 1) / 2;
-    if (gx * gy < 96 || a.I % 32 != 0) return false;
-    BMNAS_COUNT(F_PIPE_FWD);
-    hipLaunchKernelGGL((conv_pipe_fwd_k<32, 2>), dim3((unsigned)(gx * gy)), dim3(256), (conv_pipe_lds<32, 2>(a.L)), st, a, gx);
-    return true;
-  }
-  if (a.I % 48 == 0 && conv_pipe_lds<48, 4>(a.L) <= 65536) {     // (L = 4 pads rows to twice their size)
-    BMNAS_COUNT(F_PIPE_FWD);
-    hipLaunchKernelGGL((conv_pipe_fwd_k<48, 4>), dim3((unsigned)(gx * gy)), dim3(256), (conv_pipe_lds<48, 4>(a.L)), st, a, gx);
-    return true;
-  }
-  if (a.I % 32 == 0) {
-    BMNAS_COUNT(F_PIPE_FWD);
-    hipLaunchKernelGGL((conv_pipe_fwd_k<32, 4>), dim3((unsigned)(gx * gy)), dim3(256), (conv_pipe_lds<32, 4>(a.L)), st, a, gx);
-    return true;
-  }
-  return false;
+  const int ngv = pipe_fwd_ngv(a.n_groups, a.J, kPipeMinWgs);
+  if (ngv == 0) return false;
+  const int gx = (a.n_groups + ngv - 1) / ngv, gy = (a.J + kPipeJ - 1) / kPipeJ;
+  if (ngv == 2) return a.I % 32 == 0 && launch_pipe_fwd_tiles<32, 2>(a, gx, gy, st);
+  if (a.I % 48 == 0 && conv_pipe_lds<48, 4>(a.L) <= 65536)       // (L = 4 pads rows to twice their size)
+    return launch_pipe_fwd_tiles<48, 4>(a, gx, gy, st);
+  return a.I % 32 == 0 && launch_pipe_fwd_tiles<32, 4>(a, gx, gy, st);
+}
+
+// pipelined data-gradient tiles (pipe_bwd_serves), with the BatchNorm fold where a.bn_U asks for it
+inline void launch_pipe_bwd(const ConvArgs& a, hipStream_t st) {
+  const int gx = (a.n_groups + 1) / 2;
+  BMNAS_COUNT(F_PIPE_BWD);
+  hipLaunchKernelGGL((conv_pipe_bwd_k<48, 2>), dim3((unsigned)pipe_bwd_tiles(a.n_groups, a.J)), dim3(256),
+                     (conv_pipe_bwd_lds<48, 2>(a.L)) + bn_fold_lds(a), st, a, gx);
 }
 
 template <bool TRANS>
 void launch_gemm(const ConvArgs& a, hipStream_t st) {
   const long jt = a.J / 16, ng = a.n_groups;
   if (TRANS && launch_pipe_fwd(a, st)) return;
-  if (!TRANS && conv_pipe_mode() && a.I == a.Ci && a.fold == 0 && a.I % 48 == 0 && a.J % 16 == 0 && a.ldw % 4 == 0) {
-    const int gx = (a.n_groups + 1) / 2, gy = (a.J + kPipeBJ - 1) / kPipeBJ;
-    if (gx * gy >= 96) {
-      BMNAS_COUNT(F_PIPE_BWD);
-      hipLaunchKernelGGL((conv_pipe_bwd_k<48, 2>), dim3((unsigned)(gx * gy)), dim3(256),
-                         (conv_pipe_bwd_lds<48, 2>(a.L)), st, a, gx);
-      return;
-    }
-  }
-  {
-    // split-K kernel.  Measured on MI355X: what costs time at batch 128 is the number of
-    // ROUNDS of workgroups a CU has to run (each round pays launch + one memory round trip +
-    // the store drain, ~3 us), not MFMA or bytes.  So: the largest output tile that still
-    // gives every CU a workgroup (>= 256), all of them resident at once.
-    // Tile choice is empirical (MI355X, batch 128, K = 192 / 576): 2x2 tiles with >= 1024
-    // workgroups 14.4 us, 1x1 tiles 14.6 us; fewer, fatter workgroups were SLOWER (4x4: 22-26 us,
-    // 2x2 with 384 workgroups: 18-22 us) — more waves in flight beat operand reuse here.
-    auto wgs = [&](long tn, long tj) { return ((ng + tn - 1) / tn) * ((jt + tj - 1) / tj); };
-    if (wgs(2, 2) >= 1024 && launch_ksplit<TRANS, 2, 2>(a, st)) return;
-    if (launch_ksplit<TRANS, 1, 1>(a, st)) return;
-  }
+  if (!TRANS && pipe_bwd_serves(a.I, a.J, a.ldw, a.fold, a.n_groups, kPipeMinWgs)) return launch_pipe_bwd(a, st);
+  if (ksplit_2x2_grid(a.n_groups, a.J) && launch_ksplit<TRANS, 2, 2>(a, st)) return;
+  if (launch_ksplit<TRANS, 1, 1>(a, st)) return;
   {
     // generic fallback: whole-K LDS-staged tiles.  No shape of the reference's configurations lands here (the
     // pipelined tile kernels take the large grids, the split-K kernels the small ones); what does: channel
@@ -1869,26 +1974,14 @@ void launch_gemm(const ConvArgs& a, hipStream_t st) {
 }
 }  // namespace
 
-extern "C" int bmnas_conv1x1_fwd(const float* const* srcs, int n_src, int C_src, const float* W,
-                                 int ldw, int fold_cols, const float* bias, float* U, float* part,
-                                 int stat_shards, int b, int L, int M, void* stream) {
-  if (!srcs || !W || !U || n_src < 1 || C_src < 1 || b < 0 || M < 1 || fold_cols < 0 || stat_shards < 0)
-    return BMNAS_E_ARG;
-  if (fold_cols % 4 || (fold_cols > 0 && ldw < n_src * C_src + fold_cols)) return BMNAS_E_SHAPE;
-  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
-  if (C_src % 16 || M % 16 || ldw % 4 || ldw < n_src * C_src) return BMNAS_E_SHAPE;
+extern "C" int bmnas_conv1x1_fwd(const float* const* srcs, int n_src, int C_src, const float* W, int ldw,
+                                 int fold_cols, const float* bias, float* U, float* part, int stat_shards, int b,
+                                 int L, int M, void* stream) {
+  if (int e = conv_check(srcs && W && U && stat_shards >= 0, n_src, C_src, b, M, ldw, fold_cols, true)) return e;
   ConvArgs a{};
-  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  if (int e = conv_fwd_args(a, srcs, n_src, C_src, W, ldw, fold_cols, bias, U, part, stat_shards, b, L, M)) return e;
   if (b == 0) return 0;
-  for (int q = 0; q < n_src; ++q) {
-    if (!srcs[q]) return BMNAS_E_ARG;
-    a.act.p[q] = srcs[q];
-  }
-  a.dst.p[0] = U;
-  a.W = W; a.bias = bias; a.ldw = ldw;
-  a.part = stat_shards ? nullptr : part; a.stat = stat_shards ? part : nullptr; a.stat_shards = stat_shards;
-  a.Ci = C_src; a.I = n_src * C_src; a.Cj = M; a.J = M;
-  a.b = b; a.L = L; a.acc_mask = 0; a.n_part = a.n_groups; a.probe = conv_probe(); a.fold = fold_cols;
+  if (null_src(a.act, n_src)) return BMNAS_E_ARG;
   launch_gemm<true>(a, (hipStream_t)stream);
   BMNAS_CHECK_LAUNCH();
   return 0;
@@ -1897,18 +1990,10 @@ extern "C" int bmnas_conv1x1_fwd(const float* const* srcs, int n_src, int C_src,
 extern "C" int bmnas_conv1x1_bwd_data(const float* dU, const float* W, int ldw, int fold_cols,
                                       float* const* dsrcs, int n_src, int C_src,
                                       uint32_t accumulate_mask, int b, int L, int M, void* stream) {
-  if (!dU || !W || !dsrcs || n_src < 1 || C_src < 1 || b < 0 || M < 1 || fold_cols < 0) return BMNAS_E_ARG;
-  if (fold_cols % 4 || (fold_cols > 0 && ldw < n_src * C_src + fold_cols)) return BMNAS_E_SHAPE;
-  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
-  if (C_src % 16 || M % 16 || ldw < n_src * C_src) return BMNAS_E_SHAPE;
+  if (int e = conv_check(dU && W && dsrcs, n_src, C_src, b, M, ldw, fold_cols, false)) return e;
   ConvArgs a{};
-  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  if (int e = conv_bwd_args(a, dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b, L, M)) return e;
   if (b == 0) return 0;
-  a.act.p[0] = dU;
-  for (int q = 0; q < n_src; ++q) a.dst.p[q] = dsrcs[q];
-  a.W = W; a.bias = nullptr; a.part = nullptr; a.ldw = ldw;
-  a.Ci = M; a.I = M; a.Cj = C_src; a.J = n_src * C_src;
-  a.b = b; a.L = L; a.acc_mask = accumulate_mask; a.probe = conv_probe(); a.fold = fold_cols;
   launch_gemm<false>(a, (hipStream_t)stream);
   BMNAS_CHECK_LAUNCH();
   return 0;
@@ -1919,41 +2004,26 @@ extern "C" int bmnas_conv1x1_fwd_sdpa(const float* const* srcs, int n_src, int C
                                       int stat_shards, int b, int L, int M, const float* x, const float* y,
                                       const float* ln_w, const float* ln_b, float* out, float* xhat,
                                       float* stats, int C, bmnas_dropout_t drop, void* stream) {
-  if (!srcs || !W || !U || n_src < 1 || C_src < 1 || b < 0 || M < 1 || fold_cols < 0) return BMNAS_E_ARG;
-  if (!x || !y || !ln_w || !ln_b || !out || !xhat || !stats) return BMNAS_E_ARG;
-  if (fold_cols % 4 || (fold_cols > 0 && ldw < n_src * C_src + fold_cols)) return BMNAS_E_SHAPE;
-  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
-  if (C_src % 16 || M % 16 || ldw % 4 || ldw < n_src * C_src) return BMNAS_E_SHAPE;
+  // (a negative stat_shards is NOT refused here, unlike in bmnas_conv1x1_fwd: it reads as "sharded")
+  if (int e = conv_check(srcs && W && U && x && y && ln_w && ln_b && out && xhat && stats, n_src, C_src, b, M, ldw,
+                         fold_cols, true))
+    return e;
   ConvArgs a{};
-  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  if (int e = conv_fwd_args(a, srcs, n_src, C_src, W, ldw, fold_cols, bias, U, part, stat_shards, b, L, M)) return e;
   SdpaFwdArgs s{};
   if (int e = geom(b, C, L, &s.G)) return e;
   if (b == 0) return 0;
-  for (int q = 0; q < n_src; ++q) {
-    if (!srcs[q]) return BMNAS_E_ARG;
-    a.act.p[q] = srcs[q];
-  }
-  a.dst.p[0] = U;
-  a.W = W; a.bias = bias; a.ldw = ldw;
-  a.part = stat_shards ? nullptr : part; a.stat = stat_shards ? part : nullptr; a.stat_shards = stat_shards;
-  a.Ci = C_src; a.I = n_src * C_src; a.Cj = M; a.J = M;
-  a.b = b; a.L = L; a.acc_mask = 0; a.n_part = a.n_groups; a.probe = conv_probe(); a.fold = fold_cols;
+  if (null_src(a.act, n_src)) return BMNAS_E_ARG;
   s.x = x; s.y = y; s.ln_w = ln_w; s.ln_b = ln_b; s.out = out; s.xhat = xhat; s.stats = stats;
   s.drop = to_cfg(drop);
   s.groups = (b + s.G.spw - 1) / s.G.spw;
   hipStream_t st = (hipStream_t)stream;
-  const long jt = a.J / 16, ng = a.n_groups;
+  const int kch = sdpa_kch(C);
+  const int ngv = pipe_fwd_ngv(a.n_groups, a.J, kSdpaWideMinWgs);
   bool done = false;
-  {
-    const int kch = sdpa_kch(C);
-    // 64-column tiles only when they already give every CU two workgroups; else 32-column tiles
-    // (MM-IMDB batch 128: 384 instead of 192 GEMM workgroups, 8 us per step faster)
-    const int gy = (a.J + kPipeJ - 1) / kPipeJ;
-    // (re-measured with the pipelined chunk step, MM-IMDB b128: 64-column tiles 12.5-13.1 us against 11.2)
-    const int ngv = (a.n_groups + 3) / 4 * gy >= 512 ? 4 : 2;
-    const int gx = (a.n_groups + ngv - 1) / ngv;
-    if (conv_pipe_mode() && a.I == C && a.fold == 0 && a.ldw % 4 == 0 && gx * gy >= conv_pipe_min() && kch <= 4) {
-      dim3 grid((unsigned)(s.groups + gx * gy));
+  if (ngv != 0 && conv_pipe_mode() && a.I == C && a.fold == 0 && a.ldw % 4 == 0 && kch <= 4) {
+    const int gx = (a.n_groups + ngv - 1) / ngv, gy = (a.J + kPipeJ - 1) / kPipeJ;
+    dim3 grid((unsigned)(s.groups + gx * gy));
 #define PF_CASE(KCv, K)                                                                                \
   if (!done && a.I % KCv == 0 && kch == K &&                                                           \
       (ngv == 2 ? conv_pipe_lds<KCv, 2>(a.L) : conv_pipe_lds<KCv, 4>(a.L)) <= 65536) {                 \
@@ -1966,15 +2036,14 @@ extern "C" int bmnas_conv1x1_fwd_sdpa(const float* const* srcs, int n_src, int C
                          std::max((size_t)kSdpaFwdLds, (conv_pipe_lds<KCv, 4>(a.L))), st, a, s, gx);        \
     done = true;                                                                                       \
   }
-      // 32-channel chunks first: 38 KB of LDS instead of 55 KB keeps four workgroups on a CU
-      // (measured 2.6 us per step faster than 48-channel chunks at K = 192; the data-gradient body
-      // showed no such preference and stays at 48)
-      PF_CASE(32, 1) PF_CASE(32, 2) PF_CASE(32, 3) PF_CASE(32, 4)
-      PF_CASE(48, 1) PF_CASE(48, 2) PF_CASE(48, 3) PF_CASE(48, 4)
+    // 32-channel chunks first: 38 KB of LDS instead of 55 KB keeps four workgroups on a CU
+    // (measured 2.6 us per step faster than 48-channel chunks at K = 192; the data-gradient body
+    // showed no such preference and stays at 48)
+    PF_CASE(32, 1) PF_CASE(32, 2) PF_CASE(32, 3) PF_CASE(32, 4)
+    PF_CASE(48, 1) PF_CASE(48, 2) PF_CASE(48, 3) PF_CASE(48, 4)
 #undef PF_CASE
-    }
   }
-  if (!done && ((ng + 1) / 2) * ((jt + 1) / 2) >= 1024) done = launch_ksplit_sdpa_fwd<2, 2>(a, s, st);
+  if (!done && ksplit_2x2_grid(a.n_groups, a.J)) done = launch_ksplit_sdpa_fwd<2, 2>(a, s, st);
   if (!done) done = launch_ksplit_sdpa_fwd<1, 1>(a, s, st);
   if (!done) {
     launch_gemm<true>(a, st);
@@ -1987,33 +2056,41 @@ extern "C" int bmnas_conv1x1_fwd_sdpa(const float* const* srcs, int n_src, int C
 
 namespace {
 int g_conv_deterministic = 0;       // bmnas_conv1x1_set_deterministic
-// fill the weight-gradient arguments; waves = waves per workgroup of the kernel that will run them
-int fill_w_args(ConvWArgs& a, const float* dU, const float* const* srcs, int n_src, int C_src, float* dW,
-                int ldw, float* dbias, int dup_cols, int b, int L, int M, int waves, dim3* grid) {
-  if (!dU || !srcs || !dW || n_src < 1 || C_src < 1 || b < 0 || M < 1 || dup_cols < 0)
-    return BMNAS_E_ARG;
-  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
-  if (C_src % 16 || M % 16 || ldw < n_src * C_src + dup_cols) return BMNAS_E_SHAPE;
-  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
-  for (int q = 0; q < n_src; ++q) {
-    if (!srcs[q]) return BMNAS_E_ARG;
-    a.src.p[q] = srcs[q];
-  }
-  a.dU = dU; a.dW = dW; a.dbias = dbias; a.ldw = ldw; a.C_src = C_src; a.M = M;
-  a.K = n_src * C_src; a.dup_cols = dup_cols; a.b = b; a.L = L;
-  const int tiles = ((M + 31) / 32) * ((a.K + 31) / 32);
-  // splits of the batch: as many as keep the grid at <= ~256 eight-wave workgroups (measured at
-  // 108 tiles: 2 splits 9.1 us, 3: 10.9, 4: 9.8, 1: 16.8 — every extra split is another round of
-  // fp32 atomics on dW), at most 8 n-groups per wave per split, never fewer than one
-  int splits = (256 * 8 / waves) / tiles;
-  const int max_splits = (a.n_groups + 7) / 8;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1 || g_conv_deterministic) splits = 1;           // deterministic mode: one walk over the batch, no atomics
+
+// Splits of the batch for a weight gradient that has the chip to itself: as many as keep the grid at <= ~256
+// eight-wave workgroups (measured at 108 tiles: 2 splits 9.1 us, 3: 10.9, 4: 9.8, 1: 16.8 — every extra split is
+// another round of fp32 atomics on dW).  waves = waves per workgroup of the kernel that will run the tiles.
+inline int conv_w_splits(const dim3& tiles, int waves) { return (256 * 8 / waves) / (int)(tiles.x * tiles.y); }
+
+// Give the weight-gradient tiles `wanted` splits of the batch: at most 8 n-groups per wave per split, never fewer
+// than one; deterministic mode: one walk over the batch, no atomics.  Returns the splits actually used (grid.z).
+inline unsigned set_w_splits(ConvWArgs& a, int wanted) {
+  int splits = std::min(wanted, (a.n_groups + 7) / 8);
+  if (splits < 1 || g_conv_deterministic) splits = 1;
   a.groups_per_split = (a.n_groups + splits - 1) / splits;
   splits = (a.n_groups + a.groups_per_split - 1) / a.groups_per_split;
   a.use_atomic = splits > 1;
-  *grid = dim3((M + 31) / 32, (a.K + 31) / 32, splits);
+  return (unsigned)splits;
+}
+
+// check and fill the weight-gradient arguments; waves = waves per workgroup of the kernel that will run them
+int fill_w_args(ConvWArgs& a, const float* dU, const float* const* srcs, int n_src, int C_src, float* dW,
+                int ldw, float* dbias, int dup_cols, int b, int L, int M, int waves, dim3* grid) {
+  // (no weight fold here; the dup_cols columns must fit in a row behind the n_src * C_src that conv_check knows)
+  if (int e = conv_check(dU && srcs && dW && dup_cols >= 0, n_src, C_src, b, M, ldw - dup_cols, 0, false)) return e;
+  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  for (int q = 0; q < n_src; ++q) a.src.p[q] = srcs[q];
+  if (null_src(a.src, n_src)) return BMNAS_E_ARG;
+  a.dU = dU; a.dW = dW; a.dbias = dbias; a.ldw = ldw; a.C_src = C_src; a.M = M;
+  a.K = n_src * C_src; a.dup_cols = dup_cols; a.b = b; a.L = L;
+  *grid = dim3((M + 31) / 32, (a.K + 31) / 32, 1);
+  grid->z = set_w_splits(a, conv_w_splits(*grid, waves));
   return 0;
+}
+
+inline void launch_conv_w(const ConvWArgs& w, const dim3& grid, hipStream_t st) {
+  BMNAS_COUNT(F_CONV_W);
+  hipLaunchKernelGGL(conv_w_k, grid, dim3(512), 0, st, w);
 }
 }  // namespace
 
@@ -2024,14 +2101,10 @@ extern "C" int bmnas_conv1x1_bwd_weight(const float* dU, const float* const* src
   dim3 grid;
   if (int e = fill_w_args(a, dU, srcs, n_src, C_src, dW, ldw, dbias, dup_cols, b, L, M, 8, &grid)) return e;
   if (b == 0) return 0;
-  BMNAS_COUNT(F_CONV_W);
-  hipLaunchKernelGGL(conv_w_k, grid, dim3(512), 0, (hipStream_t)stream, a);
+  launch_conv_w(a, grid, (hipStream_t)stream);
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
-
-extern "C" int bmnas_bn_bwd_apply(float* dV, const float* U, const float* chan, const float* bn_grad, int b,
-                                  int M, int L, int training, void* stream);
 
 extern "C" int bmnas_conv1x1_bwd_all_sdpa(const float* dU, const float* W, int ldw, int fold_cols,
                                           float* const* dsrcs, int n_src, int C_src,
@@ -2043,12 +2116,10 @@ extern "C" int bmnas_conv1x1_bwd_all_sdpa(const float* dU, const float* W, int l
                                           float* dx, float* dy, uint32_t sdpa_accumulate_mask, int C,
                                           bmnas_dropout_t drop, const float* bn_U, const float* bn_chan,
                                           const float* bn_grad, int bn_training, void* stream) {
-  if (bn_U != nullptr && (!bn_chan || (bn_training && !bn_grad))) return BMNAS_E_ARG;
-  if (!dU || !W || !dsrcs || n_src < 1 || C_src < 1 || b < 0 || M < 1 || fold_cols < 0) return BMNAS_E_ARG;
-  if (!g || !x || !y || !ln_w || !xhat || !stats || !dx) return BMNAS_E_ARG;
-  if (fold_cols % 4 || (fold_cols > 0 && ldw < n_src * C_src + fold_cols)) return BMNAS_E_SHAPE;
-  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
-  if (C_src % 16 || M % 16 || ldw < n_src * C_src) return BMNAS_E_SHAPE;
+  if (int e = conv_check(bn_fold_ok(bn_U, bn_chan, bn_grad, bn_training) && dU && W && dsrcs && g && x && y && ln_w &&
+                             xhat && stats && dx,
+                         n_src, C_src, b, M, ldw, fold_cols, false))
+    return e;
   for (int q = 0; q < n_src; ++q)
     if (dsrcs[q] == dx || (dy && dsrcs[q] == dy)) return BMNAS_E_ARG;
   ConvWArgs w{};
@@ -2060,86 +2131,61 @@ extern "C" int bmnas_conv1x1_bwd_all_sdpa(const float* dU, const float* W, int l
       return e;
   }
   ConvArgs a{};
-  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  if (int e = conv_bwd_args(a, dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b, L, M)) return e;
   SdpaBwdArgs s{};
   if (int e = geom(b, C, L, &s.G)) return e;
   if (b == 0) return 0;
-  a.act.p[0] = dU;
-  for (int q = 0; q < n_src; ++q) a.dst.p[q] = dsrcs[q];
-  a.W = W; a.bias = nullptr; a.part = nullptr; a.ldw = ldw;
-  a.Ci = M; a.I = M; a.Cj = C_src; a.J = n_src * C_src;
-  a.b = b; a.L = L; a.acc_mask = accumulate_mask; a.probe = conv_probe(); a.fold = fold_cols;
   s.g = g; s.gscale = gscale; s.x = x; s.y = y; s.ln_w = ln_w; s.xhat = xhat; s.stats = stats;
   s.dx = dx; s.dy = dy; s.acc_mask = sdpa_accumulate_mask; s.drop = to_cfg(drop);
   s.groups = (b + s.G.spw - 1) / s.G.spw;
   hipStream_t st = (hipStream_t)stream;
+  // Which launch: the pipelined data-gradient tiles (32 x 64; 16 x 64 measured slower: +4 us per step), the split-K
+  // tiles (small grids, NodeMixedOp shape only; 3 kch blocks per wave), or neither: three launches
   const int kch = sdpa_kch(C);
-  bool done = false;
-  const int gy = (a.J + kPipeBJ - 1) / kPipeBJ;
-  const int ngv = 2;                                  // 32 x 64 data-gradient tiles (16 x 64 measured slower: +4 us per step)
-  const int gx = (a.n_groups + ngv - 1) / ngv;
-  const bool pipe_ok = conv_pipe_mode() && a.I % 48 == 0 && a.fold == 0 && a.ldw % 4 == 0 && a.J % 16 == 0 &&
-                       kch <= 4 && gx * gy >= conv_pipe_min() / 2;   // measured: pays from ~48 data-gradient tiles up
-  // the split-K merged kernel (small grids): same conditions as its branch below
-  const long jt_ = a.J / 16, ng_ = a.n_groups;
-  const bool ks_big = ((ng_ + 1) / 2) * ((jt_ + 1) / 2) >= 1024 && 3 * kch * 16 + 16 <= 232;
-  const int ks_tn = ks_big ? 2 : 1;
-  const bool ks_ok = !pipe_ok && a.I == 3 * C && C % 64 == 0 && kch <= 4 &&
-                     3 * kch * 4 * (2 * ks_tn) + 4 * ks_tn * ks_tn <= 232 &&
-                     3 * kch * 4 * (3 * ks_tn) + 4 * ks_tn * ks_tn <= 232;   // (+ the raw-output registers of the fold)
+  const bool pipe = kch <= 4 && pipe_bwd_serves(a.I, a.J, a.ldw, a.fold, a.n_groups, kPipeMinWgsMerged);
+  const int tn = ksplit_2x2_grid(a.n_groups, a.J) && ksplit_fits(3 * kch, 2, 2) ? 2 : 1;
+  const bool ksplit = !pipe && a.I == 3 * C && C % 64 == 0 && kch <= 4 && ksplit_fits(3 * kch, tn, tn);
   if (bn_U != nullptr) {
-    if (pipe_ok || ks_ok) {                         // the GEMM kernels apply the BatchNorm backward on the fly
-      a.bn_U = w.bn_U = bn_U; a.bn_chan = w.bn_chan = bn_chan; a.bn_grad = w.bn_grad = bn_grad;
-      a.bn_train = w.bn_train = bn_training;
+    if (pipe || (ksplit && ksplit_fits(3 * kch, tn, tn, true))) {   // the GEMM kernels apply the BatchNorm backward on the fly
+      set_bn_fold(&a, &w, bn_U, bn_chan, bn_grad, bn_training);
     } else {                                        // other kernel families: as its own launch, in place
       if (int e = bmnas_bn_bwd_apply(const_cast<float*>(dU), bn_U, bn_chan, bn_grad, b, M, L, bn_training, stream))
         return e;
     }
   }
-  if (pipe_ok) {
-    {
-      const int n_w = (int)(wgrid.x * wgrid.y * wgrid.z);
-      static const int order = [] { const char* e = getenv("BMNAS_BWD_ORDER"); return e ? atoi(e) : 2; }();
-      a.order = order;
-      dim3 grid((unsigned)(s.groups + n_w + gx * gy));
-      const size_t lds = std::max(std::max(sdpa_bwd_lds(C), conv_w_lds<4>()),
-                                  (conv_pipe_bwd_lds<48, 2>(a.L)) + (a.bn_U ? (size_t)a.I * sizeof(float4) : 0));
+  const int n_w = (int)(wgrid.x * wgrid.y * wgrid.z);
+  if (pipe) {
+    const int gx = (a.n_groups + 1) / 2;
+    a.order = 2;                                    // D W A: the table in profiles/r04_bwd_block_order.txt (see the kernel)
+    dim3 grid((unsigned)(s.groups + n_w + pipe_bwd_tiles(a.n_groups, a.J)));
+    const size_t lds = std::max(std::max(sdpa_bwd_lds(C), conv_w_lds<4>()),
+                                (conv_pipe_bwd_lds<48, 2>(a.L)) + bn_fold_lds(a));
     // negative wx = XCD-aware weight-gradient tile order (see the kernel)
     const int wxa = (wgrid.z == 4 && wgrid.x % 2 == 0) ? -(int)wgrid.x : (int)wgrid.x;
+    BMNAS_COUNT(F_BWD_ALL_PIPE);
 #define PB_CASE(K)                                                                                     \
-  if (!done && kch == K) {                                                                             \
-    BMNAS_COUNT(F_BWD_ALL_PIPE);                                                                       \
+  case K:                                                                                              \
     hipLaunchKernelGGL((conv_bwd_all_pipe_k<48, K, 2>), grid, dim3(256), lds, st, a, s, w, gx, n_w,    \
                        wxa, (int)wgrid.y);                                                             \
-    done = true;                                                                                       \
-  }
-      PB_CASE(1) PB_CASE(2) PB_CASE(3) PB_CASE(4)
+    break;
+    switch (kch) { PB_CASE(1) PB_CASE(2) PB_CASE(3) PB_CASE(4) }
 #undef PB_CASE
-    }
-  }
-  if (!done && a.I == 3 * C && C % 64 == 0 && kch <= 4) {
-    const long jt = a.J / 16, ng = a.n_groups;
-    const bool big = ((ng + 1) / 2) * ((jt + 1) / 2) >= 1024 && 3 * kch * 16 + 16 <= 232;
-    const int TNv = big ? 2 : 1;
-    if (3 * kch * 4 * (2 * TNv) + 4 * TNv * TNv <= 232) {
-      const int gx = (a.n_groups + TNv - 1) / TNv, gy = (a.J / 16 + TNv - 1) / TNv;
-      const int n_data = gx * gy, n_w = (int)(wgrid.x * wgrid.y * wgrid.z);
-      dim3 grid((unsigned)(s.groups + n_data + n_w));
-      const size_t lds = std::max(std::max(sdpa_bwd_lds(C), conv_w_lds<4>()),
-                                  conv_ksplit_lds<2, 2>() + (a.bn_U ? (size_t)a.I * sizeof(float4) : 0));
+  } else if (ksplit) {
+    const int gx = (a.n_groups + tn - 1) / tn, gy = (a.J / 16 + tn - 1) / tn;
+    dim3 grid((unsigned)(s.groups + gx * gy + n_w));
+    const size_t lds = std::max(std::max(sdpa_bwd_lds(C), conv_w_lds<4>()), conv_ksplit_lds<2, 2>() + bn_fold_lds(a));
+    BMNAS_COUNT(F_BWD_ALL_KSPLIT);
 #define ALL_CASE(T, K)                                                                                 \
-  if (!done && TNv == T && kch == K) {                                                                 \
-    BMNAS_COUNT(F_BWD_ALL_KSPLIT);                                                                     \
+  case 4 * T + K:                                                                                      \
     hipLaunchKernelGGL((conv_bwd_all_k<T, T, K>), grid, dim3(256), lds, st, a, s, w, gx, n_w,          \
                        (int)wgrid.x, (int)wgrid.y);                                                    \
-    done = true;                                                                                       \
-  }
+    break;
+    switch (4 * tn + kch) {
       ALL_CASE(1, 1) ALL_CASE(1, 2) ALL_CASE(1, 3) ALL_CASE(1, 4)
       ALL_CASE(2, 1) ALL_CASE(2, 2) ALL_CASE(2, 3) ALL_CASE(2, 4)
-#undef ALL_CASE
     }
-  }
-  if (!done) {                                       // shape outside the merged kernels: three launches
+#undef ALL_CASE
+  } else {                                           // shape outside the merged kernels: three launches
     if (int e = bmnas_conv1x1_bwd_data(dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b, L, M,
                                        stream))
       return e;
@@ -2153,28 +2199,16 @@ extern "C" int bmnas_conv1x1_bwd_all_sdpa(const float* dU, const float* W, int l
   return 0;
 }
 
-namespace {
-// the grid rule of bmnas_conv1x1_bwd_all's one-launch form (the only one that can carry the mix epilogue)
-inline bool bwd_all_merged(int b, int L, int M, int J) {
-  int Lb, spw, ng;
-  if (check_shape(b, L, &Lb, &spw, &ng)) return false;
-  const long jt = J / 16;
-  const int kpw = (M / 16 + 3) / 4;
-  const bool pipe = conv_pipe_mode() && M % 48 == 0 && (((long)ng + 1) / 2) * ((J + kPipeBJ - 1) / kPipeBJ) >= 96;
-  return !pipe && (((long)ng + 1) / 2) * ((jt + 1) / 2) < 1024 && kpw <= 4 && kpw * 4 * 3 + 4 <= 232;
-}
-}  // namespace
-
+// The query has no ldw or fold argument: it answers for an aligned ldw and no weight fold.  With the mix epilogue
+// fold_cols must be 0 anyway, and bmnas_conv1x1_bwd_all_mix asks this same query before it looks at its own ldw.  What
+// is left is one-way: at ldw % 4 != 0 the launch never takes the pipelined tiles, so it can run the one-launch form
+// where the query said no — the caller then merely did not ask for the epilogue; the query never says yes where the
+// launch would refuse.
 extern "C" int bmnas_conv1x1_bwd_all_mix_ok(int b, int L, int M, int n_src, int C_src) {
-  return b >= 1 && n_src >= 1 && C_src % 16 == 0 && M % 16 == 0 && bwd_all_merged(b, L, M, n_src * C_src);
+  int Lb, spw, ng;
+  return b >= 1 && n_src >= 1 && C_src % 16 == 0 && M % 16 == 0 && check_shape(b, L, &Lb, &spw, &ng) == 0 &&
+         bwd_pair_serves(M, n_src * C_src, 0, 0, ng);
 }
-
-extern "C" int bmnas_conv1x1_bwd_all_mix(const float* dU, const float* W, int ldw, int fold_cols,
-                                         float* const* dsrcs, int n_src, int C_src, uint32_t accumulate_mask,
-                                         int b, int L, int M, const float* const* wsrcs, float* dW,
-                                         int ldw_grad, float* dbias, int dup_cols, const float* bn_U,
-                                         const float* bn_chan, const float* bn_grad, int bn_training,
-                                         const bmnas_mix_ep_t* mix, void* stream);
 
 extern "C" int bmnas_conv1x1_bwd_all(const float* dU, const float* W, int ldw, int fold_cols,
                                      float* const* dsrcs, int n_src, int C_src, uint32_t accumulate_mask,
@@ -2192,7 +2226,7 @@ extern "C" int bmnas_conv1x1_bwd_all_mix(const float* dU, const float* W, int ld
                                          int ldw_grad, float* dbias, int dup_cols, const float* bn_U,
                                          const float* bn_chan, const float* bn_grad, int bn_training,
                                          const bmnas_mix_ep_t* mix, void* stream) {
-  if (bn_U != nullptr && (!bn_chan || (bn_training && !bn_grad))) return BMNAS_E_ARG;
+  if (!bn_fold_ok(bn_U, bn_chan, bn_grad, bn_training)) return BMNAS_E_ARG;
   MixEp me{};
   if (mix != nullptr) {
     if (!mix->U || !mix->chan || !mix->x || !mix->p1 || !mix->gamma || !mix->dx || !mix->dV || !mix->bn_grad ||
@@ -2204,31 +2238,17 @@ extern "C" int bmnas_conv1x1_bwd_all_mix(const float* dU, const float* W, int ld
     me.dg_stride = mix->dgamma_shard_stride; me.dg_shards = mix->dgamma_shards; me.acc_dx = mix->accumulate_dx;
     me.q = mix->q; me.on = 1; me.dglu = to_cfg(mix->drop_glu); me.dfc = to_cfg(mix->drop_fc);
   }
-  if (!dU || !W || !dsrcs || n_src < 1 || C_src < 1 || b < 0 || M < 1 || fold_cols < 0) return BMNAS_E_ARG;
-  if (fold_cols % 4 || (fold_cols > 0 && ldw < n_src * C_src + fold_cols)) return BMNAS_E_SHAPE;
-  if (n_src > kConvPtrs) return BMNAS_E_LIMIT;
-  if (C_src % 16 || M % 16 || ldw < n_src * C_src) return BMNAS_E_SHAPE;
+  if (int e = conv_check(dU && W && dsrcs, n_src, C_src, b, M, ldw, fold_cols, false)) return e;
   ConvWArgs w{};
   dim3 wgrid;
   if (int e = fill_w_args(w, dU, wsrcs, n_src, C_src, dW, ldw_grad, dbias, dup_cols, b, L, M, 4, &wgrid))
     return e;
   ConvArgs a{};
-  if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+  if (int e = conv_bwd_args(a, dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b, L, M)) return e;
   if (b == 0) return 0;
-  a.act.p[0] = dU;
-  for (int q = 0; q < n_src; ++q) a.dst.p[q] = dsrcs[q];
-  a.W = W; a.bias = nullptr; a.part = nullptr; a.ldw = ldw;
-  a.Ci = M; a.I = M; a.Cj = C_src; a.J = n_src * C_src;
-  a.b = b; a.L = L; a.acc_mask = accumulate_mask; a.probe = conv_probe(); a.fold = fold_cols;
   hipStream_t st = (hipStream_t)stream;
-  // merged where bmnas_conv1x1_bwd_data would take the 1x1-tile split-K kernel anyway (small grids:
-  // every launch there is at the ~4.5 us floor, so two launches fewer is the whole gain)
-  const long jt = a.J / 16, ng = a.n_groups;
-  const int kpw = (a.I / 16 + 3) / 4;
-  const bool pipe = conv_pipe_mode() && a.fold == 0 && a.I % 48 == 0 && a.ldw % 4 == 0 &&
-                    ((ng + 1) / 2) * ((a.J + kPipeBJ - 1) / kPipeBJ) >= 96;
-  const bool merged = !pipe && ((ng + 1) / 2) * ((jt + 1) / 2) < 1024 && kpw <= 4 &&
-                      kpw * 4 * 3 + 4 <= 232;
+  const bool pipe = pipe_bwd_serves(a.I, a.J, a.ldw, a.fold, a.n_groups, kPipeMinWgs);
+  const bool merged = bwd_pair_serves(a.I, a.J, a.ldw, a.fold, a.n_groups);
   bool want_data = false;
   for (int q = 0; q < n_src; ++q) want_data = want_data || dsrcs[q] != nullptr;
   if (mix != nullptr && !(merged && want_data)) return BMNAS_E_LIMIT;     // (host-checked by the caller: _mix_ok)
@@ -2237,42 +2257,28 @@ extern "C" int bmnas_conv1x1_bwd_all_mix(const float* dU, const float* W, int ld
     // BatchNorm input gradient while staging their operands, so only the other data-gradient families
     // (whole-K LDS / direct kernels of the K = 2048 reshape layers) need the in-place launch first
     const bool fold_here = bn_U != nullptr && (pipe || !want_data);
+    if (fold_here) set_bn_fold(&a, &w, bn_U, bn_chan, bn_grad, bn_training);
     if (bn_U != nullptr && !fold_here)
       if (int e = bmnas_bn_bwd_apply(const_cast<float*>(dU), bn_U, bn_chan, bn_grad, b, M, L, bn_training, stream))
         return e;
-    if (want_data) {
-      if (fold_here) {
-        a.bn_U = bn_U; a.bn_chan = bn_chan; a.bn_grad = bn_grad; a.bn_train = bn_training;
-        const int pgx = (a.n_groups + 1) / 2, pgy = (a.J + kPipeBJ - 1) / kPipeBJ;
-        BMNAS_COUNT(F_PIPE_BWD);
-        hipLaunchKernelGGL((conv_pipe_bwd_k<48, 2>), dim3((unsigned)(pgx * pgy)), dim3(256),
-                           (conv_pipe_bwd_lds<48, 2>(a.L)) + (size_t)a.I * sizeof(float4), st, a, pgx);
-        BMNAS_CHECK_LAUNCH();
-      } else if (int e = bmnas_conv1x1_bwd_data(dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b,
-                                                L, M, stream)) {
+    if (want_data && pipe) {
+      launch_pipe_bwd(a, st);
+      BMNAS_CHECK_LAUNCH();
+    } else if (want_data) {
+      if (int e = bmnas_conv1x1_bwd_data(dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b, L, M, stream))
         return e;
-      }
     }
-    ConvWArgs w8{};
-    dim3 grid8;
-    if (int e = fill_w_args(w8, dU, wsrcs, n_src, C_src, dW, ldw_grad, dbias, dup_cols, b, L, M, 8, &grid8))
-      return e;
-    if (fold_here) {
-      w8.bn_U = bn_U; w8.bn_chan = bn_chan; w8.bn_grad = bn_grad; w8.bn_train = bn_training;
-    }
-    BMNAS_COUNT(F_CONV_W);
-    hipLaunchKernelGGL(conv_w_k, grid8, dim3(512), 0, st, w8);
+    wgrid.z = set_w_splits(w, conv_w_splits(wgrid, 8));       // conv_w_k alone: eight-wave workgroups
+    launch_conv_w(w, wgrid, st);
     BMNAS_CHECK_LAUNCH();
     return 0;
   }
-  if (bn_U != nullptr) {
-    a.bn_U = w.bn_U = bn_U; a.bn_chan = w.bn_chan = bn_chan; a.bn_grad = w.bn_grad = bn_grad;
-    a.bn_train = w.bn_train = bn_training;
-  }
-  const int gx = (int)ng, gy = (int)jt;
+  if (bn_U != nullptr) set_bn_fold(&a, &w, bn_U, bn_chan, bn_grad, bn_training);
+  const int kpw = (a.I / 16 + 3) / 4;
+  const int gx = a.n_groups, gy = a.J / 16;
   const int n_w = (int)(wgrid.x * wgrid.y * wgrid.z);
   dim3 grid((unsigned)(n_w + gx * gy));
-  const size_t lds = std::max(conv_w_lds<4>(), conv_ksplit_lds<1, 1>() + (a.bn_U ? (size_t)a.I * sizeof(float4) : 0));
+  const size_t lds = std::max(conv_w_lds<4>(), conv_ksplit_lds<1, 1>() + bn_fold_lds(a));
   BMNAS_COUNT(F_BWD_PAIR);
 #define BP_CASE(K)                                                                                     \
   case K:                                                                                              \
@@ -2303,11 +2309,8 @@ extern "C" int bmnas_conv1x1_fwd_group(const bmnas_conv_fwd_prob_t* probs, int n
   G.n = n;
   size_t lds = conv_ksplit_lds<1, 1>();
   int blocks = 0;
-  // longest contraction first: its tiles run longest
   int order[kGroupMax];
-  for (int p = 0; p < n; ++p) order[p] = p;
-  for (int i = 1; i < n; ++i)
-    for (int j = i; j > 0 && probs[order[j]].C_in > probs[order[j - 1]].C_in; --j) std::swap(order[j], order[j - 1]);
+  order_by_c_in(probs, n, order);
   // tile family, decided for the GROUP: the pipelined 32 x 96 tiles reuse their operands 3-6x better than the
   // 16 x 16 split-K tiles and the group as a whole fills the chip with them from ~96 tiles up, even where a
   // single layer would not (NTU at 64 samples: 32 tiles per layer, 256 for the group)
@@ -2316,17 +2319,16 @@ extern "C" int bmnas_conv1x1_fwd_group(const bmnas_conv_fwd_prob_t* probs, int n
   long pipe_tiles = 0;
   for (int q = 0; q < n; ++q)
     if (probs[q].C_in % 32 == 0) pipe_tiles += (long)((ng0 + 1) / 2) * ((M + kPipeJ - 1) / kPipeJ);
-  const bool use_pipe = pipe_tiles >= 96;
+  const bool use_pipe = pipe_tiles >= kPipeMinWgs;
   for (int q = 0; q < n; ++q) {
     const bmnas_conv_fwd_prob_t& P = probs[order[q]];
-    if (!P.src || !P.W || !P.U || P.C_in < 16) return BMNAS_E_ARG;
-    if (P.C_in % 16 || P.ldw % 4 || P.ldw < P.C_in) return BMNAS_E_SHAPE;
     ConvArgs& a = G.a[q];
-    if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
-    a.act.p[0] = P.src; a.dst.p[0] = P.U; a.W = P.W; a.bias = P.bias; a.ldw = P.ldw;
-    a.part = nullptr; a.stat = stat_shards ? P.stat : nullptr; a.stat_shards = stat_shards;
+    if (int e = conv_check(P.src && P.W && P.U && P.C_in >= 16, 1, P.C_in, b, M, P.ldw, 0, true)) return e;
+    if (int e = conv_fwd_args(a, &P.src, 1, P.C_in, P.W, P.ldw, 0, P.bias, P.U, stat_shards ? P.stat : nullptr,
+                              stat_shards, b, L, M))
+      return e;
+    a.probe = 0;                                   // (the grouped launches take no in-body probes)
     if (stat_shards && !P.stat) return BMNAS_E_ARG;
-    a.Ci = P.C_in; a.I = P.C_in; a.Cj = M; a.J = M; a.b = b; a.L = L; a.n_part = a.n_groups;
     const int pgx = (a.n_groups + 1) / 2, pgy = (M + kPipeJ - 1) / kPipeJ;
     G.start[q] = blocks;
     if (P.C_in % 32 == 0 && use_pipe) {
@@ -2358,24 +2360,21 @@ extern "C" int bmnas_conv1x1_fwd_group(const bmnas_conv_fwd_prob_t* probs, int n
     }();
     // (measured, NTU b64 / Ego b48, us — 96-column tiles: 1 quad 53.4 / 53.6, 2 quads 39.7 / 40.2, 4 quads 39.0 / 38.8:
     // the longest tiles are then bound by their CU's matrix pipe, 21.8 us for a 32 x 96 x 2048 tile; with the narrow
-    // tiles below: 2 quads 22.3 / 31.2, 4 quads 20.1 / 27.5.  BMNAS_FWD_GROUP_QUADS = 1 / 2 for the table)
-    static const int quad_mode = [] { const char* e = getenv("BMNAS_FWD_GROUP_QUADS"); return e ? atoi(e) : 4; }();
-    quads = std::min(quads, quad_mode);
+    // tiles below: 2 quads 22.3 / 31.2, 4 quads 20.1 / 27.5.  Hence: as many quads, up to 4, as divide every chunk count)
     size_t pipe_lds = conv_pipe_lds<32, 2>(L);
     while (quads > 1 && pipe_lds * quads > (size_t)lds_max) quads >>= 1;
     if (all_pipe && max_chunks >= 32 && blocks <= 320 && quads > 1) {
       // Tile width per layer.  A width that is no multiple of 96 (NTU / Ego: 128) wastes two thirds of its ragged
       // tile's MFMAs, and a 32 x 96 x 2048 tile keeps ONE CU's matrix pipe busy for 21.8 us while most CUs idle:
       // 64-column tiles where 96 does not divide the width, 32-column tiles for the long contractions (4x the
-      // tiles, a quarter of the work each).  BMNAS_FWD_GROUP_NARROW=0: 96-column tiles only (the table in DESIGN.md).
-      static const int narrow = [] { const char* e = getenv("BMNAS_FWD_GROUP_NARROW"); return e ? atoi(e) : 1; }();
+      // tiles, a quarter of the work each).  (Against 96-column tiles only: the table in DESIGN.md section 3.)
       ConvFwdGroup Gq = G;                                       // (G itself stays as the plain kernel wants it)
       int qblocks = 0;
       pipe_lds = 0;
       for (int q = 0; q < n; ++q) {
         const int nc = G.a[q].I / 32, pgx = (G.a[q].n_groups + 1) / 2;
         int jt = 3;
-        if (narrow && M % 96 != 0) jt = (nc >= 32 && M % 32 == 0) ? 1 : (M % 64 == 0 ? 2 : 3);
+        if (M % 96 != 0) jt = (nc >= 32 && M % 32 == 0) ? 1 : (M % 64 == 0 ? 2 : 3);
         Gq.kind[q] = jt == 3 ? 0 : (jt == 2 ? 2 : 3);
         Gq.start[q] = qblocks;
         Gq.gx[q] = pgx;
@@ -2423,35 +2422,24 @@ extern "C" int bmnas_conv1x1_bwd_group(const bmnas_conv_bwd_prob_t* probs, int n
   G.n = n;
   size_t lds = conv_w_lds<4>();
   int order[kGroupMax];
-  for (int p = 0; p < n; ++p) order[p] = p;
-  for (int i = 1; i < n; ++i)
-    for (int j = i; j > 0 && probs[order[j]].C_in > probs[order[j - 1]].C_in; --j) std::swap(order[j], order[j - 1]);
+  order_by_c_in(probs, n, order);
+  long w_tiles = 0;                                  // weight-gradient tiles of the whole group
+  for (int q = 0; q < n; ++q) w_tiles += (long)((M + 31) / 32) * ((probs[q].C_in + 31) / 32);
   int blocks = 0;
   for (int q = 0; q < n; ++q) {                      // weight-gradient tiles
     const bmnas_conv_bwd_prob_t& P = probs[order[q]];
-    if (!P.dV || !P.W || !P.src || !P.dW || P.C_in < 16) return BMNAS_E_ARG;
-    if (P.bn_U != nullptr && (!P.bn_chan || (bn_training && !P.bn_grad))) return BMNAS_E_ARG;
-    if (P.C_in % 16 || P.ldw % 4 || P.ldw < P.C_in) return BMNAS_E_SHAPE;
+    if (int e = conv_check(P.dV && P.W && P.src && P.dW && P.C_in >= 16 &&
+                               bn_fold_ok(P.bn_U, P.bn_chan, P.bn_grad, bn_training),
+                           1, P.C_in, b, M, P.ldw, 0, true))
+      return e;
     ConvWArgs& w = G.w[q];
     dim3 wgrid;
-    const float* srcs[1] = {P.src};
-    if (int e = fill_w_args(w, P.dV, srcs, 1, P.C_in, P.dW, P.ldw_grad, P.dbias, 0, b, L, M, 4, &wgrid)) return e;
-    {
-      // fill_w_args sizes the batch splits for a conv that has the chip to itself; here n layers share the
-      // grid: as many splits as bring the GROUP to ~3 weight-gradient workgroups per CU (every split is another
-      // round of fp32 atomics on dW)
-      long tiles_all = 0;
-      for (int r = 0; r < n; ++r) tiles_all += (long)((M + 31) / 32) * ((probs[r].C_in + 31) / 32);
-      int splits = (int)std::max<long>(1, (768 + tiles_all - 1) / tiles_all);
-      const int max_splits = (w.n_groups + 7) / 8;
-      splits = std::min(splits, std::max(1, max_splits));
-      if (g_conv_deterministic) splits = 1;
-      w.groups_per_split = (w.n_groups + splits - 1) / splits;
-      splits = (w.n_groups + w.groups_per_split - 1) / w.groups_per_split;
-      w.use_atomic = splits > 1;
-      wgrid.z = (unsigned)splits;
-    }
-    w.bn_U = P.bn_U; w.bn_chan = P.bn_chan; w.bn_grad = P.bn_grad; w.bn_train = bn_training;
+    if (int e = fill_w_args(w, P.dV, &P.src, 1, P.C_in, P.dW, P.ldw_grad, P.dbias, 0, b, L, M, 4, &wgrid)) return e;
+    // fill_w_args sizes the batch splits for a conv that has the chip to itself; here n layers share the
+    // grid: as many splits as bring the GROUP to ~3 weight-gradient workgroups per CU (every split is another
+    // round of fp32 atomics on dW)
+    wgrid.z = set_w_splits(w, (int)std::max<long>(1, (768 + w_tiles - 1) / w_tiles));
+    set_bn_fold(nullptr, &w, P.bn_U, P.bn_chan, P.bn_grad, bn_training);
     G.wstart[q] = blocks; G.wx[q] = (int)wgrid.x; G.wy[q] = (int)wgrid.y;
     blocks += (int)(wgrid.x * wgrid.y * wgrid.z);
   }
@@ -2463,32 +2451,34 @@ extern "C" int bmnas_conv1x1_bwd_group(const bmnas_conv_bwd_prob_t* probs, int n
     int Lb0, spw0, ng0;
     if (int e = check_shape(b > 0 ? b : 1, L, &Lb0, &spw0, &ng0)) return e;
     for (int q = 0; q < n; ++q)
-      if (probs[q].dsrc != nullptr) pipe_tiles += (long)((ng0 + 1) / 2) * ((probs[q].C_in + kPipeBJ - 1) / kPipeBJ);
+      if (probs[q].dsrc != nullptr) pipe_tiles += pipe_bwd_tiles(ng0, probs[q].C_in);
   }
+  const bool use_pipe = pipe_tiles >= kPipeMinWgs;
   for (int q = 0; q < n; ++q) {                      // data-gradient tiles
     const bmnas_conv_bwd_prob_t& P = probs[order[q]];
     ConvArgs& a = G.a[q];
-    if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
     G.dstart[q] = blocks;
-    if (P.dsrc == nullptr) continue;
-    a.act.p[0] = P.dV; a.dst.p[0] = P.dsrc; a.W = P.W; a.ldw = P.ldw;
-    a.Ci = M; a.I = M; a.Cj = P.C_in; a.J = P.C_in; a.b = b; a.L = L; a.acc_mask = P.accumulate ? 1u : 0u;
-    a.bn_U = P.bn_U; a.bn_chan = P.bn_chan; a.bn_grad = P.bn_grad; a.bn_train = bn_training;
-    const int pgx = (a.n_groups + 1) / 2, pgy = (a.J + kPipeBJ - 1) / kPipeBJ;
-    const size_t coef = a.bn_U ? (size_t)a.I * sizeof(float4) : 0;
-    if (M % 48 == 0 && pipe_tiles >= 96) {
+    if (P.dsrc == nullptr) {                         // no input gradient wanted: no tiles
+      if (int e = check_shape(b, L, &a.Lb, &a.spw, &a.n_groups)) return e;
+      continue;
+    }
+    if (int e = conv_bwd_args(a, P.dV, P.W, P.ldw, 0, &P.dsrc, 1, P.C_in, P.accumulate ? 1u : 0u, b, L, M)) return e;
+    a.probe = 0;                                     // (G.probe drops whole classes; no in-body probes here)
+    set_bn_fold(&a, nullptr, P.bn_U, P.bn_chan, P.bn_grad, bn_training);
+    const int pgx = (a.n_groups + 1) / 2;
+    if (M % 48 == 0 && use_pipe) {
       G.kind[q] = 0; G.gx[q] = pgx;
-      blocks += pgx * pgy;
-      lds = std::max(lds, conv_pipe_bwd_lds<48, 2>(L) + coef);
-    } else if (M % 32 == 0 && pipe_tiles >= 96) {
+      blocks += (int)pipe_bwd_tiles(a.n_groups, a.J);
+      lds = std::max(lds, conv_pipe_bwd_lds<48, 2>(L) + bn_fold_lds(a));
+    } else if (M % 32 == 0 && use_pipe) {
       G.kind[q] = 1; G.gx[q] = pgx;
-      blocks += pgx * pgy;
-      lds = std::max(lds, conv_pipe_bwd_lds<32, 2>(L) + coef);
+      blocks += (int)pipe_bwd_tiles(a.n_groups, a.J);
+      lds = std::max(lds, conv_pipe_bwd_lds<32, 2>(L) + bn_fold_lds(a));
     } else {
       G.kind[q] = (M / 16 + 3) / 4 <= 3 ? 3 : 6;
       G.gx[q] = a.n_groups;
       blocks += a.n_groups * (a.J / 16);
-      lds = std::max(lds, conv_ksplit_lds<1, 1>() + coef);
+      lds = std::max(lds, conv_ksplit_lds<1, 1>() + bn_fold_lds(a));
     }
   }
   G.dstart[n] = blocks;

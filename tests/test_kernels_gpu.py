@@ -714,10 +714,14 @@ def test_bn_relu_ln_tail(b, C, L, acc, sums):
                                                         (7, 64, 4, 64, 2, True, 3), (5, 192, 16, 192, 2, True, 0),
                                                         (128, 192, 16, 192, 2, True, 1), (250, 128, 8, 128, 2, True, 0),
                                                         (128, 512, 16, 192, 1, True, -1), (64, 2048, 8, 128, 1, True, 0),
-                                                        (6, 2048, 8, 128, 1, True, -1)])
+                                                        (6, 2048, 8, 128, 1, True, -1),
+                                                        # the boundary of the pipelined data-gradient tiles: 96 / 95 of them
+                                                        (192, 64, 16, 48, 1, True, 0), (192, 64, 16, 48, 1, None, 1),
+                                                        (190, 64, 16, 48, 1, True, 1), (190, 64, 16, 48, 1, None, 0)])
 def test_conv1x1_bwd_all_pair(b, C, L, M, n_src, training, acc):
     """bmnas_conv1x1_bwd_all (out_conv + bn backward, node_search.py:63-66): BatchNorm input gradient,
-    data gradient and weight / bias gradient; merged launch at the small grids, three launches otherwise."""
+    data gradient and weight / bias gradient; merged launch at the small grids, three launches otherwise.
+    training None: no BatchNorm in the call (bn_U = NULL), dV is dU."""
     from bmnas import lib
     g = _gen(4100 + b + C + n_src)
     dV, U = _rand(g, b, M, L), _rand(g, b, M, L) * 1.5 + 0.3
@@ -736,7 +740,9 @@ def test_conv1x1_bwd_all_pair(b, C, L, M, n_src, training, acc):
     xhat = (Ud - mean[None, :, None]) * rstd[None, :, None]
     scale = rstd * bn_w.double()
     s_dx, s_d = (dVd * xhat).sum(dim=(0, 2)), dVd.sum(dim=(0, 2))
-    if training:
+    if training is None:
+        dU = dVd
+    elif training:
         dU = scale[None, :, None] * (dVd - s_d[None, :, None] / N - xhat * s_dx[None, :, None] / N)
     else:
         dU = scale[None, :, None] * dVd
@@ -750,7 +756,7 @@ def test_conv1x1_bwd_all_pair(b, C, L, M, n_src, training, acc):
     dV_dev = dV.to(dev())
     before = lib.conv_family_calls(reset=True)
     lib.conv1x1_bwd_all(dV_dev, W.to(dev()), n_src * C, dst, C, acc, b, L, M, 0, [x.to(dev()) for x in srcs], dW,
-                        n_src * C, db, 0, (U.to(dev()), chan, bn_grad, training))
+                        n_src * C, db, 0, None if training is None else (U.to(dev()), chan, bn_grad, training))
     fam = lib.conv_family_calls(reset=True)
     import os
     pipe_on = os.environ.get('BMNAS_CONV_PIPE', '1') != '0'
@@ -758,7 +764,9 @@ def test_conv1x1_bwd_all_pair(b, C, L, M, n_src, training, acc):
     pipe = pipe_on and M % 48 == 0 and ((ng + 1) // 2) * ((n_src * C + 63) // 64) >= 96
     merged = want_data and not pipe and ((ng + 1) // 2) * ((jt + 1) // 2) < 1024
     assert (fam['bwd_pair'] == 1) == merged, fam
-    untouched = merged or pipe or not want_data         # else bn_bwd_apply ran in place first
+    if pipe and want_data:
+        assert fam['pipe_bwd'] == 1 and fam['conv_w'] == 1, fam
+    untouched = merged or pipe or not want_data or training is None      # else bn_bwd_apply ran in place first
     ref = torch.einsum('mc,bml->bcl', W.double(), dU)
     for q in range(n_src if want_data else 0):
         want = ref[:, q * C:(q + 1) * C]
