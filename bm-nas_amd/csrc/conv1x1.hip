@@ -1766,6 +1766,14 @@ inline void set_bn_fold(ConvArgs* a, ConvWArgs* w, const float* bn_U, const floa
   if (a) { a->bn_U = bn_U; a->bn_chan = bn_chan; a->bn_grad = bn_grad; a->bn_train = bn_training; }
   if (w) { w->bn_U = bn_U; w->bn_chan = bn_chan; w->bn_grad = bn_grad; w->bn_train = bn_training; }
 }
+// ... or, for the kernel families that do not fold: as a launch of its own, dU overwritten in place.  Eval mode needs
+// no bn_grad (bn_fold_ok) and bn_bwd_apply_k does not read it there, but bmnas_bn_bwd_apply refuses a NULL: it gets
+// bn_chan in its place, as the folding kernels do.
+inline int bn_apply_in_place(const float* dU, const float* bn_U, const float* bn_chan, const float* bn_grad,
+                             int bn_training, int b, int M, int L, void* stream) {
+  return bmnas_bn_bwd_apply(const_cast<float*>(dU), bn_U, bn_chan, bn_training ? bn_grad : bn_chan, b, M, L,
+                            bn_training, stream);
+}
 inline size_t bn_fold_lds(const ConvArgs& a) { return a.bn_U ? (size_t)a.I * sizeof(float4) : 0; }   // its coefficients
 
 // Forward-shaped problem (checked by conv_check): U (b, M, L) = W cat(srcs) + bias.  A NULL among srcs is refused by
@@ -2149,7 +2157,7 @@ extern "C" int bmnas_conv1x1_bwd_all_sdpa(const float* dU, const float* W, int l
     if (pipe || (ksplit && ksplit_fits(3 * kch, tn, tn, true))) {   // the GEMM kernels apply the BatchNorm backward on the fly
       set_bn_fold(&a, &w, bn_U, bn_chan, bn_grad, bn_training);
     } else {                                        // other kernel families: as its own launch, in place
-      if (int e = bmnas_bn_bwd_apply(const_cast<float*>(dU), bn_U, bn_chan, bn_grad, b, M, L, bn_training, stream))
+      if (int e = bn_apply_in_place(dU, bn_U, bn_chan, bn_grad, bn_training, b, M, L, stream))
         return e;
     }
   }
@@ -2259,7 +2267,7 @@ extern "C" int bmnas_conv1x1_bwd_all_mix(const float* dU, const float* W, int ld
     const bool fold_here = bn_U != nullptr && (pipe || !want_data);
     if (fold_here) set_bn_fold(&a, &w, bn_U, bn_chan, bn_grad, bn_training);
     if (bn_U != nullptr && !fold_here)
-      if (int e = bmnas_bn_bwd_apply(const_cast<float*>(dU), bn_U, bn_chan, bn_grad, b, M, L, bn_training, stream))
+      if (int e = bn_apply_in_place(dU, bn_U, bn_chan, bn_grad, bn_training, b, M, L, stream))
         return e;
     if (want_data && pipe) {
       launch_pipe_bwd(a, st);

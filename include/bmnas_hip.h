@@ -170,7 +170,15 @@ int bmnas_conv1x1_num_partials(int b, int L);
  * stat_shards > 0 selects the other form of batch statistics: part is then a ZERO-FILLED buffer of
  * stat_shards * M * 2 floats into which the launch adds, with fp32 atomics, the per-channel sums of
  * d = U - bias and of d^2 (shard = column block % stat_shards).  The kernel that applies the
- * BatchNorm finalises them itself (bmnas_bn_fin_t below): no bmnas_bn_finalize launch. */
+ * BatchNorm finalises them itself (bmnas_bn_fin_t below): no bmnas_bn_finalize launch.
+ * What the buffer holds: part[(shard*M + m)*2 + {0,1}] += (sum of d, sum of d^2) of channel m over the VALID
+ * (sample, l) columns of the column blocks of that shard; padded columns of the last n-group add nothing, a bias
+ * of NULL makes d = U.  A column block is what one workgroup reduces before its atomics: ONE n-group g (16
+ * columns, g < bmnas_conv1x1_num_partials) in the split-K and whole-K LDS kernels, so shard = g % stat_shards;
+ * the 2 or 4 consecutive n-groups of a tile in the pipelined tile kernels, so shard = (g / 2) % stat_shards or
+ * (g / 4) % stat_shards.  Shards that no block maps to (stat_shards > blocks) keep their value.  Only the sum over
+ * the shards is independent of the kernel family, and that is all a consumer may rely on
+ * (tests/test_conv_kernels_gpu.py checks every shard by the family that ran, tests/conv_ref.py: shard_sums). */
 int bmnas_conv1x1_fwd(const float* const* srcs, int n_src, int C_src, const float* W, int ldw,
                       int fold_cols, const float* bias, float* U, float* part, int stat_shards, int b,
                       int L, int M, void* stream);

@@ -15,6 +15,8 @@ fp32 torch contraction in the same test, so no family runs unverified:
     fwd_sdpa_pipe / _ksplit conv + attention in one launch (search NodeMixedOp, large / small batch)
     bwd_all_pipe / _ksplit  data-gradient + weight-gradient + attention backward in one launch
     conv_w                  weight-gradient GEMM alone
+
+Per-instantiation cases (every register variant, tile size and edge path, against float64): tests/test_conv_kernels_gpu.py.
 """
 import numpy as np
 import pytest
