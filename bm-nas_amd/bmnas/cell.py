@@ -186,6 +186,7 @@ class HeadState(Pack):
     and labels.  `marker` stands in for dlogits in that case: the backward recognises it by address."""
 
     deferred = None      # ('bce' | 'ce', labels)
+    crit = None          # lib.Criterion of a deferred weighted / smoothed criterion (None: the bare mean form)
     gscale = None        # 0-dim device tensor multiplying dlogits (None: 1)
 
     def resolve(self, g):
@@ -1168,12 +1169,13 @@ def fusion_cell_bwd(sv, g, need_input_grads, dalpha_w, dbeta_ws, dgamma_ws, CG, 
             loss_part = _empty(x0, n_chunk) if (DETERMINISTIC and mode != 0) else None
             lib.head_bwd_lazy([n.lazy.desc for n in tailn], [n.lazy.lnp_head for n in tailn], bufs, mask, CP.ln_w,
                               CP.ln_b, head.W, head.hb, sv.stats, mode, gten, gscale, labels, head.loss, part, b, C,
-                              L, O, getattr(CG, 'scrub', None), loss_part)
+                              L, O, getattr(CG, 'scrub', None), loss_part, crit=head.crit if mode else None)
             if loss_part is not None:            # the chunks' shares in a fixed order (a four-element sum)
                 head.loss.copy_(loss_part.sum(0, keepdim=True))
         else:
             lib.head_bwd(sv.states[-M:], head.sums, bufs, mask, CP.ln_w, CP.ln_b, head.W, head.hb, sv.stats, mode,
-                         gten, gscale, labels, head.loss, part, b, C, L, O, getattr(CG, 'scrub', None))
+                         gten, gscale, labels, head.loss, part, b, C, L, O, getattr(CG, 'scrub', None),
+                         crit=head.crit if mode else None)
         head.dW = head.dbias = None
         if want:
             hsum = _empty(x0, (O + 3) * D)

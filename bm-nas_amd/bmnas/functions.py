@@ -342,7 +342,7 @@ class FoundHeadFn(Function):
         part = torch.empty(n_chunk * (O + 3) * D, device=states[0].device, dtype=torch.float32) if want else None
         dstates = [torch.empty_like(s) if ctx.needs_input_grad[5 + i] else None for i, s in enumerate(states)]
         lib.head_bwd(states, sums, dstates, 0, ctx.lw, ctx.lb, head.W, head.hb, ctx.stats, mode, gten, gscale, labels,
-                     head.loss, part, b, C, L, O, None)
+                     head.loss, part, b, C, L, O, None, crit=head.crit if mode else None)
         dlw = dlb = dW = dbias = None
         if want:
             hsum = torch.empty((O + 3) * D, device=states[0].device, dtype=torch.float32)
@@ -1291,14 +1291,17 @@ class DeferredLossFn(Function):
     """The criterion of a fused head, evaluated by the head's BACKWARD launch (bmnas_head_bwd modes
     1 / 2): forward only records kind and labels and hands out the loss scalar that the backward
     will fill — valid once backward has run, which is all a captured step needs (nothing can read a
-    value between two nodes of a hipGraph).  Enabled by bmnas.nn.fused_criterion()."""
+    value between two nodes of a hipGraph).  Enabled by bmnas.nn.fused_criterion().  crit: the lib.Criterion of a
+    weighted / smoothed criterion (bmnas_head_bwd_crit; its weight tensors are read, by address, when the backward
+    launch runs), None for the bare mean form."""
 
     @staticmethod
-    def forward(ctx, z, target, head, kind):
+    def forward(ctx, z, target, head, kind, crit=None):
         if head.deferred is not None:
             raise lib.BmnasError('fused criterion: a second criterion on the same logits (the head evaluates ONE '
                                  'criterion in its backward launch); call it outside bmnas.nn.fused_criterion()')
         head.deferred = (kind, target if target.is_contiguous() else target.contiguous())
+        head.crit = crit
         head.gscale = None
         ctx.head = head
         return head.loss.view(())
@@ -1309,7 +1312,7 @@ class DeferredLossFn(Function):
         u = _UNIT.get((gl.device.type, gl.device.index))
         if not (u is not None and gl.data_ptr() == u.data_ptr()):
             head.gscale = gl.contiguous().float()          # d(loss)/d(loss) other than the constant 1
-        return head.marker, None, None, None
+        return head.marker, None, None, None, None
 
 
 class BCEWithLogitsFn(_LossFn):
@@ -1334,3 +1337,43 @@ class CrossEntropyFn(_LossFn):
         rows = torch.empty(b, device=z.device, dtype=torch.float32)
         lib.cross_entropy(z, label.contiguous(), loss, dz, rows, b, O)
         return _LossFn._finish(ctx, loss, dz)
+
+
+class BCEWithLogitsCritFn(_LossFn):
+    """BCEWithLogits with per-class weight / pos_weight and reduction mean | sum (bmnas_bce_logits_crit)."""
+
+    @staticmethod
+    def forward(ctx, z, y, crit):
+        _require_gpu(z, 'BCEWithLogits loss')
+        z, y = _c(_f32(z)), _c(_f32(y))
+        loss = torch.empty(1, device=z.device, dtype=torch.float32)
+        dz = torch.empty_like(z)
+        O = z.shape[-1]
+        lib.bce_logits_crit(z, y, crit, loss, dz, z.numel() // O, O)
+        ctx.save_for_backward(dz)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        return (*_LossFn.backward(ctx, gl), None)
+
+
+class CrossEntropyCritFn(_LossFn):
+    """CrossEntropy with class weights, label smoothing, ignore_index and reduction mean | sum
+    (bmnas_cross_entropy_crit)."""
+
+    @staticmethod
+    def forward(ctx, z, label, crit):
+        _require_gpu(z, 'CrossEntropy loss')
+        z = _c(_f32(z))
+        b, O = z.shape
+        loss = torch.empty(1, device=z.device, dtype=torch.float32)
+        dz = torch.empty_like(z)
+        rows = torch.empty(b, device=z.device, dtype=torch.float32)
+        lib.cross_entropy_crit(z, label.contiguous(), crit, loss, dz, rows, b, O)
+        ctx.save_for_backward(dz)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        return (*_LossFn.backward(ctx, gl), None)

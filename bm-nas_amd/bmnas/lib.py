@@ -73,6 +73,35 @@ class LazyLn(C.Structure):
     _fields_ = [('pre', C.c_void_p), ('rec', C.c_void_p), ('prm', C.c_void_p), ('ln_w', C.c_void_p),
                 ('ln_b', C.c_void_p), ('stats', C.c_void_p)]
 
+class CriterionDesc(C.Structure):
+    """bmnas_criterion_t: the options of a weighted / smoothed criterion, passed by value"""
+    _fields_ = [('weight', C.c_void_p), ('pos_weight', C.c_void_p), ('label_smoothing', C.c_float),
+                ('ignore_index', C.c_int64), ('reduction', C.c_int)]
+
+
+CRIT_BCE, CRIT_CE = 1, 2
+REDUCTIONS = {'mean': 0, 'sum': 1}
+
+
+class Criterion:
+    """Host side of bmnas_criterion_t.  It keeps the weight tensors alive and names them by ADDRESS: the kernels read
+    them when the launch runs, so an in-place edit between two replays of a captured step takes effect."""
+
+    def __init__(self, kind, weight=None, pos_weight=None, label_smoothing=0.0, ignore_index=-100, reduction='mean'):
+        if kind not in ('bce', 'ce') or reduction not in REDUCTIONS:
+            raise BmnasError(f'criterion kind {kind!r} / reduction {reduction!r}: kind bce | ce, reduction mean | sum')
+        self.kind, self.weight, self.pos_weight = kind, weight, pos_weight
+        self.label_smoothing, self.ignore_index, self.reduction = float(label_smoothing), int(ignore_index), reduction
+
+    @property
+    def code(self):
+        return CRIT_BCE if self.kind == 'bce' else CRIT_CE
+
+    def desc(self):
+        return CriterionDesc(_ptr(self.weight), _ptr(self.pos_weight), self.label_smoothing, self.ignore_index,
+                             REDUCTIONS[self.reduction])
+
+
 MAX_GROUP = 8
 
 
@@ -255,6 +284,12 @@ SIGNATURES = {
                                 _P, _P, _U32, _P, _P, _I, _I, _I, Dropout, Dropout, _P, _P], _I),
     'bmnas_head_bwd': ([_PP, _PP, _PP, _I, _U32, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I,
                         _P, _I64, _P], _I),
+    'bmnas_head_bwd_crit': ([_PP, _PP, _PP, _I, _U32, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I,
+                             _P, _I64, CriterionDesc, _P], _I),
+    'bmnas_head_bwd_lazy_crit': ([C.POINTER(LazyLn), _PP, _PP, _I, _U32, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P,
+                                  _I, _I, _I, _I, _P, _I64, _P, CriterionDesc, _P], _I),
+    'bmnas_bce_logits_crit': ([_P, _P, CriterionDesc, _P, _P, _I, _I, _P], _I),
+    'bmnas_cross_entropy_crit': ([_P, _P, CriterionDesc, _P, _P, _P, _I, _I, _P], _I),
     'bmnas_sum_chunks': ([_P, _P, _I, _I64, _P], _I),
     'bmnas_comm_available': ([], _I),
     'bmnas_comm_unique_id_bytes': ([], _I),
@@ -474,8 +509,20 @@ def head_fwd(srcs, sums, ln_w, ln_b, W, bias, hb, stats, b, Cc, L, O):
 
 
 def head_bwd(srcs, sums, dsrcs, acc_mask, ln_w, ln_b, W, hb, stats, mode, g, gscale, labels, loss, part,
-             b, Cc, L, O, scrub=None):
-    """mode 0: g = dlogits; 1: BCEWithLogits(mean) vs float labels; 2: CrossEntropy(mean) vs int64 labels."""
+             b, Cc, L, O, scrub=None, crit=None):
+    """mode 0: g = dlogits; 1: BCEWithLogits(mean) vs float labels; 2: CrossEntropy(mean) vs int64 labels.
+    crit (a Criterion, modes 1 / 2): the weighted / smoothed form of that criterion (bmnas_head_bwd_crit)."""
+    if crit is not None:
+        if mode != crit.code:
+            raise BmnasError(f'mode {mode} with a {crit.kind!r} descriptor: the descriptor forms evaluate the criterion '
+                             'they describe')
+        _check(load().bmnas_head_bwd_crit(_ptrs(srcs), _ptrs(sums), _ptrs(dsrcs), len(srcs), acc_mask, _ptr(ln_w),
+                                          _ptr(ln_b), _ptr(W), _ptr(hb), _ptr(stats), mode,
+                                          None if gscale is None else gscale.data_ptr(),
+                                          None if labels is None else labels.data_ptr(), _ptr(loss), _ptr(part),
+                                          b, Cc, L, O, _ptr(scrub), 0 if scrub is None else scrub.numel(),
+                                          crit.desc(), _stream()), 'head_bwd_crit')
+        return
     _check(load().bmnas_head_bwd(_ptrs(srcs), _ptrs(sums), _ptrs(dsrcs), len(srcs), acc_mask, _ptr(ln_w),
                                  _ptr(ln_b), _ptr(W), _ptr(hb), _ptr(stats), mode, _ptr(g),
                                  None if gscale is None else gscale.data_ptr(),
@@ -566,9 +613,21 @@ def set_deterministic(on):
 
 
 def head_bwd_lazy(lazies, lnparts, dsrcs, acc_mask, ln_w, ln_b, W, hb, stats, mode, g, gscale, labels, loss, part,
-                  b, Cc, L, O, scrub=None, loss_part=None):
+                  b, Cc, L, O, scrub=None, loss_part=None, crit=None):
     n = len(lazies)
     arr = (LazyLn * n)(*lazies)
+    if crit is not None:
+        if mode != crit.code:
+            raise BmnasError(f'mode {mode} with a {crit.kind!r} descriptor: the descriptor forms evaluate the criterion '
+                             'they describe')
+        _check(load().bmnas_head_bwd_lazy_crit(arr, _ptrs(lnparts), _ptrs(dsrcs), n, acc_mask, _ptr(ln_w), _ptr(ln_b),
+                                               _ptr(W), _ptr(hb), _ptr(stats), mode,
+                                               None if gscale is None else gscale.data_ptr(),
+                                               None if labels is None else labels.data_ptr(), _ptr(loss), _ptr(part),
+                                               b, Cc, L, O, _ptr(scrub), 0 if scrub is None else scrub.numel(),
+                                               _ptr(loss_part), crit.desc(), _stream()),
+               'head_bwd_lazy_crit')
+        return
     _check(load().bmnas_head_bwd_lazy(arr, _ptrs(lnparts), _ptrs(dsrcs), n, acc_mask, _ptr(ln_w), _ptr(ln_b),
                                       _ptr(W), _ptr(hb), _ptr(stats), mode, _ptr(g),
                                       None if gscale is None else gscale.data_ptr(),
@@ -1022,6 +1081,16 @@ def linear_bwd(g, gscale, feat, W, dfeat, dW, dbias, b, O, Kd):
 def bce_logits(z, y, loss, dz):
     _check(load().bmnas_bce_logits(_ptr(z), _ptr(y), _ptr(loss), _ptr(dz), z.numel(), _stream()),
            'bce_logits')
+
+
+def bce_logits_crit(z, y, crit, loss, dz, rows, O):
+    _check(load().bmnas_bce_logits_crit(_ptr(z), _ptr(y), crit.desc(), _ptr(loss), _ptr(dz), rows, O, _stream()),
+           'bce_logits_crit')
+
+
+def cross_entropy_crit(z, label, crit, loss, dz, row_loss, b, O):
+    _check(load().bmnas_cross_entropy_crit(_ptr(z), label.data_ptr(), crit.desc(), _ptr(loss), _ptr(dz),
+                                           _ptr(row_loss), b, O, _stream()), 'cross_entropy_crit')
 
 
 def cross_entropy(z, label, loss, dz, row_loss, b, O):

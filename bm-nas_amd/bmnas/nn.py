@@ -1,16 +1,18 @@
 """Drop-in nn.Module replacements for the two callers right after the fusion cell: the
 central classifier (nn.Linear) and the criterion, both on the gfx950 kernels of
 csrc/linear.hip.  Same constructor signatures, parameter names and state_dict keys as the torch
-classes they subclass.  Option combinations the kernels do not cover (the reference never uses
-them) run the torch parent class after a one-time RuntimeWarning (bmnas.lib.note_off_path):
-nothing leaves the HIP path silently."""
+classes they subclass.  The criteria take class weights, pos_weight, label smoothing, ignore_index and
+reduction 'mean' | 'sum' on the kernels (criterion_route says which calls); the combinations left
+run the torch parent class after a one-time RuntimeWarning (bmnas.lib.note_off_path): nothing
+leaves the HIP path silently."""
 import torch
 import torch.nn as nn
 
 import contextlib
 
 from . import lib
-from .functions import BCEWithLogitsFn, CrossEntropyFn, DeferredLossFn, LinearFn
+from .functions import (BCEWithLogitsCritFn, BCEWithLogitsFn, CrossEntropyCritFn, CrossEntropyFn, DeferredLossFn,
+                        LinearFn)
 
 _FUSED_CRITERION = [False]
 
@@ -49,14 +51,90 @@ class Linear(nn.Linear):
         return super().forward(x)
 
 
+def _on_gpu(t):
+    return t.device.type == 'cuda'
+
+
+def _class_weight_ok(w, n_classes):
+    """None, or what the kernels read by address: a contiguous 1-D fp32 device tensor with one entry per class."""
+    return w is None or (w.dim() == 1 and w.shape[0] == n_classes and w.dtype == torch.float32 and _on_gpu(w)
+                         and w.is_contiguous())
+
+
+def _bare_ok(module, input, target):
+    """The conditions under which the bare mean kernels ran before the options existed, unchanged: calls that took
+    them then take them now."""
+    if isinstance(module, nn.BCEWithLogitsLoss):
+        return (_on_gpu(input) and module.weight is None and module.pos_weight is None and module.reduction == 'mean'
+                and input.dtype == torch.float32 and target.dtype == torch.float32
+                and tuple(input.shape) == tuple(target.shape))
+    if isinstance(module, nn.CrossEntropyLoss):
+        return (_on_gpu(input) and len(input.shape) == 2 and module.weight is None and module.reduction == 'mean'
+                and module.label_smoothing == 0.0 and module.ignore_index == -100
+                and target.dtype == torch.int64 and len(target.shape) == 1 and input.dtype == torch.float32)
+    return False
+
+
+def _criterion_plan(module, input, target):
+    """-> None (the torch parent class runs), 'bare' (the kernels of the plain mean form: today's numbers) or 'crit'
+    (the weighted / smoothed kernels, bmnas_criterion_t).  Reads shapes, dtypes and devices only."""
+    if _bare_ok(module, input, target):
+        return 'bare'
+    if not (_on_gpu(input) and _on_gpu(target) and input.dtype == torch.float32 and len(input.shape) >= 1
+            and module.reduction in ('mean', 'sum')):
+        return None
+    n_classes = input.shape[-1]
+    if not _class_weight_ok(module.weight, n_classes):
+        return None
+    if isinstance(module, nn.BCEWithLogitsLoss):
+        if not (target.dtype == torch.float32 and tuple(input.shape) == tuple(target.shape)
+                and _class_weight_ok(module.pos_weight, n_classes)):
+            return None
+        return 'crit'
+    if isinstance(module, nn.CrossEntropyLoss):
+        # (class-index targets only: probability targets have the logits' dtype and shape)
+        if not (len(input.shape) == 2 and target.dtype == torch.int64 and len(target.shape) == 1
+                and target.shape[0] == input.shape[0] and 0.0 <= module.label_smoothing < 1.0):
+            return None
+        return 'crit'
+    return None
+
+
+def criterion_route(module, input, target):
+    """'native': the call runs on the gfx950 kernels (csrc/linear.hip, or csrc/head.hip's backward launch inside
+    fused_criterion()); 'torch': it warns once and runs the torch parent class.  A pure host decision over shapes,
+    dtypes, devices and the module's options:
+
+      BCEWithLogitsLoss   fp32 device logits (..., O) and targets of the same shape; `weight` / `pos_weight` absent or
+                          contiguous 1-D fp32 device tensors of length O; reduction 'mean' | 'sum'.
+      CrossEntropyLoss    fp32 device logits (b, O), int64 class-index targets (b); `weight` as above;
+                          0 <= label_smoothing < 1; any ignore_index; reduction 'mean' | 'sum'.
+
+    Everything else is 'torch': reduction='none', probability targets, weights of other shapes or dtypes, CPU tensors.
+    The bare mean forms (no weight, no smoothing, ignore_index -100) are selected under exactly the conditions that
+    selected them before the options existed (_bare_ok).
+    A default-constructed CrossEntropyLoss() keeps the kernels of the bare mean form, which do NOT look for labels equal
+    to its ignore_index of -100 (the reference's label sets hold none); give any other option, or another ignore_index,
+    and ignored rows are honoured."""
+    return 'torch' if _criterion_plan(module, input, target) is None else 'native'
+
+
+def _crit_of(module, kind):
+    return lib.Criterion(kind, weight=module.weight, pos_weight=getattr(module, 'pos_weight', None),
+                         label_smoothing=getattr(module, 'label_smoothing', 0.0),
+                         ignore_index=getattr(module, 'ignore_index', -100), reduction=module.reduction)
+
+
 class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
     def forward(self, input, target):
-        if (input.is_cuda and self.weight is None and self.pos_weight is None and self.reduction == 'mean'
-                and input.dtype == torch.float32 and target.dtype == torch.float32
-                and input.shape == target.shape):
+        plan = _criterion_plan(self, input, target)
+        if plan is not None:
+            crit = _crit_of(self, 'bce') if plan == 'crit' else None
             head = _deferrable(input)
             if head is not None:
-                return DeferredLossFn.apply(input, target, head, 'bce')
+                return DeferredLossFn.apply(input, target, head, 'bce', crit)
+            if crit is not None:
+                return BCEWithLogitsCritFn.apply(input, target, crit)
             return BCEWithLogitsFn.apply(input, target)
         lib.note_off_path('bmnas.nn.BCEWithLogitsLoss', f'input {tuple(input.shape)} {input.dtype} on {input.device}, '
                           f'target {tuple(target.shape)} {target.dtype}, reduction {self.reduction}')
@@ -65,12 +143,14 @@ class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):
     def forward(self, input, target):
-        if (input.is_cuda and input.dim() == 2 and self.weight is None and self.reduction == 'mean'
-                and self.label_smoothing == 0.0 and self.ignore_index == -100
-                and target.dtype == torch.int64 and target.dim() == 1 and input.dtype == torch.float32):
+        plan = _criterion_plan(self, input, target)
+        if plan is not None:
+            crit = _crit_of(self, 'ce') if plan == 'crit' else None
             head = _deferrable(input)
             if head is not None:
-                return DeferredLossFn.apply(input, target, head, 'ce')
+                return DeferredLossFn.apply(input, target, head, 'ce', crit)
+            if crit is not None:
+                return CrossEntropyCritFn.apply(input, target, crit)
             return CrossEntropyFn.apply(input, target)
         lib.note_off_path('bmnas.nn.CrossEntropyLoss', f'input {tuple(input.shape)} {input.dtype} on {input.device}, '
                           f'target {tuple(target.shape)} {target.dtype}, reduction {self.reduction}')

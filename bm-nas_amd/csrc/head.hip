@@ -252,6 +252,12 @@ struct HeadBwdArgs {
   long long scrub4;
   int b, O, D, CL, n_src, mode;
   int probe;                 // BMNAS_HEAD_PROBE: timing diagnostics only (results incomplete)
+  // the weighted / smoothed criteria (CR != 0 instantiations only; bmnas_criterion_t): a NULL pointer means ones
+  const float* cw;           // (O) class weights
+  const float* cpw;          // (O) BCE positive weights
+  long long ignore;          // CE: rows with this label count for nothing
+  float eps;                 // CE: label smoothing
+  int red;                   // 0 mean, 1 sum
 };
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
@@ -265,10 +271,16 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf
 // LayerNorm backward and the state-gradient store are coalesced), and dW = dl^T feat accumulated
 // over the SG groups, with feat recomputed in B-operand layout straight from the states.
 // OT = class tiles of 16 the kernel is built for (O <= 16 OT).
+// CR = 0: modes 0 - 2 as above.  CR = 1: BCEWithLogits with per-class weight / pos_weight, CR = 2: CrossEntropy with
+// class weights, label smoothing and ignore_index, both with reduction mean or sum (the formulas: bmnas_hip.h,
+// bmnas_criterion_t).  A compile-time parameter: the CR = 0 instantiations carry none of the extra registers.  The
+// per-class values join the prologue loads (a thread owns the class stripes lo + 16 u); the denominator of the
+// weighted CE mean, sum of w[label] over the rows that count, is formed by every workgroup over all b labels in a
+// fixed order (thread-strided partial sums, wave butterflies, four LDS slots): no host read, no launch in front.
 __device__ __forceinline__ float group16_sum(float v) { return row16_sum(v); }
 __device__ __forceinline__ float group16_max(float v) { return row16_max(v); }
 
-template <int OT, int SG, bool LZ>
+template <int OT, int SG, bool LZ, int CR = 0>
 __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
   constexpr int kSteps = 4 * OT, kRows = 16 * SG;
   __shared__ float dl_s[kRows][16 * OT + 4];
@@ -328,6 +340,23 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
   {
     float zz[SG][OT], aa[SG][OT], bb[SG][OT], yy[SG][OT], st_mean[SG], st_rstd[SG], nd_mean[SG], nd_rstd[SG];
     int lab[SG];
+    float cwv[CR != 0 ? OT : 1], cpv[CR == 1 ? OT : 1];
+    if constexpr (CR != 0) {
+      // (unconditional loads, from an always-valid address where there is no such vector: hb holds >= 3 O floats)
+      const float* const cwp = a.cw != nullptr ? a.cw : a.hb;
+      const float* const cpp = a.cpw != nullptr ? a.cpw : a.hb;
+#pragma unroll
+      for (int u = 0; u < OT; ++u) {
+        const int o = lo + 16 * u;
+        const int oc = o < a.O ? o : a.O - 1;
+        const float wv_ = cwp[oc];
+        cwv[u] = a.cw != nullptr ? wv_ : 1.f;
+        if constexpr (CR == 1) {
+          const float pv_ = cpp[oc];
+          cpv[u] = a.cpw != nullptr ? pv_ : 1.f;
+        }
+      }
+    }
 #pragma unroll
     for (int g = 0; g < SG; ++g) {
       const int sp = s0 + 16 * g + (threadIdx.x >> 4);
@@ -341,7 +370,12 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
         bb[g][u] = a.hb[((int64_t)2 * a.b + spc) * a.O + oc];
         yy[g][u] = (a.mode == 1) ? a.labels_f[(int64_t)spc * a.O + oc] : 0.f;
       }
-      lab[g] = (a.mode == 2) ? (int)a.labels_i[spc] : 0;
+      if constexpr (CR == 2) {                                  // -1: the row counts for nothing (never an index)
+        const long long l = a.labels_i[spc];
+        lab[g] = (l != a.ignore && l >= 0 && l < (long long)a.O) ? (int)l : -1;
+      } else {
+        lab[g] = (a.mode == 2) ? (int)a.labels_i[spc] : 0;
+      }
       st_mean[g] = a.stats[2 * spc];
       st_rstd[g] = a.stats[2 * spc + 1];
       nd_mean[g] = LZ ? nstq[2 * spc] : 0.f;
@@ -355,13 +389,81 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
       st4_wt(a.scrub + 4 * i, make_float4(0.f, 0.f, 0.f, 0.f));
     __builtin_amdgcn_sched_barrier(0);
     float loss_acc = 0.f;
+    float cden = 1.f, cwsum = 0.f;
+    if constexpr (CR == 2) {
+      if (a.red == 0) {                                         // uniform
+        __shared__ float den_s[4];
+        float t = 0.f;
+        for (int i = threadIdx.x; i < a.b; i += 256) {
+          const long long l = a.labels_i[i];
+          const bool k = l != a.ignore && l >= 0 && l < (long long)a.O;
+          const float wl = a.cw != nullptr ? a.cw[k ? l : 0] : 1.f;
+          t += k ? wl : 0.f;
+        }
+        t = wave_sum(t);
+        if (lane == 0) den_s[wave] = t;
+        __syncthreads();
+        cden = (den_s[0] + den_s[1]) + (den_s[2] + den_s[3]);
+      }
+#pragma unroll
+      for (int u = 0; u < OT; ++u) cwsum += (lo + 16 * u < a.O) ? cwv[u] : 0.f;
+      cwsum = group16_sum(cwsum);
+    }
 #pragma unroll
     for (int g = 0; g < SG; ++g) {
       const int rr = 16 * g + (threadIdx.x >> 4);
       const bool vsp = s0 + rr < a.b;
       float dl[OT];
       float row_loss = 0.f;
-      if (a.mode == 0) {
+      if constexpr (CR == 1) {                                  // BCEWithLogits, weight / pos_weight, mean | sum
+        const float sc_ = a.red == 0 ? gs / ((float)a.b * (float)a.O) : gs;
+#pragma unroll
+        for (int u = 0; u < OT; ++u) {
+          const bool vo = lo + 16 * u < a.O;
+          const float z = zz[g][u], y = yy[g][u];
+          const float c = 1.f + (cpv[u] - 1.f) * y;
+          dl[u] = vo ? cwv[u] * ((1.f - y) - c * sigmoidf_(-z)) * sc_ : 0.f;
+          if (vo) row_loss += cwv[u] * ((1.f - y) * z + c * (log1pf(__expf(-fabsf(z))) + fmaxf(-z, 0.f)));
+        }
+      } else if constexpr (CR == 2) {                           // CrossEntropy, weight / smoothing / ignore, mean | sum
+        const bool keep = lab[g] >= 0;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < OT; ++u)
+          if (lo + 16 * u < a.O) mx = fmaxf(mx, zz[g][u]);
+        mx = group16_max(mx);
+        float e[OT], den = 0.f;
+#pragma unroll
+        for (int u = 0; u < OT; ++u) {
+          e[u] = (lo + 16 * u < a.O) ? __expf(zz[g][u] - mx) : 0.f;
+          den += e[u];
+        }
+        den = group16_sum(den);
+        const float lse = mx + __logf(den);
+        float sm = 0.f, wy = 0.f, ny = 0.f;                     // sum_c w_c (-log p_c), w[label], -log p[label]
+#pragma unroll
+        for (int u = 0; u < OT; ++u) {
+          const int o = lo + 16 * u;
+          const float nl = lse - zz[g][u];
+          if (o < a.O) sm += cwv[u] * nl;
+          if (o < a.O && o == lab[g]) {
+            wy = cwv[u];
+            ny = nl;
+          }
+        }
+        sm = group16_sum(sm);
+        wy = group16_sum(wy);
+        ny = group16_sum(ny);
+        const float a1 = (1.f - a.eps) * wy, a2 = a.eps / (float)a.O;
+        const float sc_ = gs / cden;
+#pragma unroll
+        for (int u = 0; u < OT; ++u) {
+          const int o = lo + 16 * u;
+          const float p = e[u] / den;
+          dl[u] = (o < a.O && keep) ? (a1 * (p - (o == lab[g] ? 1.f : 0.f)) + a2 * (cwsum * p - cwv[u])) * sc_ : 0.f;
+        }
+        if (lo == 0 && keep) row_loss = a1 * ny + a2 * sm;
+      } else if (a.mode == 0) {
 #pragma unroll
         for (int u = 0; u < OT; ++u) dl[u] = (lo + 16 * u < a.O) ? zz[g][u] * gs : 0.f;
       } else if (a.mode == 1) {                                 // BCEWithLogits, reduction = mean
@@ -421,7 +523,10 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
       loss_acc = wave_sum(loss_acc);
       // (the chunk's 16 SG rows are spread over the workgroup's four waves: wave partials meet in LDS first when the
       // chunk's share has to be ONE number)
-      const float share = loss_acc / (a.mode == 1 ? (float)a.b * (float)a.O : (float)a.b);
+      float share;
+      if constexpr (CR == 1) share = a.red == 0 ? loss_acc / ((float)a.b * (float)a.O) : loss_acc;
+      else if constexpr (CR == 2) share = loss_acc / cden;     // (mean over no row that counts: 0 / 0 = NaN, as torch)
+      else share = loss_acc / (a.mode == 1 ? (float)a.b * (float)a.O : (float)a.b);
       if (a.loss_part != nullptr) {
         if (lane == 0) loss_s[wave] = share;
       } else if (lane == 0) {
@@ -692,14 +797,28 @@ extern "C" int bmnas_head_fwd_lazy(const float* const* srcs, const float* const*
   return head_fwd_impl(srcs, sums, n_src, ln_w, ln_b, W, bias, hb, stats, b, C, L, O, &z, hb_part, stream);
 }
 
+// The options of a descriptor form, judged before every shape and limit rule of either entry point: kind 1 (BCE) | 2 (CE)
+static int crit_arg_check(int kind, const bmnas_criterion_t& crit) {
+  if (kind != BMNAS_CRIT_BCE && kind != BMNAS_CRIT_CE) return BMNAS_E_ARG;
+  if (!(crit.label_smoothing >= 0.f && crit.label_smoothing < 1.f)) return BMNAS_E_ARG;
+  if (crit.reduction != BMNAS_REDUCE_MEAN && crit.reduction != BMNAS_REDUCE_SUM) return BMNAS_E_ARG;
+  if (kind == BMNAS_CRIT_CE && crit.pos_weight) return BMNAS_E_ARG;
+  if (kind == BMNAS_CRIT_BCE && crit.label_smoothing != 0.f) return BMNAS_E_ARG;
+  return 0;
+}
+
 static int head_bwd_impl(const float* const* srcs, const float* const* sums, float* const* dsrcs, int n_src,
                          uint32_t accumulate_mask, const float* ln_w, const float* ln_b, const float* W,
                          const float* hb, const float* stats, int mode, const float* g, const float* gscale,
                          const void* labels, float* loss, float* part, int b, int C, int L, int O, float* scrub,
-                         int64_t scrub_n, const HeadLazy* lazy, float* loss_part, void* stream) {
+                         int64_t scrub_n, const HeadLazy* lazy, float* loss_part, const bmnas_criterion_t* crit,
+                         void* stream) {
   if (!dsrcs || !ln_w || !ln_b || !W || !hb || !stats || b < 0 || C < 1 || L < 1 || O < 1)
     return BMNAS_E_ARG;                          // (part may be NULL: no classifier / K7-affine gradients wanted)
   if (mode < 0 || mode > 2 || (mode == 0 && !g) || (mode != 0 && (!labels || !loss))) return BMNAS_E_ARG;
+  if (crit) {                                    // (the *_crit entry points have judged it already: crit_arg_check)
+    if (const int rc = crit_arg_check(mode, *crit)) return rc;
+  }
   if (scrub_n < 0 || (scrub_n > 0 && !scrub) || scrub_n % 4) return BMNAS_E_ARG;
   if (O > kMaxO) return BMNAS_E_LIMIT;
   if ((C * L) % 16) return BMNAS_E_SHAPE;
@@ -721,6 +840,10 @@ static int head_bwd_impl(const float* const* srcs, const float* const* sums, flo
   a.labels_i = mode == 2 ? (const long long*)labels : nullptr;
   a.loss = loss; a.loss_part = loss_part; a.part = part; a.scrub = scrub; a.scrub4 = scrub_n / 4;
   a.b = b; a.O = O; a.CL = C * L; a.D = n_src * C * L; a.n_src = n_src;
+  if (crit) {
+    a.cw = crit->weight; a.cpw = crit->pos_weight; a.ignore = crit->ignore_index; a.eps = crit->label_smoothing;
+    a.red = crit->reduction;
+  }
 #if (defined(BMNAS_BODY_PROBES) && BMNAS_BODY_PROBES) || defined(BMNAS_CLASS_PROBE)
   static const int probe = []() { const char* e = getenv("BMNAS_HEAD_PROBE"); return e ? atoi(e) : 0; }();
   a.probe = probe;
@@ -733,10 +856,16 @@ static int head_bwd_impl(const float* const* srcs, const float* const* sums, flo
   hipStream_t st = (hipStream_t)stream;
   HeadLazy z{};
   if (lazy) z = *lazy;
-#define HB2(OTv, SGv)                                                                                   \
+#define HB3(OTv, SGv, LZv)                                                                              \
   do {                                                                                                  \
-    if (lazy) hipLaunchKernelGGL((head_bwd_k<OTv, SGv, true>), grid, dim3(256), 0, st, a, z);           \
-    else hipLaunchKernelGGL((head_bwd_k<OTv, SGv, false>), grid, dim3(256), 0, st, a, z);               \
+    if (!crit) hipLaunchKernelGGL((head_bwd_k<OTv, SGv, LZv>), grid, dim3(256), 0, st, a, z);           \
+    else if (mode == 1) hipLaunchKernelGGL((head_bwd_k<OTv, SGv, LZv, 1>), grid, dim3(256), 0, st, a, z); \
+    else hipLaunchKernelGGL((head_bwd_k<OTv, SGv, LZv, 2>), grid, dim3(256), 0, st, a, z);              \
+  } while (0)
+#define HB2(OTv, SGv)              \
+  do {                             \
+    if (lazy) HB3(OTv, SGv, true); \
+    else HB3(OTv, SGv, false);     \
   } while (0)
 #define HB(OTv)               \
   do {                        \
@@ -746,6 +875,7 @@ static int head_bwd_impl(const float* const* srcs, const float* const* sums, flo
   if (OT <= 2) HB(2); else if (OT <= 4) HB(4); else if (OT <= 6) HB(6); else HB(8);
 #undef HB
 #undef HB2
+#undef HB3
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -756,14 +886,25 @@ extern "C" int bmnas_head_bwd(const float* const* srcs, const float* const* sums
                               const float* gscale, const void* labels, float* loss, float* part,
                               int b, int C, int L, int O, float* scrub, int64_t scrub_n, void* stream) {
   return head_bwd_impl(srcs, sums, dsrcs, n_src, accumulate_mask, ln_w, ln_b, W, hb, stats, mode, g, gscale, labels,
-                       loss, part, b, C, L, O, scrub, scrub_n, nullptr, nullptr, stream);
+                       loss, part, b, C, L, O, scrub, scrub_n, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int bmnas_head_bwd_lazy(const bmnas_lazy_ln_t* lazy, float* const* lnpart, float* const* dsrcs,
+extern "C" int bmnas_head_bwd_crit(const float* const* srcs, const float* const* sums, float* const* dsrcs,
                                    int n_src, uint32_t accumulate_mask, const float* ln_w, const float* ln_b,
-                                   const float* W, const float* hb, const float* stats, int mode, const float* g,
+                                   const float* W, const float* hb, const float* stats, int kind,
                                    const float* gscale, const void* labels, float* loss, float* part, int b, int C,
-                                   int L, int O, float* scrub, int64_t scrub_n, float* loss_part, void* stream) {
+                                   int L, int O, float* scrub, int64_t scrub_n, bmnas_criterion_t crit,
+                                   void* stream) {
+  if (const int rc = crit_arg_check(kind, crit)) return rc;
+  return head_bwd_impl(srcs, sums, dsrcs, n_src, accumulate_mask, ln_w, ln_b, W, hb, stats, kind, nullptr, gscale,
+                       labels, loss, part, b, C, L, O, scrub, scrub_n, nullptr, nullptr, &crit, stream);
+}
+
+static int head_bwd_lazy_impl(const bmnas_lazy_ln_t* lazy, float* const* lnpart, float* const* dsrcs, int n_src,
+                              uint32_t accumulate_mask, const float* ln_w, const float* ln_b, const float* W,
+                              const float* hb, const float* stats, int mode, const float* g, const float* gscale,
+                              const void* labels, float* loss, float* part, int b, int C, int L, int O, float* scrub,
+                              int64_t scrub_n, float* loss_part, const bmnas_criterion_t* crit, void* stream) {
   if (!lazy || !lnpart || n_src < 1) return BMNAS_E_ARG;
   if (n_src > kHeadSrc) return BMNAS_E_LIMIT;
   if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;             // (as the forward half: the sources are its family's)
@@ -776,7 +917,27 @@ extern "C" int bmnas_head_bwd_lazy(const bmnas_lazy_ln_t* lazy, float* const* ln
   }
   z.lq = -1; z.P = 0;
   return head_bwd_impl(srcs, nullptr, dsrcs, n_src, accumulate_mask, ln_w, ln_b, W, hb, stats, mode, g, gscale,
-                       labels, loss, part, b, C, L, O, scrub, scrub_n, &z, loss_part, stream);
+                       labels, loss, part, b, C, L, O, scrub, scrub_n, &z, loss_part, crit, stream);
+}
+
+extern "C" int bmnas_head_bwd_lazy(const bmnas_lazy_ln_t* lazy, float* const* lnpart, float* const* dsrcs,
+                                   int n_src, uint32_t accumulate_mask, const float* ln_w, const float* ln_b,
+                                   const float* W, const float* hb, const float* stats, int mode, const float* g,
+                                   const float* gscale, const void* labels, float* loss, float* part, int b, int C,
+                                   int L, int O, float* scrub, int64_t scrub_n, float* loss_part, void* stream) {
+  return head_bwd_lazy_impl(lazy, lnpart, dsrcs, n_src, accumulate_mask, ln_w, ln_b, W, hb, stats, mode, g, gscale,
+                            labels, loss, part, b, C, L, O, scrub, scrub_n, loss_part, nullptr, stream);
+}
+
+extern "C" int bmnas_head_bwd_lazy_crit(const bmnas_lazy_ln_t* lazy, float* const* lnpart, float* const* dsrcs,
+                                        int n_src, uint32_t accumulate_mask, const float* ln_w, const float* ln_b,
+                                        const float* W, const float* hb, const float* stats, int kind,
+                                        const float* gscale, const void* labels, float* loss, float* part, int b,
+                                        int C, int L, int O, float* scrub, int64_t scrub_n, float* loss_part,
+                                        bmnas_criterion_t crit, void* stream) {
+  if (const int rc = crit_arg_check(kind, crit)) return rc;
+  return head_bwd_lazy_impl(lazy, lnpart, dsrcs, n_src, accumulate_mask, ln_w, ln_b, W, hb, stats, kind, nullptr,
+                            gscale, labels, loss, part, b, C, L, O, scrub, scrub_n, loss_part, &crit, stream);
 }
 
 extern "C" int bmnas_sum_chunks(const float* part, float* out, int n_chunk, int64_t n, void* stream) {

@@ -294,6 +294,134 @@ __global__ __launch_bounds__(256) void mean_k(const float* __restrict__ v, float
   if (threadIdx.x == 0) out[0] = t / (float)n;
 }
 
+// ---- the same criteria with per-class weights, label smoothing, ignore_index and reduction mean | sum (the formulas:
+// bmnas_hip.h, bmnas_criterion_t).  Kernels of their own: the bare forms above keep their code and their numbers.
+struct Crit {
+  const float* w;      // (O) or NULL = ones
+  const float* pw;     // (O) or NULL = ones (BCE)
+  long long ignore;
+  float eps;
+  int red;             // 0 mean, 1 sum
+};
+
+__global__ __launch_bounds__(1024) void bce_logits_w_k(const float* __restrict__ z, const float* __restrict__ y, Crit c,
+                                                       float* __restrict__ loss, float* __restrict__ dz, int n, int O) {
+  __shared__ float red[16];
+  float s = 0.f;
+  const float inv = c.red == 0 ? 1.f / (float)n : 1.f;
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    const float zi = z[i], yi = y[i];
+    const int o = i % O;
+    const float w = c.w != nullptr ? c.w[o] : 1.f;
+    const float cp = 1.f + ((c.pw != nullptr ? c.pw[o] : 1.f) - 1.f) * yi;
+    s += w * ((1.f - yi) * zi + cp * (log1pf(expf(-fabsf(zi))) + fmaxf(-zi, 0.f)));
+    if (dz != nullptr) dz[i] = w * ((1.f - yi) - cp / (1.f + expf(zi))) * inv;     // 1 - sigmoid(z) = 1 / (1 + e^z)
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int w = 0; w < 16; ++w) t += red[w];
+    loss[0] = t * inv;
+  }
+}
+
+// a label that counts, else -1 (ignore_index, or outside [0, O): never an index)
+__device__ __forceinline__ int ce_label(const int64_t* __restrict__ label, int m, const Crit& c, int O) {
+  const long long l = label[m];
+  return (l != c.ignore && l >= 0 && l < (long long)O) ? (int)l : -1;
+}
+
+// den of the mean = sum of w[label] over the rows that count, by the 256 threads of a workgroup in a fixed order
+// (thread-strided partial sums, wave butterflies, four LDS slots); every thread gets it.  sum: 1.
+__device__ __forceinline__ float ce_den(const int64_t* __restrict__ label, const Crit& c, int b, int O, float* red) {
+  if (c.red != 0) return 1.f;
+  float t = 0.f;
+  for (int i = threadIdx.x; i < b; i += 256) {
+    const int l = ce_label(label, i, c, O);
+    const float wl = c.w != nullptr ? c.w[l >= 0 ? l : 0] : 1.f;
+    t += l >= 0 ? wl : 0.f;
+  }
+  return block_sum256(t, red);
+}
+
+// One row by one wave: returns the row's un-normalised loss (every lane), writes its dz row scaled by 1 / den.
+__device__ __forceinline__ float ce_w_row(const float* __restrict__ zr, float* __restrict__ dzr, int lab, const Crit& c,
+                                          int O, float den_inv, int lane) {
+  float mx = -INFINITY;
+  for (int o = lane; o < O; o += 64) mx = fmaxf(mx, zr[o]);
+  mx = wave_max(mx);
+  float den = 0.f, wsum = 0.f;
+  for (int o = lane; o < O; o += 64) {
+    den += expf(zr[o] - mx);
+    wsum += c.w != nullptr ? c.w[o] : 1.f;
+  }
+  den = wave_sum(den);
+  wsum = wave_sum(wsum);
+  const float lse = mx + logf(den);
+  float sm = 0.f;
+  for (int o = lane; o < O; o += 64) sm += (c.w != nullptr ? c.w[o] : 1.f) * (lse - zr[o]);
+  sm = wave_sum(sm);
+  const bool keep = lab >= 0;
+  const float wy = keep ? (c.w != nullptr ? c.w[lab] : 1.f) : 0.f;
+  const float ny = keep ? lse - zr[lab] : 0.f;
+  const float a1 = (1.f - c.eps) * wy, a2 = c.eps / (float)O;
+  if (dzr != nullptr)
+    for (int o = lane; o < O; o += 64) {
+      const float p = expf(zr[o] - mx) / den;
+      const float wo = c.w != nullptr ? c.w[o] : 1.f;
+      dzr[o] = keep ? (a1 * (p - (o == lab ? 1.f : 0.f)) + a2 * (wsum * p - wo)) * den_inv : 0.f;
+    }
+  return keep ? a1 * ny + a2 * sm : 0.f;
+}
+
+// b <= 256 as ONE workgroup (ce_small_k's shape)
+__global__ __launch_bounds__(256) void ce_w_small_k(const float* __restrict__ z, const int64_t* __restrict__ label,
+                                                    Crit c, float* __restrict__ row_loss, float* __restrict__ dz,
+                                                    float* __restrict__ loss, int b, int O) {
+  __shared__ float red[4], red2[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float den = ce_den(label, c, b, O, red);
+  const float den_inv = 1.f / den;
+  float acc = 0.f;
+  for (int m = wave; m < b; m += 4) {
+    const float rl = ce_w_row(z + (int64_t)m * O, dz != nullptr ? dz + (int64_t)m * O : nullptr,
+                              ce_label(label, m, c, O), c, O, den_inv, lane);
+    if (lane == 0) {
+      row_loss[m] = rl;
+      acc += rl;
+    }
+  }
+  if (lane == 0) red2[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[0] = ((red2[0] + red2[1]) + (red2[2] + red2[3])) / den;
+}
+
+// above: one wave per row, every workgroup forms den itself; ce_w_finish_k sums the rows and divides
+__global__ __launch_bounds__(256) void ce_w_rows_k(const float* __restrict__ z, const int64_t* __restrict__ label,
+                                                   Crit c, float* __restrict__ row_loss, float* __restrict__ dz, int b,
+                                                   int O) {
+  __shared__ float red[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float den = dz != nullptr ? ce_den(label, c, b, O, red) : 1.f;      // (uniform)
+  const int m = blockIdx.x * 4 + wave;
+  if (m >= b) return;
+  const float rl = ce_w_row(z + (int64_t)m * O, dz != nullptr ? dz + (int64_t)m * O : nullptr,
+                            ce_label(label, m, c, O), c, O, 1.f / den, lane);
+  if (lane == 0) row_loss[m] = rl;
+}
+
+__global__ __launch_bounds__(256) void ce_w_finish_k(const float* __restrict__ v, const int64_t* __restrict__ label,
+                                                     Crit c, float* __restrict__ out, int b, int O) {
+  __shared__ float red[4], red2[4];
+  const float den = ce_den(label, c, b, O, red);
+  float s = 0.f;
+  for (int i = threadIdx.x; i < b; i += 256) s += v[i];
+  const float t = block_sum256(s, red2);
+  if (threadIdx.x == 0) out[0] = t / den;
+}
+
 }  // namespace
 
 #define LIN_DISPATCH(TJ, CALL)      \
@@ -370,6 +498,44 @@ extern "C" int bmnas_cross_entropy(const float* z, const int64_t* label, float* 
   hipLaunchKernelGGL(ce_rows_k, dim3((b + 3) / 4), dim3(256), 0, st, z, label, row_loss, dz, b, O);
   BMNAS_CHECK_LAUNCH();
   hipLaunchKernelGGL(mean_k, dim3(1), dim3(256), 0, st, row_loss, loss, b);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+// BMNAS_E_ARG first (the options), then nothing else to refuse: any rows, O >= 1
+static int crit_check(const bmnas_criterion_t& crit, int kind) {
+  if (!(crit.label_smoothing >= 0.f && crit.label_smoothing < 1.f)) return BMNAS_E_ARG;
+  if (crit.reduction != BMNAS_REDUCE_MEAN && crit.reduction != BMNAS_REDUCE_SUM) return BMNAS_E_ARG;
+  if (kind == BMNAS_CRIT_CE && crit.pos_weight) return BMNAS_E_ARG;
+  if (kind == BMNAS_CRIT_BCE && crit.label_smoothing != 0.f) return BMNAS_E_ARG;
+  return 0;
+}
+
+extern "C" int bmnas_bce_logits_crit(const float* z, const float* y, bmnas_criterion_t crit, float* loss, float* dz,
+                                     int rows, int O, void* stream) {
+  if (!z || !y || !loss || rows < 1 || O < 1) return BMNAS_E_ARG;
+  if (const int rc = crit_check(crit, BMNAS_CRIT_BCE)) return rc;
+  if ((int64_t)rows * O > (int64_t)1 << 30) return BMNAS_E_LIMIT;
+  const Crit c{crit.weight, crit.pos_weight, (long long)crit.ignore_index, crit.label_smoothing, crit.reduction};
+  hipLaunchKernelGGL(bce_logits_w_k, dim3(1), dim3(1024), 0, (hipStream_t)stream, z, y, c, loss, dz, rows * O, O);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_cross_entropy_crit(const float* z, const int64_t* label, bmnas_criterion_t crit, float* loss,
+                                        float* dz, float* row_loss, int b, int O, void* stream) {
+  if (!z || !label || !loss || !row_loss || b < 1 || O < 1) return BMNAS_E_ARG;
+  if (const int rc = crit_check(crit, BMNAS_CRIT_CE)) return rc;
+  const Crit c{crit.weight, nullptr, (long long)crit.ignore_index, crit.label_smoothing, crit.reduction};
+  hipStream_t st = (hipStream_t)stream;
+  if (b <= 256) {
+    hipLaunchKernelGGL(ce_w_small_k, dim3(1), dim3(256), 0, st, z, label, c, row_loss, dz, loss, b, O);
+    BMNAS_CHECK_LAUNCH();
+    return 0;
+  }
+  hipLaunchKernelGGL(ce_w_rows_k, dim3((b + 3) / 4), dim3(256), 0, st, z, label, c, row_loss, dz, b, O);
+  BMNAS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ce_w_finish_k, dim3(1), dim3(256), 0, st, row_loss, label, c, loss, b, O);
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

@@ -30,6 +30,33 @@ def data_parallel_world(args=None):
     return bdist.env_world()
 
 
+def _class_vector(args, name, device):
+    """args.<name> as an fp32 tensor of num_outputs entries, or None when the argument set has none."""
+    values = getattr(args, name, None)
+    if values is None:
+        return None
+    t = torch.as_tensor([float(v) for v in values], dtype=torch.float32, device=device)
+    if t.numel() != args.num_outputs:
+        raise ValueError(f'args.{name} has {t.numel()} entries, the task has {args.num_outputs} outputs')
+    return t
+
+
+def make_criterion(kind, args, device=None):
+    """The search drivers' criterion: kind 'bce' (MM-IMDB, reference mmimdb_darts_searchable.py:22) or 'ce' (NTU, Ego).
+    The reference's argument sets give the bare mean criterion, exactly as before.  Optional, all read with getattr:
+      args.pos_weight       'bce': num_outputs floats, the weight of each genre's positive term
+      args.class_weight     num_outputs floats, the per-class rescaling weight of either criterion
+      args.label_smoothing  'ce': a float in [0, 1)
+    The weight tensors are buffers of the criterion, which the hypernet holds as a submodule: they move with
+    model.to(device) and are read by address by the gfx950 kernels (bmnas.nn.criterion_route)."""
+    weight = _class_vector(args, 'class_weight', device)
+    if kind == 'bce':
+        return bnn.BCEWithLogitsLoss(weight=weight, pos_weight=_class_vector(args, 'pos_weight', device))
+    if kind == 'ce':
+        return bnn.CrossEntropyLoss(weight=weight, label_smoothing=float(getattr(args, 'label_smoothing', 0.0)))
+    raise ValueError(f'criterion kind {kind!r}')
+
+
 class HyperNetBase(nn.Module):
     """backbones (set by the subclass) -> reshape_layers -> fusion_net -> central_classifier.
     Attribute names are the reference's: trainers reach into .reshape_layers / .fusion_net."""

@@ -800,6 +800,54 @@ int bmnas_bce_logits(const float* z, const float* y, float* loss, float* dz, int
 int bmnas_cross_entropy(const float* z, const int64_t* label, float* loss, float* dz,
                         float* row_loss, int b, int O, void* stream);
 
+/* ---- class-weighted / label-smoothed criteria -------------------------------------------------
+ * The options of torch.nn.BCEWithLogitsLoss / CrossEntropyLoss beyond the bare mean form, passed BY VALUE.  The
+ * pointers are device arrays of O floats read when the launch runs (a captured step follows in-place edits); NULL
+ * means ones.
+ *   BCE  (BMNAS_CRIT_BCE; z, y of shape (rows, O)):   c = 1 + (pos_weight - 1) y
+ *        l  = weight [(1 - y) z + c (log1p(exp(-|z|)) + max(-z, 0))]
+ *        dz = weight [(1 - y) - c (1 - sigmoid(z))]            mean: / (rows O);  sum: as is
+ *        label_smoothing must be 0 and ignore_index is not read.
+ *   CE   (BMNAS_CRIT_CE; int64 class labels (b)):   keep_i = label_i != ignore_index (a label outside [0, O) counts
+ *        as ignored too and is never used as an index), p = softmax(z_i), W = sum_c weight_c, e = label_smoothing
+ *        loss  = sum_i keep_i [(1 - e) weight[y_i] (-log p[y_i]) + (e / O) sum_c weight_c (-log p_c)] / den
+ *        dz_ic = keep_i [(1 - e) weight[y_i] (p_c - [c == y_i]) + (e / O) (W p_c - weight_c)] / den
+ *        den   = sum_i keep_i weight[y_i] (mean) | 1 (sum).  Ignored rows: dz exactly 0.  No row counts under mean:
+ *        loss NaN, dz 0 (as torch).  den is formed inside the launch by every workgroup in a fixed order.
+ *        pos_weight must be NULL.
+ * Refusals: BMNAS_E_ARG (label_smoothing outside [0, 1) or non-zero for BCE, reduction not 0 / 1, pos_weight for
+ * CE, kind not 1 / 2, null pointers), then the shape and limit rules of the entry point's plain form. */
+#define BMNAS_CRIT_BCE 1
+#define BMNAS_CRIT_CE 2
+#define BMNAS_REDUCE_MEAN 0
+#define BMNAS_REDUCE_SUM 1
+typedef struct {
+  const float* weight;       /* (O) per-class rescaling weight, nullable */
+  const float* pos_weight;   /* (O) BCE weight of the positive term, nullable */
+  float label_smoothing;     /* CE: in [0, 1) */
+  int64_t ignore_index;      /* CE */
+  int reduction;             /* BMNAS_REDUCE_MEAN | BMNAS_REDUCE_SUM */
+} bmnas_criterion_t;
+/* One launch.  loss[0] and, if dz != NULL, dz (rows, O). */
+int bmnas_bce_logits_crit(const float* z, const float* y, bmnas_criterion_t crit, float* loss, float* dz, int rows,
+                          int O, void* stream);
+/* One launch for b <= 256, two above; row_loss: (b) scratch. */
+int bmnas_cross_entropy_crit(const float* z, const int64_t* label, bmnas_criterion_t crit, float* loss, float* dz,
+                             float* row_loss, int b, int O, void* stream);
+/* bmnas_head_bwd / bmnas_head_bwd_lazy modes 1 / 2 with the descriptor: kind = BMNAS_CRIT_BCE (float labels (b, O))
+ * | BMNAS_CRIT_CE (int64 labels (b)); *loss += the loss (or loss_part[chunk] = the chunk's share).  Every other
+ * argument as in the plain forms. */
+int bmnas_head_bwd_crit(const float* const* srcs, const float* const* sums, float* const* dsrcs, int n_src,
+                        uint32_t accumulate_mask, const float* ln_w, const float* ln_b, const float* W,
+                        const float* hb, const float* stats, int kind, const float* gscale, const void* labels,
+                        float* loss, float* part, int b, int C, int L, int O, float* scrub, int64_t scrub_n,
+                        bmnas_criterion_t crit, void* stream);
+int bmnas_head_bwd_lazy_crit(const bmnas_lazy_ln_t* lazy, float* const* lnpart, float* const* dsrcs, int n_src,
+                             uint32_t accumulate_mask, const float* ln_w, const float* ln_b, const float* W,
+                             const float* hb, const float* stats, int kind, const float* gscale,
+                             const void* labels, float* loss, float* part, int b, int C, int L, int O,
+                             float* scrub, int64_t scrub_n, float* loss_part, bmnas_criterion_t crit, void* stream);
+
 /* ---- multi-tensor Adam (row f2) ----------------------------------------------------------
  * One launch applies torch.optim.Adam's update (amsgrad off; L2 weight decay added to the
  * gradient) to every tensor of an optimizer — the w-step at train_searchable/mmimdb.py:101 and the
