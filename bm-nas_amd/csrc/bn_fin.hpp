@@ -51,7 +51,8 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
     // between the sums and the affine parameters: two dependent round trips at the start of every consumer
     const bool tr = f.training != 0;
     const bool has_cb = tr && f.conv_bias != nullptr, need_run = upd || !tr;
-    const int mv = m0 + 8 <= M ? m0 : (M >= 8 ? M - 8 : 0);    // (dummy reads stay inside bn_w)
+    const int mv = m0 + 8 <= M ? m0 : (M >= 8 ? M - 8 : 0);    // (dummy reads stay inside bn_w: eight floats from
+    const int second = (tr || M >= 8) ? 1 : 0;                 //  mv, or the four of M == 4 twice)
     const float4* st = tr ? reinterpret_cast<const float4*>(f.stat + 2 * m0)
                           : reinterpret_cast<const float4*>(f.bn_w + mv);
     const int64_t sstr = tr ? (int64_t)(M / 2) : 0;
@@ -60,7 +61,7 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
     for (int k = 0; k < kMaxShards; ++k) {                     // clamped shard index: no predicated loads
       const float4* p = st + (int64_t)(k < f.shards ? k : 0) * sstr;
       v[k][0] = p[0];                                          // (sum, sumsq) of channels m0, m0 + 1
-      v[k][1] = p[1];                                          //              of channels m0 + 2, m0 + 3
+      v[k][1] = p[second];                                     //              of channels m0 + 2, m0 + 3
     }
     const float4 w4 = ld4(f.bn_w + m0), b4 = ld4(f.bn_b + m0);
     float4 cb4 = ld4((has_cb ? f.conv_bias : f.bn_w) + m0);
@@ -68,7 +69,7 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
     float4 rv4 = ld4((need_run ? f.running_var : f.bn_w) + m0);
     long long nb = 0;
     const bool bump = wr && f.training && f.nbt != nullptr && m0 < f.n_nbt;
-    if (bump) nb = f.nbt[m0];                                  // (n_nbt <= 4: the counters of thread 0)
+    if (bump) nb = f.nbt[m0];                                  // (counters 4t .. 4t + 3 of thread t: n_nbt <= M)
     if (!has_cb) cb4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!need_run) {
       rm4 = make_float4(0.f, 0.f, 0.f, 0.f);

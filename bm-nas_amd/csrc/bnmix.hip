@@ -1485,7 +1485,8 @@ extern "C" int bmnas_bn_glu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin,
                                 bmnas_dropout_t drop, void* stream) {
   if (!U || !chan || !out || b < 0 || C < 1) return BMNAS_E_ARG;
   if (L % 4 || L > 16) return BMNAS_E_SHAPE;
-  if (2 * C > 4096) return BMNAS_E_LIMIT;                 // scale | shift of every channel sit in LDS
+  // scale | shift of every channel sit in LDS, written four adjacent channels per thread (bn_fin_fill)
+  if (2 * C > 4096 || (2 * C) % 4) return BMNAS_E_LIMIT;
   BnFin f;
   if (int e = to_fin(fin, &f)) return e;
   if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
@@ -1517,7 +1518,8 @@ static int bn_act_fwd(Kern kern, const float* U, float* chan, bmnas_bn_fin_t fin
                       bmnas_dropout_t drop, void* stream) {
   if (!U || !chan || !out || b < 0 || M < 1) return BMNAS_E_ARG;
   if (L % 4 || L > 16) return BMNAS_E_SHAPE;
-  if (M > 4096) return BMNAS_E_LIMIT;                    // scale | shift of every channel sit in LDS
+  // scale | shift of every channel sit in LDS, written four adjacent channels per thread (bn_fin_fill)
+  if (M > 4096 || M % 4) return BMNAS_E_LIMIT;
   BnFin f;
   if (int e = to_fin(fin, &f)) return e;
   if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;

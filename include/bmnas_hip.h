@@ -449,7 +449,10 @@ int bmnas_bn_glu_bwd(const float* g, const float* U, const float* chan, float* d
                      int b, int C, int L, bmnas_dropout_t drop, void* stream);
 
 /* ---- BN + ReLU + dropout: ConcatFC tail (node_operations.py:53-55) and the NodeCell
- * out_conv tail (node_search.py:60-64) ---------------------------------------------------- */
+ * out_conv tail (node_search.py:60-64) ----------------------------------------------------
+ * Forward: M % 4 == 0 and M <= 4096 (2C for bmnas_bn_glu_fwd), BMNAS_E_LIMIT otherwise, like
+ * bmnas_bn_relu_fwd_group: scale | shift of every channel sit in LDS, four adjacent channels per thread.
+ * fin.n_nbt counters are advanced as far as n_nbt <= M. */
 int bmnas_bn_relu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b, int M, int L,
                       bmnas_dropout_t drop, void* stream);
 int bmnas_bn_relu_bwd(const float* g, const float* U, const float* chan, float* dV, float* bn_grad,

@@ -63,6 +63,42 @@ def build_found_net(cfg, genotype, seed, mode):
     return net
 
 
+GUARD = 64                                         # sentinel elements on each side of every output (float4 aligned)
+
+
+class Pool:
+    """Outputs of a kernel-level test: each a view into its own NaN buffer with GUARD floats before and after it
+    (int64 outputs: a buffer of one sentinel value).  check(): the guards are bit-unchanged."""
+
+    def __init__(self):
+        self.bufs = []
+
+    def new(self, *shape, base=None):
+        n = 1
+        for s in shape:
+            n *= int(s)
+        buf = torch.full((n + 2 * GUARD,), float('nan'), device=dev())
+        self.bufs.append((buf, n, buf[:GUARD].view(torch.int32).clone()))
+        view = buf[GUARD:GUARD + n].view(*shape)
+        if base is not None:
+            view.copy_(base)
+        return view
+
+    def new_i64(self, base):
+        n = int(base.numel())
+        buf = torch.full((n + 2 * GUARD,), -0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=dev())
+        self.bufs.append((buf, n, buf[:GUARD].view(torch.int32).clone()))
+        view = buf[GUARD:GUARD + n]
+        view.copy_(base)
+        return view
+
+    def check(self):
+        torch.cuda.synchronize()
+        for buf, n, bits in self.bufs:
+            assert torch.equal(buf[:GUARD].view(torch.int32), bits) and \
+                torch.equal(buf[GUARD + n:].view(torch.int32), bits), f'a guard of a {n}-element output was written'
+
+
 def scale_tol(want, rel=1e-4, floor=1e-6):
     """absolute tolerance = rel * (largest magnitude of the expected tensor)"""
     w = np.asarray(want, dtype=np.float64)

@@ -104,14 +104,13 @@ import pytest
 import torch
 
 import conv_ref as cr
-from gpu_util import assert_close_scaled, dev
+from gpu_util import GUARD, Pool as _Pool, assert_close_scaled, dev
 
 pytestmark = pytest.mark.gpu
 
 # the family expectations describe the DEFAULT dispatch (tests/test_dispatch_gpu.py does the same)
 _FORCED = [k for k in ('BMNAS_CONV_PIPE', 'BMNAS_FUSE_ATTN_GEMM', 'BMNAS_FUSE_BWD_PAIR')
            if os.environ.get(k) is not None]
-GUARD = 64                                         # sentinel floats on each side of every output (float4 aligned)
 NAN = float('nan')
 R_U, R_DATA, R_W, R_SUM, R_M2 = 2e-5, 3e-5, 5e-5, 5e-5, 2e-4
 
@@ -127,30 +126,6 @@ def _rand(g, *shape):
 def _b(ng, L):
     """the ragged batch of ng n-groups: one sample in the last group (L 16: one sample is a whole group)"""
     return (ng - 1) * (16 // L) + 1
-
-
-class _Pool:
-    """Outputs of a test: each a view into its own NaN buffer with GUARD floats before and after it."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def new(self, *shape, base=None):
-        n = 1
-        for s in shape:
-            n *= int(s)
-        buf = torch.full((n + 2 * GUARD,), NAN, device=dev())
-        self.bufs.append((buf, n, buf[:GUARD].view(torch.int32).clone()))
-        view = buf[GUARD:GUARD + n].view(*shape)
-        if base is not None:
-            view.copy_(base)
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for buf, n, bits in self.bufs:
-            assert torch.equal(buf[:GUARD].view(torch.int32), bits) and \
-                torch.equal(buf[GUARD + n:].view(torch.int32), bits), f'a guard of a {n}-float output was written'
 
 
 def _served(expect, forbid=()):
