@@ -250,6 +250,10 @@ SIGNATURES = {
     'bmnas_cross_entropy': ([_P, _P, _P, _P, _P, _I, _I, _P], _I),
     'bmnas_adam_chunk_elems': ([], _I),
     'bmnas_adam_multi': ([_P, _P, _I, _P, _P], _I),
+    'bmnas_grad_norm_parts': ([], _I),
+    'bmnas_grad_sqnorm_multi': ([_P, _P, _I, _P, _P], _I),
+    'bmnas_adam_multi_clip': ([_P, _P, _I, _P, _P, _I, _P, _P, _P], _I),
+    'bmnas_grad_scale_multi': ([_P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_copy_batch_max': ([], _I),
     'bmnas_copy_blob_max': ([], _I),
     'bmnas_copy_batch': ([_PP, _PP, C.POINTER(C.c_longlong), _I, _P, _P, _I, _P, C.c_ulonglong, _P], _I),
@@ -1107,6 +1111,30 @@ def adam_multi(table, chunks, n_chunks, hyp):
     hyp: float32 device (rows, 8)."""
     _check(load().bmnas_adam_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), _stream()),
            'adam_multi')
+
+
+def grad_norm_parts():
+    return load().bmnas_grad_norm_parts()
+
+
+def grad_sqnorm_multi(table, chunks, n_chunks, partials):
+    """One sum of grad^2 per workgroup of the fixed grid into partials[: min(n_chunks, grad_norm_parts())] (fp32 device);
+    table / chunks as for adam_multi."""
+    _check(load().bmnas_grad_sqnorm_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, _ptr(partials), _stream()),
+           'grad_sqnorm_multi')
+
+
+def adam_multi_clip(table, chunks, n_chunks, hyp, partials, n_parts, clip, norm_out):
+    """adam_multi on gradients scaled by min(1, clip / (sqrt(sum(partials[:n_parts])) + 1e-6)); clip, norm_out: fp32 device
+    scalars (max_norm in, pre-clip norm out).  `.grad` is NOT written."""
+    _check(load().bmnas_adam_multi_clip(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), _ptr(partials),
+                                        n_parts, clip.data_ptr(), norm_out.data_ptr(), _stream()), 'adam_multi_clip')
+
+
+def grad_scale_multi(table, chunks, n_chunks, partials, n_parts, clip, norm_out):
+    """grad *= the same coefficient, in place."""
+    _check(load().bmnas_grad_scale_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, _ptr(partials), n_parts,
+                                         clip.data_ptr(), norm_out.data_ptr(), _stream()), 'grad_scale_multi')
 
 
 def copy_blob_max():

@@ -10,6 +10,12 @@ with the tensor descriptors into ONE pinned staging buffer, copied to the device
 H2D copy, and one `bmnas_adam_multi` launch updates every tensor (torch's foreach path: ~10
 launches per parameter group).  Because all per-step values travel through the staging buffer,
 a step captured in a hipGraph replays correctly: `prepare_replay()` before each replay.
+
+`Adam(..., max_grad_norm=c)` clips the global L2 norm of the gradients inside the step — what
+`torch.nn.utils.clip_grad_norm_(all parameters, c)` between backward() and step() computes (DARTS'
+`--grad_clip`), captured steps included: one norm launch (`bmnas_grad_sqnorm_multi`) in front of the
+clipped update (`bmnas_adam_multi_clip`).  The update scales each gradient in registers: `.grad` is
+NOT written and keeps the unclipped values.  `clip_grad_norm_` below is the stand-alone, in-place form.
 """
 import math
 
@@ -25,13 +31,44 @@ assert _DESC.itemsize == 48
 
 
 class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
+                 max_grad_norm=None):
+        """max_grad_norm (None or a positive float): clip the global L2 norm over every parameter of the optimizer that has
+        a gradient, all groups together, before the update.  An attribute, not a `param_groups` entry (state_dict() stays
+        that of torch.optim.Adam); it may be edited between steps and replays — it travels with the per-step scalars —
+        but not switched between None and a value under a captured plan.  `.grad` is left UNCLIPPED: the scaling happens
+        in the update's registers.  `last_grad_norm` / `grad_norms` hold the pre-clip norm(s) on the device."""
         if amsgrad:
             raise lib.BmnasError('bmnas.optim.Adam: amsgrad is not on the reference path')
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
+        self.max_grad_norm = max_grad_norm
+        self._clip_value()
         self._plan = None
         self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
         self._touch = 0          # bumped by everything that may re-point .grad or move the step counts outside a replay
+
+    def _clip_value(self):
+        """max_grad_norm as a float (validated), or None."""
+        c = self.max_grad_norm
+        if c is None:
+            return None
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not c > 0:
+            raise lib.BmnasError(f'bmnas.optim.Adam: max_grad_norm must be None or a positive float, got {c!r}')
+        return float(c)
+
+    @property
+    def grad_norms(self):
+        """The pre-clip gradient norm of every step of the current plan's most recent launch / replay: fp32 device tensor
+        of `slots` entries (1 for an eager step, k for a k-step captured plan); None without clipping.  Reading it
+        queues no synchronisation of its own."""
+        pl = self._plan
+        return pl['norms'] if pl is not None and pl.get('clip') else None
+
+    @property
+    def last_grad_norm(self):
+        """0-dim fp32 device tensor: the pre-clip norm of the most recent step (a view of grad_norms' last entry)."""
+        n = self.grad_norms
+        return None if n is None else n[-1]
 
     # ------------------------------------------------------------------ plan
     def _active(self):
@@ -75,7 +112,10 @@ class Adam(torch.optim.Adam):
             row_of.append(row_idx[key])
             chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
         # (scalar slots packed back to back — 32 bytes per row —: the whole region travels by value in poke mode)
-        hyp_slot = len(rows) * 32
+        # clipping: max_grad_norm rides behind each slot's rows (16 bytes: the next slot's rows stay 16-byte aligned)
+        clip = self._clip_value() is not None
+        row_bytes = len(rows) * 32
+        hyp_slot = row_bytes + (16 if clip else 0)
         hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
         tab_slot = len(active) * _DESC.itemsize
         nbytes = hyp_bytes + slots * tab_slot
@@ -88,7 +128,7 @@ class Adam(torch.optim.Adam):
             tab['numel'] = [p.numel() for p, _ in active]
             tab['hyp_row'] = row_of
         devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        hyps = [host[i * hyp_slot:(i + 1) * hyp_slot].view(np.float32).reshape(len(rows), 8) for i in range(slots)]
+        hyps = [host[i * hyp_slot:i * hyp_slot + row_bytes].view(np.float32).reshape(len(rows), 8) for i in range(slots)]
         self._plan = dict(ids=tuple(id(p) for p, _ in active), active=active, row_of=row_of, gen=self._gen,
                           groups=[gi for gi, _ in rows], count=[t for _, t in rows],
                           pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * hyp_slot], tab=tabs[0], tabs=tabs,
@@ -98,7 +138,17 @@ class Adam(torch.optim.Adam):
                           dev_tabs=[devbuf[hyp_bytes + i * tab_slot:hyp_bytes + (i + 1) * tab_slot]
                                     for i in range(slots)],
                           chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev),
-                          n_chunks=len(chunks), slots=slots, cap_slot=0)
+                          n_chunks=len(chunks), slots=slots, cap_slot=0, clip=clip)
+        if clip:
+            # the norm launch's partials, the max_grad_norm scalars (host + device view) and the norm outputs belong to the
+            # plan: a captured plan's graph reads and writes these addresses for good
+            parts = lib.grad_norm_parts()
+            self._plan.update(
+                n_parts=min(len(chunks), parts),
+                partials=[torch.empty(parts, dtype=torch.float32, device=dev) for _ in range(slots)],
+                clips=[host[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4].view(np.float32) for i in range(slots)],
+                dev_clips=[devbuf[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4] for i in range(slots)],
+                norms=torch.zeros(slots, dtype=torch.float32, device=dev))
 
     def _stage(self, active):
         """Advance the step counts; write this step's scalars and pointers into the staging buffer."""
@@ -118,7 +168,12 @@ class Adam(torch.optim.Adam):
         pl = self._plan
         if not pl.get('poke') and slot == 0:
             pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
-        lib.adam_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot])
+        if pl['clip']:
+            lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
+            lib.adam_multi_clip(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot],
+                                pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
+        else:
+            lib.adam_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot])
 
     def wait_staging(self):
         """Block until the last launch has consumed the pinned staging buffer (the host may run
@@ -161,10 +216,11 @@ class Adam(torch.optim.Adam):
             self._plan['cap_slot'] = slot + 1
             return loss
         ids = tuple(id(p) for p, _ in active)
-        if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids:
+        clip = self.max_grad_norm is not None
+        if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids or self._plan['clip'] != clip:
             # never stage an eager step through a captured plan: its graph re-reads those buffers
             eager = getattr(self, '_eager_plan', None)
-            if eager is not None and eager['ids'] == ids:
+            if eager is not None and eager['ids'] == ids and eager['clip'] == clip:
                 self._switch(eager)
             else:
                 self._build(active)
@@ -307,6 +363,12 @@ class Adam(torch.optim.Adam):
         first, each with the learning rates its step runs with (the scheduler moves them between two calls)."""
         pl = self._plan
         h = pl['hyps'][slot]
+        c = self._clip_value()
+        if (c is not None) != pl['clip']:
+            raise lib.BmnasError('bmnas.optim.Adam: max_grad_norm was switched between None and a value under a plan built '
+                                 'for the other (a captured step holds the launches of one of them); re-capture the graph')
+        if c is not None:
+            pl['clips'][slot][0] = c
         for r, gi in enumerate(pl['groups']):
             g = self.param_groups[gi]
             pl['count'][r] += 1.0
@@ -321,3 +383,49 @@ class Adam(torch.optim.Adam):
         pl = self._plan
         return [float(-pl['hyps'][slot][r][0]) * (1 - self.param_groups[gi]['betas'][0] ** pl['count'][r])
                 for r, gi in enumerate(pl['groups'])]
+
+
+_CLIP_CACHE = {}
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ in two launches for fp32 gradients on one GPU: the multi-tensor norm
+    (`bmnas_grad_sqnorm_multi`) and an in-place `grad *= min(1, max_norm / (norm + 1e-6))` (`bmnas_grad_scale_multi`).
+    -> the pre-clip norm as a 0-dim device tensor (no synchronisation).  Eager only: inside a stream capture it raises —
+    `Adam(max_grad_norm=...)` is how a captured step clips.  CPU tensors, other dtypes, `norm_type != 2` and
+    `error_if_nonfinite=True` go to torch's function (its behaviour is the contract there)."""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    parameters = list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    ours = (len(grads) > 0 and float(norm_type) == 2.0 and not error_if_nonfinite and
+            all(g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == grads[0].device
+                for g in grads))
+    if not ours:
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=norm_type,
+                                              error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    if torch.cuda.is_current_stream_capturing():
+        raise lib.BmnasError('bmnas.optim.clip_grad_norm_ is eager only (it stages a descriptor table per call); inside a '
+                             'captured step clip with bmnas.optim.Adam(max_grad_norm=...)')
+    dev = grads[0].device
+    key = (dev, float(max_norm), tuple((g.data_ptr(), g.numel()) for g in grads))
+    ent = _CLIP_CACHE.get('last')
+    if ent is None or ent['key'] != key:
+        E = lib.adam_chunk_elems()
+        tab = np.zeros(len(grads), dtype=_DESC)
+        tab['grad'] = [g.data_ptr() for g in grads]
+        tab['numel'] = [g.numel() for g in grads]
+        chunks = [(i, c) for i, g in enumerate(grads) for c in range((g.numel() + E - 1) // E)]
+        host = np.concatenate([np.array([max_norm, 0, 0, 0], dtype=np.float32).view(np.uint8), tab.view(np.uint8)])
+        buf = torch.from_numpy(host).to(dev)
+        ent = dict(key=key, buf=buf, clip=buf[:4], tab=buf[16:],
+                   chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev), n_chunks=len(chunks),
+                   partials=torch.empty(lib.grad_norm_parts(), dtype=torch.float32, device=dev))
+        _CLIP_CACHE['last'] = ent
+    norm = torch.empty(1, dtype=torch.float32, device=dev)
+    n_parts = min(ent['n_chunks'], lib.grad_norm_parts())
+    if ent['n_chunks'] == 0:             # every gradient is empty
+        return norm.zero_()[0]
+    lib.grad_sqnorm_multi(ent['tab'], ent['chunks'], ent['n_chunks'], ent['partials'])
+    lib.grad_scale_multi(ent['tab'], ent['chunks'], ent['n_chunks'], ent['partials'], n_parts, ent['clip'], norm)
+    return norm[0]

@@ -35,9 +35,12 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
   p = p + h.neg_step * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adam_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
-                                                    const int32_t* __restrict__ chunks,
-                                                    const float* __restrict__ hyp) {
+// One workgroup's chunk.  CLIP: the gradient is scaled by the clip coefficient `c` first — torch clips `.grad`, then
+// Adam adds wd * p — as a product of its own (__fmul_rn: never contracted into the weight-decay multiply-add, so that
+// c == 1 leaves the bits of the unclipped step).  CLIP = false is the kernel as it always was: `c` is not read.
+template <bool CLIP>
+__device__ __forceinline__ void adam_chunk(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                           const int32_t* __restrict__ chunks, const float* __restrict__ hyp, float c) {
   const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
   const bmnas_adam_tensor_t t = tensors[ti];
   const float* hr = hyp + 8 * t.hyp_row;
@@ -49,7 +52,8 @@ __global__ __launch_bounds__(256) void adam_multi_k(const bmnas_adam_tensor_t* _
   const uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
   if ((al & 15) == 0 && e + 4 <= t.numel) {
     float4 p = ld4(t.param + e), m = ld4(t.exp_avg + e), v = ld4(t.exp_avg_sq + e);
-    const float4 g = ld4(t.grad + e);
+    float4 g = ld4(t.grad + e);
+    if constexpr (CLIP) g = make_float4(__fmul_rn(g.x, c), __fmul_rn(g.y, c), __fmul_rn(g.z, c), __fmul_rn(g.w, c));
     adam1(p.x, g.x, m.x, v.x, h);
     adam1(p.y, g.y, m.y, v.y, h);
     adam1(p.z, g.z, m.z, v.z, h);
@@ -61,11 +65,92 @@ __global__ __launch_bounds__(256) void adam_multi_k(const bmnas_adam_tensor_t* _
     const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
     for (int64_t i = e; i < end; ++i) {
       float p = t.param[i], m = t.exp_avg[i], v = t.exp_avg_sq[i];
-      adam1(p, t.grad[i], m, v, h);
+      float g = t.grad[i];
+      if constexpr (CLIP) g = __fmul_rn(g, c);
+      adam1(p, g, m, v, h);
       t.param[i] = p;
       t.exp_avg[i] = m;
       t.exp_avg_sq[i] = v;
     }
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                                    const int32_t* __restrict__ chunks,
+                                                    const float* __restrict__ hyp) {
+  adam_chunk<false>(tensors, chunks, hyp, 1.f);
+}
+
+// ---- global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) -----------------------------------
+// Two launches, no atomics, no zero-fill: grad_sqnorm_multi_k leaves one partial sum of squares per workgroup of a FIXED
+// grid; every workgroup of the consumer adds the partials in one fixed order, so all of them — and every run, and every
+// data-parallel replica — derive the same bits.
+constexpr int kNormParts = 256;   // partials = lanes of the consumer's one block_sum256
+
+__global__ __launch_bounds__(256) void grad_sqnorm_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                                           const int32_t* __restrict__ chunks, int n_chunks,
+                                                           float* __restrict__ partials) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {        // chunks w, w + G, w + 2G, ... in that order
+    const bmnas_adam_tensor_t t = tensors[chunks[2 * c]];
+    const int64_t e = (int64_t)chunks[2 * c + 1] * kChunk + threadIdx.x * 4;
+    if (e >= t.numel) continue;
+    if (((uintptr_t)t.grad & 15) == 0 && e + 4 <= t.numel) {
+      const float4 g = ld4(t.grad + e);
+      acc += g.x * g.x;
+      acc += g.y * g.y;
+      acc += g.z * g.z;
+      acc += g.w * g.w;
+    } else {
+      const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
+      for (int64_t i = e; i < end; ++i) acc += t.grad[i] * t.grad[i];
+    }
+  }
+  const float total = block_sum256(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// sqrt(sum of the partials) and torch's coefficient: max_norm / (norm + 1e-6) clamped to <= 1 by a compare and select
+// (a NaN norm gives a NaN coefficient, as torch.clamp does; fminf would give 1).  Every thread of the block gets both.
+__device__ __forceinline__ float clip_coef(const float* __restrict__ partials, int n_parts,
+                                           const float* __restrict__ clip, float* red, float& norm) {
+  const float v = ((int)threadIdx.x < n_parts) ? partials[threadIdx.x] : 0.f;
+  norm = sqrtf(block_sum256(v, red));
+  const float c = clip[0] / (norm + 1e-6f);
+  return (c > 1.f) ? 1.f : c;
+}
+
+__global__ __launch_bounds__(256) void adam_multi_clip_k(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                                         const int32_t* __restrict__ chunks,
+                                                         const float* __restrict__ hyp,
+                                                         const float* __restrict__ partials, int n_parts,
+                                                         const float* __restrict__ clip, float* __restrict__ norm_out) {
+  __shared__ float red[4];
+  float norm;
+  const float c = clip_coef(partials, n_parts, clip, red, norm);
+  if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  adam_chunk<true>(tensors, chunks, hyp, c);
+}
+
+__global__ __launch_bounds__(256) void grad_scale_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                                          const int32_t* __restrict__ chunks,
+                                                          const float* __restrict__ partials, int n_parts,
+                                                          const float* __restrict__ clip, float* __restrict__ norm_out) {
+  __shared__ float red[4];
+  float norm;
+  const float c = clip_coef(partials, n_parts, clip, red, norm);
+  if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  const bmnas_adam_tensor_t t = tensors[chunks[2 * blockIdx.x]];
+  float* __restrict__ grad = const_cast<float*>(t.grad);
+  const int64_t e = (int64_t)chunks[2 * blockIdx.x + 1] * kChunk + threadIdx.x * 4;
+  if (e >= t.numel) return;
+  if (((uintptr_t)grad & 15) == 0 && e + 4 <= t.numel) {
+    const float4 g = ld4(grad + e);
+    st4_wtg<5>(grad + e, make_float4(__fmul_rn(g.x, c), __fmul_rn(g.y, c), __fmul_rn(g.z, c), __fmul_rn(g.w, c)));
+  } else {
+    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
+    for (int64_t i = e; i < end; ++i) grad[i] = __fmul_rn(grad[i], c);
   }
 }
 
@@ -78,6 +163,42 @@ extern "C" int bmnas_adam_multi(const bmnas_adam_tensor_t* tensors, const int32_
   if (!tensors || !chunks || !hyp || n_chunks < 0) return BMNAS_E_ARG;
   if (n_chunks == 0) return 0;
   hipLaunchKernelGGL(adam_multi_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, hyp);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_grad_norm_parts(void) { return kNormParts; }
+
+extern "C" int bmnas_grad_sqnorm_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                                       float* partials, void* stream) {
+  if (!tensors || !chunks || !partials || n_chunks <= 0) return BMNAS_E_ARG;
+  const int g = n_chunks < kNormParts ? n_chunks : kNormParts;
+  hipLaunchKernelGGL(grad_sqnorm_multi_k, dim3(g), dim3(256), 0, (hipStream_t)stream, tensors, chunks, n_chunks,
+                     partials);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+// `.grad` is NOT written: the clipped gradient exists only in registers (4 B per parameter of stores and a third
+// launch saved); callers that read `.grad` after the step see the unclipped values.
+extern "C" int bmnas_adam_multi_clip(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                                     const float* hyp, const float* partials, int n_parts, const float* clip,
+                                     float* norm_out, void* stream) {
+  if (!tensors || !chunks || !hyp || !partials || !clip || !norm_out || n_chunks <= 0) return BMNAS_E_ARG;
+  if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;   // what the norm launch wrote
+  hipLaunchKernelGGL(adam_multi_clip_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, hyp,
+                     partials, n_parts, clip, norm_out);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_grad_scale_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                                      const float* partials, int n_parts, const float* clip, float* norm_out,
+                                      void* stream) {
+  if (!tensors || !chunks || !partials || !clip || !norm_out || n_chunks <= 0) return BMNAS_E_ARG;
+  if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;
+  hipLaunchKernelGGL(grad_scale_multi_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, partials,
+                     n_parts, clip, norm_out);
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

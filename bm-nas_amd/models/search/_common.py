@@ -132,11 +132,16 @@ def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_d
     the reference's train_darts_model between model construction and the trainer call
     (mmimdb_darts_searchable.py:26-40).  nn.DataParallel is replaced by per-process replicas
     whose optimizers average gradients over RCCL right before step() (bmnas.dist)."""
-    optimizer = Adam(model.central_params(), lr=args.eta_max, weight_decay=weight_decay)
+    # args.grad_clip / args.arch_grad_clip (optional; the reference's argument sets have neither, DARTS ships
+    # `--grad_clip 5`): the global gradient-norm clip of the weight / alpha step, inside the one-launch Adam step
+    # (bmnas.optim.Adam(max_grad_norm=...): captured steps included; `.grad` stays unclipped)
+    optimizer = Adam(model.central_params(), lr=args.eta_max, weight_decay=weight_decay,
+                     max_grad_norm=getattr(args, 'grad_clip', None))
     scheduler = sc.LRCosineAnnealingScheduler(args.eta_max, args.eta_min, args.Ti, args.Tm,
                                               num_batches_per_epoch)
     arch_optimizer = Adam(model.arch_parameters(), lr=args.arch_learning_rate, betas=(0.5, 0.999),
-                             weight_decay=args.arch_weight_decay)
+                             weight_decay=args.arch_weight_decay,
+                             max_grad_norm=getattr(args, 'arch_grad_clip', None))
     if data_parallel_world(args) > 1:
         # one process per GPU: the unchanged mains pass cuda:0 to every rank
         # (main_darts_searchable_mmimdb.py:86), so the rank's own device comes from LOCAL_RANK,

@@ -875,6 +875,30 @@ int bmnas_adam_chunk_elems(void);
 int bmnas_adam_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
                      const float* hyp, void* stream);
 
+/* ---- global gradient-norm clipping in the Adam step (torch.nn.utils.clip_grad_norm_, norm_type 2) ----------
+ * DARTS' `--grad_clip`: the remedy for the diverged search the trainers' `nan_escape` ends
+ * (train_searchable/_loop.py).  Two launches over the SAME descriptor table and (tensor, chunk) list as
+ * bmnas_adam_multi, no atomics and no zero-fill, so the result is bit-identical from run to run:
+ *   bmnas_grad_sqnorm_multi: a fixed grid of G = min(n_chunks, bmnas_grad_norm_parts()) workgroups; workgroup w
+ *     walks chunks w, w + G, ... and stores its sum of grad^2 to partials[w] (G floats written, nothing else;
+ *     reads only `grad` and `numel` of a descriptor).
+ *   bmnas_adam_multi_clip: bmnas_adam_multi with every gradient scaled first, BEFORE the weight-decay term, by
+ *       norm = sqrt(sum of partials[0 .. n_parts));  c = clip[0] / (norm + 1e-6);  c = c > 1 ? 1 : c
+ *     (a NaN norm gives a NaN coefficient, as torch's clamp does).  n_parts must be the G of the norm launch.
+ *     clip: DEVICE float, max_norm (read at run time: a captured graph replays with a changed value);
+ *     norm_out: DEVICE float, receives the pre-clip norm.  `.grad` is NOT written: the clipped gradient lives in
+ *     registers only, the tensors keep the unclipped values.
+ *   bmnas_grad_scale_multi: the same coefficient, grad *= c IN PLACE (the stand-alone clip_grad_norm_). */
+int bmnas_grad_norm_parts(void);
+int bmnas_grad_sqnorm_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                            float* partials, void* stream);
+int bmnas_adam_multi_clip(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                          const float* hyp, const float* partials, int n_parts, const float* clip,
+                          float* norm_out, void* stream);
+int bmnas_grad_scale_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                           const float* partials, int n_parts, const float* clip, float* norm_out,
+                           void* stream);
+
 /* ---- a batch into a captured step's static tensors (bmnas.graph._copy_batch_in) -------------------
  * The reference hands every batch over with `.to(device)` per tensor (train_searchable/mmimdb.py:60-63,
  * ntu.py:60-66, ego.py:60-66); a replayed step reads its inputs from fixed addresses, so a batch that is
