@@ -253,6 +253,7 @@ SIGNATURES = {
     'bmnas_grad_norm_parts': ([], _I),
     'bmnas_grad_sqnorm_multi': ([_P, _P, _I, _P, _P], _I),
     'bmnas_adam_multi_clip': ([_P, _P, _I, _P, _P, _I, _P, _P, _P], _I),
+    'bmnas_adam_multi_ex': ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_grad_scale_multi': ([_P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_copy_batch_max': ([], _I),
     'bmnas_copy_blob_max': ([], _I),
@@ -1129,6 +1130,21 @@ def adam_multi_clip(table, chunks, n_chunks, hyp, partials, n_parts, clip, norm_
     scalars (max_norm in, pre-clip norm out).  `.grad` is NOT written."""
     _check(load().bmnas_adam_multi_clip(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), _ptr(partials),
                                         n_parts, clip.data_ptr(), norm_out.data_ptr(), _stream()), 'adam_multi_clip')
+
+
+ADAM_AMSGRAD, ADAM_DECOUPLED = 1, 2          # BMNAS_ADAM_* (include/bmnas_hip.h)
+
+
+def adam_multi_ex(table, chunks, n_chunks, hyp, max_exp_avg_sq, flags, partials=None, n_parts=0, clip=None,
+                  norm_out=None):
+    """adam_multi / adam_multi_clip with flags = ADAM_AMSGRAD | ADAM_DECOUPLED.  max_exp_avg_sq: device tensor holding one
+    float* per descriptor of `table` (the running maxima; None without ADAM_AMSGRAD).  ADAM_DECOUPLED: slot 5 of a `hyp`
+    row holds float(1 - lr * weight_decay) instead of weight_decay.  Clips iff partials is given (then clip and norm_out
+    too, as for adam_multi_clip).  flags == 0 runs the kernels of adam_multi / adam_multi_clip."""
+    p = lambda t: None if t is None else t.data_ptr()
+    _check(load().bmnas_adam_multi_ex(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), p(max_exp_avg_sq),
+                                      int(flags), p(partials), n_parts, p(clip), p(norm_out), _stream()),
+           'adam_multi_ex')
 
 
 def grad_scale_multi(table, chunks, n_chunks, partials, n_parts, clip, norm_out):

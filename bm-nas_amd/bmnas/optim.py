@@ -16,6 +16,13 @@ a step captured in a hipGraph replays correctly: `prepare_replay()` before each 
 `--grad_clip`), captured steps included: one norm launch (`bmnas_grad_sqnorm_multi`) in front of the
 clipped update (`bmnas_adam_multi_clip`).  The update scales each gradient in registers: `.grad` is
 NOT written and keeps the unclipped values.  `clip_grad_norm_` below is the stand-alone, in-place form.
+
+`Adam(..., amsgrad=True)` and `Adam(..., decoupled_weight_decay=True)` / `AdamW` are torch's two switches, kept in
+torch's own `param_groups` keys (so a torch.optim.AdamW or amsgrad checkpoint loads and is honoured) and run by the same
+single launch (`bmnas_adam_multi_ex`; with both off the launches are `bmnas_adam_multi` / `bmnas_adam_multi_clip` as
+before).  AMSGrad keeps torch's per-parameter `max_exp_avg_sq`; its pointers ride behind the descriptor table in the
+staging buffer.  Decoupled decay stages float(1 - lr * weight_decay) where the L2 mode stages weight_decay.  One launch
+is one kernel instantiation: all groups of an optimizer must agree on each switch.
 """
 import math
 
@@ -32,15 +39,17 @@ assert _DESC.itemsize == 48
 
 class Adam(torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
-                 max_grad_norm=None):
-        """max_grad_norm (None or a positive float): clip the global L2 norm over every parameter of the optimizer that has
+                 max_grad_norm=None, *, decoupled_weight_decay=False):
+        """amsgrad / decoupled_weight_decay: torch.optim.Adam's, stored in `param_groups` under torch's keys and read from
+        there when a plan is built (a loaded checkpoint's values count); every group must hold the same value of each.
+        They may be edited between eager steps (the plan is rebuilt) but not under a captured plan.
+        max_grad_norm (None or a positive float): clip the global L2 norm over every parameter of the optimizer that has
         a gradient, all groups together, before the update.  An attribute, not a `param_groups` entry (state_dict() stays
         that of torch.optim.Adam); it may be edited between steps and replays — it travels with the per-step scalars —
         but not switched between None and a value under a captured plan.  `.grad` is left UNCLIPPED: the scaling happens
         in the update's registers.  `last_grad_norm` / `grad_norms` hold the pre-clip norm(s) on the device."""
-        if amsgrad:
-            raise lib.BmnasError('bmnas.optim.Adam: amsgrad is not on the reference path')
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad),
+                         decoupled_weight_decay=bool(decoupled_weight_decay))
         self.max_grad_norm = max_grad_norm
         self._clip_value()
         self._plan = None
@@ -74,13 +83,55 @@ class Adam(torch.optim.Adam):
     def _active(self):
         return [(p, gi) for gi, g in enumerate(self.param_groups) for p in g['params'] if p.grad is not None]
 
-    def _init_state(self, p):
+    def _variant(self):
+        """-> (clip, amsgrad, decoupled): what selects the launches of a step, the key of a plan.  The two switches are
+        read from `param_groups` (torch's keys; a checkpoint written before torch had one lacks it: off)."""
+        return (self._clip_value() is not None,) + self._switches()
+
+    def _switches(self):
+        """-> (amsgrad, decoupled_weight_decay) of the param_groups, which must agree on each."""
+        first = None
+        for g in self.param_groups:
+            sw = (bool(g.get('amsgrad', False)), bool(g.get('decoupled_weight_decay', False)))
+            if first is None:
+                first = sw
+            elif sw != first:
+                name = 'amsgrad' if sw[0] != first[0] else 'decoupled_weight_decay'
+                raise lib.BmnasError(f"bmnas.optim.Adam: param_groups disagree on '{name}' (one launch updates every "
+                                     'group with one kernel: per-group mixing is not supported)')
+        return first or (False, False)
+
+    def _init_state(self, p, amsgrad=False):
+        """amsgrad: `max_exp_avg_sq` is created with the moments — and, as zeros, for a state that has the moments but
+        not it (an amsgrad=False checkpoint continued with amsgrad on: the first maximum then equals exp_avg_sq; torch
+        raises KeyError there)."""
         st = self.state[p]
         if len(st) == 0:
             st['step'] = torch.tensor(0.0, dtype=torch.float32)
             st['exp_avg'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
             st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        if amsgrad and 'max_exp_avg_sq' not in st:
+            st['max_exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         return st
+
+    def _state_ptrs(self, plan):
+        """(Re)write the state pointers of every descriptor table of `plan` — and the running-maximum pointers behind
+        them — from the CURRENT state tensors, validated."""
+        names = ('exp_avg', 'exp_avg_sq') + (('max_exp_avg_sq',) if plan['amsgrad'] else ())
+        ptrs = {n: [] for n in names}
+        for p, _ in plan['active']:
+            st = self._init_state(p, plan['amsgrad'])
+            for n in names:
+                t = st[n]
+                if t.device != p.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                    raise lib.BmnasError(f'bmnas.optim.Adam: {n} must be contiguous fp32 on {p.device}, of the '
+                                         "parameter's size")
+                ptrs[n].append(t.data_ptr())
+        for i, tab in enumerate(plan['tabs']):
+            tab['exp_avg'] = ptrs['exp_avg']
+            tab['exp_avg_sq'] = ptrs['exp_avg_sq']
+            if plan['amsgrad']:
+                plan['maxes'][i][:] = ptrs['max_exp_avg_sq']
 
     def _flush_counts(self):
         """Write the plan's step counts back into the per-parameter `step` tensors."""
@@ -93,6 +144,7 @@ class Adam(torch.optim.Adam):
         """slots > 1: a captured graph that holds `slots` consecutive optimizer steps (bmnas.graph.GraphedTrainStep(k=...)):
         every step has its own scalar rows and its own descriptor table (each step's backward leaves its gradients in
         tensors of its own), all in the ONE staging buffer."""
+        clip, amsgrad, decoupled = self._variant()
         self._flush_counts()
         dev = active[0][0].device
         E = lib.adam_chunk_elems()
@@ -100,10 +152,9 @@ class Adam(torch.optim.Adam):
         for i, (p, gi) in enumerate(active):
             if not p.is_cuda:
                 raise lib.BmnasError('bmnas.optim.Adam needs parameters on the GPU (HIP kernel, no CPU path)')
-            st = self._init_state(p)
-            for name, t in (('parameter', p), ('exp_avg', st['exp_avg']), ('exp_avg_sq', st['exp_avg_sq'])):
-                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise lib.BmnasError(f'bmnas.optim.Adam: {name} must be contiguous fp32 on {dev}')
+            st = self._init_state(p, amsgrad)
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise lib.BmnasError(f'bmnas.optim.Adam: parameter must be contiguous fp32 on {dev}')
             # parameters of one group with the same step count share a row of scalars
             key = (gi, float(st['step']))
             if key not in row_idx:
@@ -113,18 +164,18 @@ class Adam(torch.optim.Adam):
             chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
         # (scalar slots packed back to back — 32 bytes per row —: the whole region travels by value in poke mode)
         # clipping: max_grad_norm rides behind each slot's rows (16 bytes: the next slot's rows stay 16-byte aligned)
-        clip = self._clip_value() is not None
+        # amsgrad: one `float*` per descriptor (max_exp_avg_sq) rides BEHIND each slot's descriptor table — the table
+        # itself is shared with the norm launch and stays 48 bytes per tensor — so it travels with the table's upload
         row_bytes = len(rows) * 32
         hyp_slot = row_bytes + (16 if clip else 0)
         hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
-        tab_slot = len(active) * _DESC.itemsize
+        tab_bytes = len(active) * _DESC.itemsize
+        tab_slot = tab_bytes + (len(active) * 8 if amsgrad else 0)
         nbytes = hyp_bytes + slots * tab_slot
         pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
         host = pin.numpy()
-        tabs = [host[hyp_bytes + i * tab_slot:hyp_bytes + (i + 1) * tab_slot].view(_DESC) for i in range(slots)]
+        tabs = [host[hyp_bytes + i * tab_slot:hyp_bytes + i * tab_slot + tab_bytes].view(_DESC) for i in range(slots)]
         for tab in tabs:
-            tab['exp_avg'] = [self.state[p]['exp_avg'].data_ptr() for p, _ in active]
-            tab['exp_avg_sq'] = [self.state[p]['exp_avg_sq'].data_ptr() for p, _ in active]
             tab['numel'] = [p.numel() for p, _ in active]
             tab['hyp_row'] = row_of
         devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -134,11 +185,18 @@ class Adam(torch.optim.Adam):
                           pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * hyp_slot], tab=tabs[0], tabs=tabs,
                           dev=devbuf, dev_hyp=devbuf[:hyp_bytes],
                           dev_hyps=[devbuf[i * hyp_slot:(i + 1) * hyp_slot] for i in range(slots)],
-                          dev_tab=devbuf[hyp_bytes:hyp_bytes + tab_slot],
-                          dev_tabs=[devbuf[hyp_bytes + i * tab_slot:hyp_bytes + (i + 1) * tab_slot]
+                          dev_tab=devbuf[hyp_bytes:hyp_bytes + tab_bytes],
+                          dev_tabs=[devbuf[hyp_bytes + i * tab_slot:hyp_bytes + i * tab_slot + tab_bytes]
                                     for i in range(slots)],
                           chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev),
-                          n_chunks=len(chunks), slots=slots, cap_slot=0, clip=clip)
+                          n_chunks=len(chunks), slots=slots, cap_slot=0, clip=clip, amsgrad=amsgrad,
+                          decoupled=decoupled, key=(clip, amsgrad, decoupled),
+                          flags=(lib.ADAM_AMSGRAD if amsgrad else 0) | (lib.ADAM_DECOUPLED if decoupled else 0))
+        if amsgrad:
+            at = lambda i: hyp_bytes + i * tab_slot + tab_bytes
+            self._plan.update(maxes=[host[at(i):at(i) + len(active) * 8].view('<u8') for i in range(slots)],
+                              dev_maxes=[devbuf[at(i):at(i) + len(active) * 8] for i in range(slots)])
+        self._state_ptrs(self._plan)
         if clip:
             # the norm launch's partials, the max_grad_norm scalars (host + device view) and the norm outputs belong to the
             # plan: a captured plan's graph reads and writes these addresses for good
@@ -170,6 +228,14 @@ class Adam(torch.optim.Adam):
             pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
         if pl['clip']:
             lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
+        if pl['flags']:
+            mx = pl['dev_maxes'][slot] if pl['amsgrad'] else None
+            if pl['clip']:
+                lib.adam_multi_ex(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], mx, pl['flags'],
+                                  pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
+            else:
+                lib.adam_multi_ex(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], mx, pl['flags'])
+        elif pl['clip']:
             lib.adam_multi_clip(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot],
                                 pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
         else:
@@ -202,9 +268,10 @@ class Adam(torch.optim.Adam):
         active = self._active()
         if not active:
             return loss
+        key = self._variant()                   # (first: groups that disagree on a switch are refused before anything moves)
         self._touch += 1
         if torch.cuda.is_current_stream_capturing():
-            if self._plan is None or self._plan['ids'] != tuple(id(p) for p, _ in active):
+            if self._plan is None or self._plan['ids'] != tuple(id(p) for p, _ in active) or self._plan['key'] != key:
                 raise lib.BmnasError('bmnas.optim.Adam: call capture_safe() before capturing step() in a graph')
             slot = self._plan['cap_slot']
             if slot >= self._plan['slots']:
@@ -216,11 +283,10 @@ class Adam(torch.optim.Adam):
             self._plan['cap_slot'] = slot + 1
             return loss
         ids = tuple(id(p) for p, _ in active)
-        clip = self.max_grad_norm is not None
-        if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids or self._plan['clip'] != clip:
+        if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids or self._plan['key'] != key:
             # never stage an eager step through a captured plan: its graph re-reads those buffers
             eager = getattr(self, '_eager_plan', None)
-            if eager is not None and eager['ids'] == ids and eager['clip'] == clip:
+            if eager is not None and eager['ids'] == ids and eager['key'] == key:
                 self._switch(eager)
             else:
                 self._build(active)
@@ -313,7 +379,7 @@ class Adam(torch.optim.Adam):
             self._flush_counts()
             counts = {}
             for (p, _), r in zip(plan['active'], plan['row_of']):
-                c = float(self._init_state(p)['step'])
+                c = float(self._init_state(p, plan['amsgrad'])['step'])
                 if counts.setdefault(r, c) != c:
                     raise lib.BmnasError('bmnas.optim.Adam: parameters that shared a step count when this plan was '
                                          'built have diverged (an eager step on a subset?); re-capture the graph')
@@ -323,9 +389,7 @@ class Adam(torch.optim.Adam):
         if not plan.get('poke'):
             self.wait_staging()              # the plan's last launch has consumed its pinned buffer
         if plan['gen'] != self._gen:
-            for tab in plan['tabs']:
-                tab['exp_avg'] = [self._init_state(p)['exp_avg'].data_ptr() for p, _ in plan['active']]
-                tab['exp_avg_sq'] = [self.state[p]['exp_avg_sq'].data_ptr() for p, _ in plan['active']]
+            self._state_ptrs(plan)
             plan['gen'] = self._gen
 
     def activate(self, plan):
@@ -367,6 +431,10 @@ class Adam(torch.optim.Adam):
         if (c is not None) != pl['clip']:
             raise lib.BmnasError('bmnas.optim.Adam: max_grad_norm was switched between None and a value under a plan built '
                                  'for the other (a captured step holds the launches of one of them); re-capture the graph')
+        if self._switches() != pl['key'][1:]:
+            raise lib.BmnasError("bmnas.optim.Adam: 'amsgrad' / 'decoupled_weight_decay' was switched under a plan built "
+                                 'for the other value (a captured step holds the launches of one of them); re-capture the '
+                                 'graph')
         if c is not None:
             pl['clips'][slot][0] = c
         for r, gi in enumerate(pl['groups']):
@@ -374,8 +442,12 @@ class Adam(torch.optim.Adam):
             pl['count'][r] += 1.0
             t = pl['count'][r]
             b1, b2 = g['betas']
-            h[r] = (-(g['lr'] / (1 - b1 ** t)), math.sqrt(1 - b2 ** t), b1, b2, g['eps'], g['weight_decay'],
-                    1 - b1, 1 - b2)
+            # slot 5: weight_decay (L2, added to the gradient), or the decoupled decay's factor on the parameter, formed in
+            # double as torch's `param.mul_(1 - lr * weight_decay)` does (exactly 1 without decay)
+            wd = g['weight_decay']
+            if pl['decoupled']:
+                wd = 1 - g['lr'] * wd if wd != 0 else 1.0
+            h[r] = (-(g['lr'] / (1 - b1 ** t)), math.sqrt(1 - b2 ** t), b1, b2, g['eps'], wd, 1 - b1, 1 - b2)
 
     def staged_lrs(self, slot=0):
         """The learning rate of every scalar row of `slot`, decoded from what prepare_replay() STAGED there (the fp32 value
@@ -383,6 +455,22 @@ class Adam(torch.optim.Adam):
         pl = self._plan
         return [float(-pl['hyps'][slot][r][0]) * (1 - self.param_groups[gi]['betas'][0] ** pl['count'][r])
                 for r, gi in enumerate(pl['groups'])]
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW on the same one launch: Adam with decoupled weight decay (p *= 1 - lr * weight_decay in front of
+    the update, the gradient untouched), default weight_decay 1e-2.  Like torch's class it stays decoupled whatever state
+    it loads; `amsgrad` and `max_grad_norm` as for Adam."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
+                 max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                         max_grad_norm=max_grad_norm, decoupled_weight_decay=True)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group['decoupled_weight_decay'] = True
 
 
 _CLIP_CACHE = {}

@@ -3,17 +3,21 @@
 // train_searchable/mmimdb.py:101 and architect.py:24) as ONE launch over every tensor of
 // the optimizer instead of ~10 foreach launches x param groups.
 //
-// Arithmetic = torch.optim.Adam (amsgrad off, maximize off, L2 weight decay folded into the
-// gradient), operation by operation:
-//   g   = grad + wd * p                              (only if wd != 0)
+// Arithmetic = torch.optim.Adam / torch.optim.AdamW (torch 2.10's _single_tensor_adam; maximize off),
+// operation by operation:
+//   p   = p * f                                      (decoupled weight decay: f = float(1 - lr * wd))
+//   g   = grad + wd * p                              (L2 weight decay, only if wd != 0)
 //   m   = lerp(m, g, 1 - beta1)
 //   v   = v * beta2 + (1 - beta2) * g * g
-//   p  += -(lr / bc1) * ( m / ( sqrt(v) / sqrt(bc2) + eps ) )
-// The step-dependent scalars (-(lr/bc1), sqrt(bc2)) are computed by the host in double, as
+//   vm  = maximum(vm, v)                             (amsgrad; NaN-propagating, as torch.maximum)
+//   p  += -(lr / bc1) * ( m / ( sqrt(amsgrad ? vm : v) / sqrt(bc2) + eps ) )
+// adam_multi_k / adam_multi_clip_k are the kernels with both switches off (L2, no running maximum);
+// adam_multi_ex_k<CLIP, DECOUPLED, AMSGRAD> holds every other combination (bmnas_adam_multi_ex).
+// The step-dependent scalars (-(lr/bc1), sqrt(bc2), f) are computed by the host in double, as
 // torch does, and handed over in a small device table (`hyp`, 8 floats per row) that the host
 // refreshes before every launch: a captured hipGraph replays with new learning rates / step
 // counts without re-capture.
-// HBM-streaming: 4 reads + 3 writes per element = 28 B/param.
+// HBM-streaming: 4 reads + 3 writes per element = 28 B/param; amsgrad: 5 reads + 4 writes = 36 B/param.
 #include "common.hpp"
 #include <cstring>
 #include "../../include/bmnas_hip.h"
@@ -26,21 +30,45 @@ struct Hyp {
   float neg_step, bc2_sqrt, beta2, eps, wd, w1, w2;
 };
 
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const Hyp& h) {
-  if (h.wd != 0.f) g = g + h.wd * p;
+// a * b rounded on its own: the product carries no permission to contract, so the compiler cannot fold it into a
+// neighbouring addition as a fused multiply-add (__fmul_rn is a plain `*` to this compiler, and p * f + s * q became
+// fma(f, p, s * q): with f == 1 that is p + round(s * q), not the fma(s, q, p) of the undecayed step)
+__device__ __forceinline__ float mul_alone(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// DECOUPLED: h.wd holds f = float(1 - lr * weight_decay) and the decay is a product of its own on the parameter
+// (mul_alone: never contracted into the update's multiply-add, so that f == 1 leaves the bits of the undecayed step); the
+// gradient is not touched.  AMSGRAD: `vm` is the running maximum of v, and the denominator is built from it; compare and
+// select, v winning when it is NaN — torch.maximum (fmaxf would drop a NaN).  Both false: the update as it always was.
+template <bool DECOUPLED, bool AMSGRAD>
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float& vm, const Hyp& h) {
+  if constexpr (DECOUPLED) {
+    p = mul_alone(p, h.wd);
+  } else {
+    if (h.wd != 0.f) g = g + h.wd * p;
+  }
   const float d = g - m;
   m = (h.w1 < 0.5f) ? m + h.w1 * d : g - d * (1.f - h.w1);      // at::lerp's two branches
   v = v * h.beta2 + h.w2 * (g * g);
-  const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
+  float s = v;
+  if constexpr (AMSGRAD) {
+    vm = (v > vm || v != v) ? v : vm;
+    s = vm;
+  }
+  const float denom = sqrtf(s) / h.bc2_sqrt + h.eps;
   p = p + h.neg_step * (m / denom);
 }
 
 // One workgroup's chunk.  CLIP: the gradient is scaled by the clip coefficient `c` first — torch clips `.grad`, then
 // Adam adds wd * p — as a product of its own (__fmul_rn: never contracted into the weight-decay multiply-add, so that
 // c == 1 leaves the bits of the unclipped step).  CLIP = false is the kernel as it always was: `c` is not read.
-template <bool CLIP>
+// AMSGRAD: max_exp_avg_sq[ti] is tensor ti's running maximum (one pointer per descriptor; not read otherwise).
+template <bool CLIP, bool DECOUPLED = false, bool AMSGRAD = false>
 __device__ __forceinline__ void adam_chunk(const bmnas_adam_tensor_t* __restrict__ tensors,
-                                           const int32_t* __restrict__ chunks, const float* __restrict__ hyp, float c) {
+                                           const int32_t* __restrict__ chunks, const float* __restrict__ hyp, float c,
+                                           float* const* __restrict__ max_exp_avg_sq = nullptr) {
   const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
   const bmnas_adam_tensor_t t = tensors[ti];
   const float* hr = hyp + 8 * t.hyp_row;
@@ -49,28 +77,37 @@ __device__ __forceinline__ void adam_chunk(const bmnas_adam_tensor_t* __restrict
   h.w1 = hr[6]; h.w2 = hr[7];
   const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
   if (e >= t.numel) return;
-  const uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
+  float* mx = nullptr;
+  if constexpr (AMSGRAD) mx = max_exp_avg_sq[ti];
+  uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
+  if constexpr (AMSGRAD) al |= (uintptr_t)mx;
   if ((al & 15) == 0 && e + 4 <= t.numel) {
     float4 p = ld4(t.param + e), m = ld4(t.exp_avg + e), v = ld4(t.exp_avg_sq + e);
     float4 g = ld4(t.grad + e);
+    float4 vm = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (AMSGRAD) vm = ld4(mx + e);
     if constexpr (CLIP) g = make_float4(__fmul_rn(g.x, c), __fmul_rn(g.y, c), __fmul_rn(g.z, c), __fmul_rn(g.w, c));
-    adam1(p.x, g.x, m.x, v.x, h);
-    adam1(p.y, g.y, m.y, v.y, h);
-    adam1(p.z, g.z, m.z, v.z, h);
-    adam1(p.w, g.w, m.w, v.w, h);
+    adam1<DECOUPLED, AMSGRAD>(p.x, g.x, m.x, v.x, vm.x, h);
+    adam1<DECOUPLED, AMSGRAD>(p.y, g.y, m.y, v.y, vm.y, h);
+    adam1<DECOUPLED, AMSGRAD>(p.z, g.z, m.z, v.z, vm.z, h);
+    adam1<DECOUPLED, AMSGRAD>(p.w, g.w, m.w, v.w, vm.w, h);
     st4_wtg<5>(t.param + e, p);
     st4_wtg<5>(t.exp_avg + e, m);
     st4_wtg<5>(t.exp_avg_sq + e, v);
+    if constexpr (AMSGRAD) st4_wtg<5>(mx + e, vm);
   } else {
     const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
     for (int64_t i = e; i < end; ++i) {
       float p = t.param[i], m = t.exp_avg[i], v = t.exp_avg_sq[i];
       float g = t.grad[i];
+      float vm = 0.f;
+      if constexpr (AMSGRAD) vm = mx[i];
       if constexpr (CLIP) g = __fmul_rn(g, c);
-      adam1(p, g, m, v, h);
+      adam1<DECOUPLED, AMSGRAD>(p, g, m, v, vm, h);
       t.param[i] = p;
       t.exp_avg[i] = m;
       t.exp_avg_sq[i] = v;
+      if constexpr (AMSGRAD) mx[i] = vm;
     }
   }
 }
@@ -133,6 +170,25 @@ __global__ __launch_bounds__(256) void adam_multi_clip_k(const bmnas_adam_tensor
   adam_chunk<true>(tensors, chunks, hyp, c);
 }
 
+// Every combination but "both off": decoupled weight decay and / or the amsgrad running maximum, with or without the
+// clip coefficient — one instantiation per launch (all tensors of an optimizer agree on the switches).
+template <bool CLIP, bool DECOUPLED, bool AMSGRAD>
+__global__ __launch_bounds__(256) void adam_multi_ex_k(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                                       const int32_t* __restrict__ chunks,
+                                                       const float* __restrict__ hyp,
+                                                       float* const* __restrict__ max_exp_avg_sq,
+                                                       const float* __restrict__ partials, int n_parts,
+                                                       const float* __restrict__ clip, float* __restrict__ norm_out) {
+  float c = 1.f;
+  if constexpr (CLIP) {
+    __shared__ float red[4];
+    float norm;
+    c = clip_coef(partials, n_parts, clip, red, norm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  }
+  adam_chunk<CLIP, DECOUPLED, AMSGRAD>(tensors, chunks, hyp, c, max_exp_avg_sq);
+}
+
 __global__ __launch_bounds__(256) void grad_scale_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
                                                           const int32_t* __restrict__ chunks,
                                                           const float* __restrict__ partials, int n_parts,
@@ -188,6 +244,37 @@ extern "C" int bmnas_adam_multi_clip(const bmnas_adam_tensor_t* tensors, const i
   if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;   // what the norm launch wrote
   hipLaunchKernelGGL(adam_multi_clip_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, hyp,
                      partials, n_parts, clip, norm_out);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int bmnas_adam_multi_ex(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                                   const float* hyp, float* const* max_exp_avg_sq, int flags, const float* partials,
+                                   int n_parts, const float* clip, float* norm_out, void* stream) {
+  if (flags & ~(BMNAS_ADAM_AMSGRAD | BMNAS_ADAM_DECOUPLED)) return BMNAS_E_ARG;
+  const bool ams = (flags & BMNAS_ADAM_AMSGRAD) != 0, dec = (flags & BMNAS_ADAM_DECOUPLED) != 0;
+  if (ams != (max_exp_avg_sq != nullptr)) return BMNAS_E_ARG;
+  const bool clipped = partials != nullptr;
+  if ((clip != nullptr) != clipped || (norm_out != nullptr) != clipped) return BMNAS_E_ARG;
+  if (flags == 0) {                                    // both switches off: the kernels that case always ran on
+    return clipped ? bmnas_adam_multi_clip(tensors, chunks, n_chunks, hyp, partials, n_parts, clip, norm_out, stream)
+                   : bmnas_adam_multi(tensors, chunks, n_chunks, hyp, stream);
+  }
+  if (!tensors || !chunks || !hyp || n_chunks < 0) return BMNAS_E_ARG;
+  if (clipped && (n_chunks == 0 || n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts))) return BMNAS_E_ARG;
+  if (n_chunks == 0) return 0;
+#define BMNAS_ADAM_EX(C, D, A)                                                                                       \
+  hipLaunchKernelGGL((adam_multi_ex_k<C, D, A>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, \
+                     hyp, max_exp_avg_sq, partials, n_parts, clip, norm_out)
+  switch ((clipped ? 4 : 0) | flags) {
+    case 1: BMNAS_ADAM_EX(false, false, true); break;
+    case 2: BMNAS_ADAM_EX(false, true, false); break;
+    case 3: BMNAS_ADAM_EX(false, true, true); break;
+    case 5: BMNAS_ADAM_EX(true, false, true); break;
+    case 6: BMNAS_ADAM_EX(true, true, false); break;
+    default: BMNAS_ADAM_EX(true, true, true); break;
+  }
+#undef BMNAS_ADAM_EX
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

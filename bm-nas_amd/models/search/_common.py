@@ -135,13 +135,20 @@ def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_d
     # args.grad_clip / args.arch_grad_clip (optional; the reference's argument sets have neither, DARTS ships
     # `--grad_clip 5`): the global gradient-norm clip of the weight / alpha step, inside the one-launch Adam step
     # (bmnas.optim.Adam(max_grad_norm=...): captured steps included; `.grad` stays unclipped)
+    # args.amsgrad / args.decoupled_weight_decay and args.arch_amsgrad / args.arch_decoupled_weight_decay (optional; the
+    # reference's argument sets have none of them): torch.optim.Adam's two switches for the weight / alpha optimizer —
+    # the running maximum of the second moment, and AdamW's decay on the parameter instead of the gradient — in the same
+    # one launch (bmnas_adam_multi_ex), captured steps included; absent, the optimizers are the ones they always were
     optimizer = Adam(model.central_params(), lr=args.eta_max, weight_decay=weight_decay,
-                     max_grad_norm=getattr(args, 'grad_clip', None))
+                     max_grad_norm=getattr(args, 'grad_clip', None), amsgrad=bool(getattr(args, 'amsgrad', False)),
+                     decoupled_weight_decay=bool(getattr(args, 'decoupled_weight_decay', False)))
     scheduler = sc.LRCosineAnnealingScheduler(args.eta_max, args.eta_min, args.Ti, args.Tm,
                                               num_batches_per_epoch)
     arch_optimizer = Adam(model.arch_parameters(), lr=args.arch_learning_rate, betas=(0.5, 0.999),
                              weight_decay=args.arch_weight_decay,
-                             max_grad_norm=getattr(args, 'arch_grad_clip', None))
+                             max_grad_norm=getattr(args, 'arch_grad_clip', None),
+                             amsgrad=bool(getattr(args, 'arch_amsgrad', False)),
+                             decoupled_weight_decay=bool(getattr(args, 'arch_decoupled_weight_decay', False)))
     if data_parallel_world(args) > 1:
         # one process per GPU: the unchanged mains pass cuda:0 to every rank
         # (main_darts_searchable_mmimdb.py:86), so the rank's own device comes from LOCAL_RANK,

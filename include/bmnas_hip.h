@@ -853,7 +853,7 @@ int bmnas_head_bwd_lazy_crit(const bmnas_lazy_ln_t* lazy, float* const* lnpart, 
 
 /* ---- multi-tensor Adam (row f2) ----------------------------------------------------------
  * One launch applies torch.optim.Adam's update (amsgrad off; L2 weight decay added to the
- * gradient) to every tensor of an optimizer — the w-step at train_searchable/mmimdb.py:101 and the
+ * gradient; bmnas_adam_multi_ex below has the other variants) to every tensor of an optimizer — the w-step at train_searchable/mmimdb.py:101 and the
  * alpha-step at architect.py:24, optimizers built at mmimdb_darts_searchable.py:28-33.
  *   tensors: DEVICE array of descriptors (device pointers, fp32; any alignment, any numel);
  *   chunks:  DEVICE array of n_chunks (tensor index, chunk index) int32 pairs, one workgroup each,
@@ -898,6 +898,36 @@ int bmnas_adam_multi_clip(const bmnas_adam_tensor_t* tensors, const int32_t* chu
 int bmnas_grad_scale_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
                            const float* partials, int n_parts, const float* clip, float* norm_out,
                            void* stream);
+
+/* ---- AMSGrad and decoupled weight decay (torch.optim.AdamW) in the same one launch -------------------------
+ * bmnas_adam_multi_ex: bmnas_adam_multi / bmnas_adam_multi_clip with two switches in `flags`, the arithmetic of
+ * torch 2.10's _single_tensor_adam per element:
+ *     BMNAS_ADAM_DECOUPLED:  p = p * f                         (a product of its own: f == 1 leaves the undecayed bits)
+ *     otherwise, wd != 0:    g = g + wd * p
+ *     m = lerp(m, g, 1 - beta1);   v = v * beta2 + (1 - beta2) * g * g
+ *     BMNAS_ADAM_AMSGRAD:    vmax = maximum(vmax, v)           (NaN-propagating, as torch.maximum)
+ *                            denom = sqrt(vmax) / sqrt(bc2) + eps
+ *     otherwise:             denom = sqrt(v) / sqrt(bc2) + eps
+ *     p = p + (-(lr / bc1)) * (m / denom)
+ *   hyp: the 8-float rows of bmnas_adam_multi.  Slot 5 has two meanings: `weight_decay` without
+ *     BMNAS_ADAM_DECOUPLED, and f = float(1 - lr * weight_decay) — the product formed in double by the host, 1 when
+ *     weight_decay is 0 — with it.  In decoupled mode the decay never touches the gradient.
+ *   max_exp_avg_sq: DEVICE array of one float* per descriptor of `tensors` (same order), the fp32 running maximum of
+ *     each tensor (any alignment); required with BMNAS_ADAM_AMSGRAD and NULL without it.  bmnas_adam_tensor_t is
+ *     unchanged: the norm launch and the stand-alone clip share it.
+ *   partials / n_parts / clip / norm_out: as for bmnas_adam_multi_clip; the launch clips iff partials != NULL (the
+ *     coefficient multiplies the gradient first), and the three pointers are all set or all NULL.
+ *   Reads param, grad, exp_avg, exp_avg_sq (+ the running maximum); writes param, exp_avg, exp_avg_sq (+ the running
+ *   maximum, + norm_out when clipping): 28 B per parameter, 36 B with BMNAS_ADAM_AMSGRAD.  `.grad` is NOT written.
+ *   flags == 0 is valid and runs the kernels of bmnas_adam_multi / bmnas_adam_multi_clip.
+ *   BMNAS_E_ARG (nothing launched): unknown flag bits; BMNAS_ADAM_AMSGRAD without max_exp_avg_sq or max_exp_avg_sq
+ *   without the flag; partials / clip / norm_out not all set or all NULL; an n_parts that is not the G of the norm
+ *   launch. */
+#define BMNAS_ADAM_AMSGRAD   1
+#define BMNAS_ADAM_DECOUPLED 2
+int bmnas_adam_multi_ex(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                        const float* hyp, float* const* max_exp_avg_sq, int flags,
+                        const float* partials, int n_parts, const float* clip, float* norm_out, void* stream);
 
 /* ---- a batch into a captured step's static tensors (bmnas.graph._copy_batch_in) -------------------
  * The reference hands every batch over with `.to(device)` per tensor (train_searchable/mmimdb.py:60-63,
