@@ -123,13 +123,15 @@ class GraphedTrainStep:
       arch_parameters for the alpha phase); their gradients come from torch.autograd.grad, so no
       other leaf's .grad is touched — the stepped tensors end up exactly as after
       zero_grad + backward + step.
-    * `optimizer`: a bmnas.optim.Adam (its step is capturable; per-batch learning rates and bias
-      corrections stay exact: the scalars of a replay, 32 bytes per row, travel BY VALUE in the
-      kernel arguments of the launch that copies the batch into the step's static tensors —
-      `Adam.replay_blob()`, bmnas_copy_batch — so the captured step holds no H2D copy node and the
-      host never waits for the previous replay.  Optimizers with more scalar rows than that blob
-      holds (> 8) fall back to a copy node fed from a pinned staging buffer, guarded by
-      `wait_staging()`).
+    * `optimizer`: a bmnas.optim.Adam / AdamW or a bmnas.optim.SGD.  Their step is capturable, and
+      this class drives it through their capture protocol only (capture_safe, captured_plan,
+      activate, prepare_replay, replay_blob, staged_lrs, wait_staging / mark_launched).  Per-batch
+      learning rates (and Adam's bias corrections, SGD's first-step rule) stay exact: the scalars of
+      a replay, 32 bytes per row, travel BY VALUE in the kernel arguments of the launch that copies
+      the batch into the step's static tensors — the optimizer's `replay_blob()`, bmnas_copy_batch —
+      so the captured step holds no H2D copy node and the host never waits for the previous replay.
+      Optimizers with more scalar rows than that blob holds (> 8) fall back to a copy node fed from
+      a pinned staging buffer, guarded by `wait_staging()`.
     * Data parallel (optimizer passed through bmnas.dist.attach, world size > 1): the captured step
       writes the gradients straight into the reducer's flat bucket.  Under an RCCL process group the
       all-reduce(avg) of the bucket is a launch INSIDE the captured step (`bmnas_allreduce_f32`

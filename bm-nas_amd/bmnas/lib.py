@@ -255,6 +255,7 @@ SIGNATURES = {
     'bmnas_adam_multi_clip': ([_P, _P, _I, _P, _P, _I, _P, _P, _P], _I),
     'bmnas_adam_multi_ex': ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_grad_scale_multi': ([_P, _P, _I, _P, _I, _P, _P, _P], _I),
+    'bmnas_sgd_multi': ([_P, _P, _I, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_copy_batch_max': ([], _I),
     'bmnas_copy_blob_max': ([], _I),
     'bmnas_copy_batch': ([_PP, _PP, C.POINTER(C.c_longlong), _I, _P, _P, _I, _P, C.c_ulonglong, _P], _I),
@@ -1151,6 +1152,19 @@ def grad_scale_multi(table, chunks, n_chunks, partials, n_parts, clip, norm_out)
     """grad *= the same coefficient, in place."""
     _check(load().bmnas_grad_scale_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, _ptr(partials), n_parts,
                                          clip.data_ptr(), norm_out.data_ptr(), _stream()), 'grad_scale_multi')
+
+
+SGD_MOMENTUM, SGD_NESTEROV = 1, 2            # BMNAS_SGD_* (include/bmnas_hip.h)
+
+
+def sgd_multi(table, chunks, n_chunks, hyp, flags, partials=None, n_parts=0, clip=None, norm_out=None):
+    """torch.optim.SGD's update of every tensor of `table` (bmnas_adam_tensor_t[]: exp_avg is the momentum buffer,
+    exp_avg_sq unused) in one launch; flags = SGD_MOMENTUM | SGD_NESTEROV.  hyp: float32 device (rows, 8) holding
+    { -lr, mu, 1 - dampening, mu_n, weight_decay, 0, 0, 0 } (a first-step row: mu = 0, damp1 = 1 over a zero buffer).
+    Clips iff partials is given (then clip and norm_out too, as for adam_multi_clip).  `.grad` is NOT written."""
+    p = lambda t: None if t is None else t.data_ptr()
+    _check(load().bmnas_sgd_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), int(flags),
+                                  p(partials), n_parts, p(clip), p(norm_out), _stream()), 'sgd_multi')
 
 
 def copy_blob_max():

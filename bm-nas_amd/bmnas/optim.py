@@ -23,6 +23,13 @@ single launch (`bmnas_adam_multi_ex`; with both off the launches are `bmnas_adam
 before).  AMSGrad keeps torch's per-parameter `max_exp_avg_sq`; its pointers ride behind the descriptor table in the
 staging buffer.  Decoupled decay stages float(1 - lr * weight_decay) where the L2 mode stages weight_decay.  One launch
 is one kernel instantiation: all groups of an optimizer must agree on each switch.
+
+`SGD` is torch.optim.SGD (momentum, dampening, nesterov, L2 weight decay; DARTS' weight optimizer, reference
+models/search/darts/train_search.py:84-88) on the same machinery: the descriptor table, chunk list, staging buffer,
+by-value scalar rows and norm launch are Adam's, the update is one `bmnas_sgd_multi` launch, and `max_grad_norm` means
+what it means for Adam.  `_OneLaunch` holds what the two classes share; each class says which state tensors a descriptor
+points at (`_state_ptrs`), what a scalar row holds (`_build`'s row key, `prepare_replay`) and which launch to issue
+(`_launch`).
 """
 import math
 
@@ -37,24 +44,11 @@ _DESC = np.dtype([('param', '<u8'), ('grad', '<u8'), ('exp_avg', '<u8'), ('exp_a
 assert _DESC.itemsize == 48
 
 
-class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
-                 max_grad_norm=None, *, decoupled_weight_decay=False):
-        """amsgrad / decoupled_weight_decay: torch.optim.Adam's, stored in `param_groups` under torch's keys and read from
-        there when a plan is built (a loaded checkpoint's values count); every group must hold the same value of each.
-        They may be edited between eager steps (the plan is rebuilt) but not under a captured plan.
-        max_grad_norm (None or a positive float): clip the global L2 norm over every parameter of the optimizer that has
-        a gradient, all groups together, before the update.  An attribute, not a `param_groups` entry (state_dict() stays
-        that of torch.optim.Adam); it may be edited between steps and replays — it travels with the per-step scalars —
-        but not switched between None and a value under a captured plan.  `.grad` is left UNCLIPPED: the scaling happens
-        in the update's registers.  `last_grad_norm` / `grad_norms` hold the pre-clip norm(s) on the device."""
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad),
-                         decoupled_weight_decay=bool(decoupled_weight_decay))
-        self.max_grad_norm = max_grad_norm
-        self._clip_value()
-        self._plan = None
-        self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
-        self._touch = 0          # bumped by everything that may re-point .grad or move the step counts outside a replay
+class _OneLaunch:
+    """What bmnas.optim.Adam and bmnas.optim.SGD share: the eager step over a plan, the captured plan and its replay
+    protocol (capture_safe / captured_plan / activate / prepare_replay / replay_blob / wait_staging / mark_launched),
+    and max_grad_norm.  Mixed in FRONT of the torch optimizer class.  The class supplies `_NAME`, `_variant()` (the key
+    of a plan, clipping first), `_build(active, slots)`, `_switch(plan)`, `_launch(slot)` and `prepare_replay(slot)`."""
 
     def _clip_value(self):
         """max_grad_norm as a float (validated), or None."""
@@ -62,7 +56,7 @@ class Adam(torch.optim.Adam):
         if c is None:
             return None
         if isinstance(c, bool) or not isinstance(c, (int, float)) or not c > 0:
-            raise lib.BmnasError(f'bmnas.optim.Adam: max_grad_norm must be None or a positive float, got {c!r}')
+            raise lib.BmnasError(f'{self._NAME}: max_grad_norm must be None or a positive float, got {c!r}')
         return float(c)
 
     @property
@@ -82,6 +76,186 @@ class Adam(torch.optim.Adam):
     # ------------------------------------------------------------------ plan
     def _active(self):
         return [(p, gi) for gi, g in enumerate(self.param_groups) for p in g['params'] if p.grad is not None]
+
+    def _stage(self, active):
+        """Advance the step counts; write this step's scalars and pointers into the staging buffer."""
+        self.prepare_replay()
+        self._write_ptrs(active)
+
+    def _write_ptrs(self, active, slot=0):
+        grads = [p.grad for p, _ in active]
+        for gr, (p, _) in zip(grads, active):
+            if gr.dtype != torch.float32 or not gr.is_contiguous() or gr.device != p.device:
+                raise lib.BmnasError(f'{self._NAME}: gradients must be contiguous fp32 on the parameter device')
+        tab = self._plan['tabs'][slot]
+        tab['param'] = [p.data_ptr() for p, _ in active]
+        tab['grad'] = [gr.data_ptr() for gr in grads]
+
+    def wait_staging(self):
+        """Block until the last launch has consumed the pinned staging buffer (the host may run
+        ahead of the GPU; rewriting the buffer earlier would change a step still in flight)."""
+        if self._plan is not None and self._plan.get('event') is not None:
+            self._plan['event'].synchronize()
+
+    def mark_launched(self, force=False):
+        """Record, on the current stream, that everything queued so far (a step() or a graph
+        replay that contains one) has read the staging buffer.  (Poke-mode plans: their replays do not read it —
+        nothing to record, and nothing for the next call to wait for: the host may run ahead of the GPU.)"""
+        pl = self._plan
+        if pl.get('poke') and not force:
+            return
+        if pl.get('event') is None:
+            pl['event'] = torch.cuda.Event()
+        pl['event'].record()
+
+    # ------------------------------------------------------------------ torch.optim API
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        active = self._active()
+        if not active:
+            return loss
+        key = self._variant()                   # (first: groups that disagree on a switch are refused before anything moves)
+        self._touch += 1
+        if torch.cuda.is_current_stream_capturing():
+            if self._plan is None or self._plan['ids'] != tuple(id(p) for p, _ in active) or self._plan['key'] != key:
+                raise lib.BmnasError(f'{self._NAME}: call capture_safe() before capturing step() in a graph')
+            slot = self._plan['cap_slot']
+            if slot >= self._plan['slots']:
+                raise lib.BmnasError(f'{self._NAME}: more captured steps than capture_safe(slots=...) planned')
+            self._write_ptrs(active, slot)      # the capture's static gradient tensors (of THIS step of the graph)
+            self._plan['active'] = active
+            self._plan.setdefault('slot_grads', {})[slot] = [p.grad for p, _ in active]
+            self._launch(slot)                  # scalars are refreshed by prepare_replay()
+            self._plan['cap_slot'] = slot + 1
+            return loss
+        ids = tuple(id(p) for p, _ in active)
+        if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids or self._plan['key'] != key:
+            # never stage an eager step through a captured plan: its graph re-reads those buffers
+            eager = getattr(self, '_eager_plan', None)
+            if eager is not None and eager['ids'] == ids and eager['key'] == key:
+                self._switch(eager)
+            else:
+                self._build(active)
+                self._eager_plan = self._plan
+        if self._plan['gen'] != self._gen:
+            self._switch(self._plan)
+        self.wait_staging()
+        self._stage(active)
+        self._launch()
+        self.mark_launched()
+        return loss
+
+    def zero_grad(self, set_to_none=True):
+        self._touch += 1         # .grad re-pointed / dropped: a captured plan re-attaches its static tensors next time
+        return super().zero_grad(set_to_none)
+
+    # ------------------------------------------------------------------ hipGraph support
+    def capture_safe(self, poke=False, slots=1):
+        """Build a plan OF ITS OWN from the gradients that exist NOW (static tensors of the step
+        being captured) so that step() inside `torch.cuda.graph` issues only stream work: one
+        pinned H2D copy and one launch.  The captured graph keeps reading this plan's staging
+        buffers, so the plan is never reused for eager steps: take it with `captured_plan()` after
+        the capture and call `activate(plan)` + `prepare_replay()` before every replay."""
+        active = self._active()
+        self.wait_staging()
+        self._build(active, slots)
+        self._write_ptrs(active)
+        self._plan['captured'] = True
+        # "poke" mode (round 5): the captured step holds NO H2D copy node.  The descriptor table is uploaded once after the
+        # capture (and again whenever activate() / load_state_dict changed it); the per-step scalars — 32 bytes per row —
+        # travel by value in the launch that copies the batch into the step's static tensors (bmnas_copy_batch's blob,
+        # replay_blob()).  A captured copy node cost 4.7 us per optimizer step.
+        self._plan['poke'] = bool(poke) and self._plan['hyp_all'].nbytes <= lib.copy_blob_max()
+        if slots > 1 and not self._plan['poke']:
+            raise lib.BmnasError(f'{self._NAME}: {slots} captured steps x {len(self._plan["groups"])} scalar rows do not '
+                                 'fit the by-value blob of the batch-copy launch')
+
+    def captured_plan(self):
+        """The plan a capture has just baked into a graph, with the pointer table as captured
+        (parameters, static gradient tensors) snapshotted."""
+        pl = self._plan
+        if pl is None or not pl.get('captured'):
+            raise lib.BmnasError(f'{self._NAME}: no captured plan (capture_safe() + a captured step() first)')
+        if pl['cap_slot'] != pl['slots']:
+            raise lib.BmnasError(f'{self._NAME}: the capture holds {pl["cap_slot"]} step(s), the plan was built for '
+                                 f'{pl["slots"]}')
+        pl['snap_param'] = [t['param'].copy() for t in pl['tabs']]
+        pl['snap_grad'] = [t['grad'].copy() for t in pl['tabs']]
+        # keeps every slot's static gradient tensors alive; .grad is re-attached to the LAST step's (what a sequence of
+        # eager steps leaves behind)
+        pl['static_grads'] = pl['slot_grads'][pl['slots'] - 1]
+        pl['tab_dirty'] = True                                       # poke mode: upload before the first replay
+        return pl
+
+    def replay_blob(self):
+        """Poke mode, after prepare_replay(): -> (device tensor, host bytes) of this replay's scalar rows for
+        bmnas_copy_batch's blob; uploads the descriptor table first when it changed (eagerly, on the current stream, i.e.
+        in front of the replay).  None: the captured step carries its own H2D copy node."""
+        pl = self._plan
+        if not pl.get('poke'):
+            return None
+        if pl.get('tab_dirty'):
+            self.wait_staging()
+            pl['dev'].copy_(pl['pin'], non_blocking=True)
+            self.mark_launched(force=True)       # the pinned buffer must not be rewritten before this copy has read it
+            self.wait_staging()                  # (rare: once after a capture / load_state_dict)
+            pl['tab_dirty'] = False
+        h = pl['hyp_all']
+        return pl['dev_hyp'][:h.nbytes], h.tobytes()
+
+    def activate(self, plan):
+        """Make `plan` (from captured_plan()) the current one before its graph is replayed.  Eager
+        steps in between — a ragged last batch, the Architect's eager path — run on a plan of their
+        own, so the staging buffers the graph reads are intact; but they advanced the step counts
+        and re-pointed `.grad`.  The counts are carried over, the capture-time parameter / gradient
+        pointers are restored and `.grad` is re-attached to the static tensors the graph writes."""
+        # fast path (every replay of a training loop): this plan is current, no eager step / zero_grad / load_state_dict
+        # happened since its last activation — nothing to restore
+        if self._plan is plan and plan['gen'] == self._gen and plan.get('stamp') == self._touch:
+            if not plan.get('poke'):
+                # the captured step carries an H2D copy node that reads this plan's pinned staging buffer (capture_safe()
+                # without poke, or more scalar rows than the blob holds): prepare_replay() is about to rewrite that
+                # buffer, so the previous replay's copy must have read it first
+                self.wait_staging()
+            return
+        gen = plan['gen']
+        self._switch(plan)
+        if plan['gen'] != gen:
+            plan['tab_dirty'] = True             # load_state_dict replaced the moment tensors: new pointers in the table
+        for tab, sp, sg in zip(plan['tabs'], plan['snap_param'], plan['snap_grad']):
+            if plan.get('poke') and ((tab['param'] != sp).any() or (tab['grad'] != sg).any()):
+                plan['tab_dirty'] = True
+            tab['param'] = sp
+            tab['grad'] = sg
+        for (p, _), gr in zip(plan['active'], plan['static_grads']):
+            p.grad = gr
+        plan['stamp'] = self._touch
+
+
+class Adam(_OneLaunch, torch.optim.Adam):
+    _NAME = 'bmnas.optim.Adam'
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
+                 max_grad_norm=None, *, decoupled_weight_decay=False):
+        """amsgrad / decoupled_weight_decay: torch.optim.Adam's, stored in `param_groups` under torch's keys and read from
+        there when a plan is built (a loaded checkpoint's values count); every group must hold the same value of each.
+        They may be edited between eager steps (the plan is rebuilt) but not under a captured plan.
+        max_grad_norm (None or a positive float): clip the global L2 norm over every parameter of the optimizer that has
+        a gradient, all groups together, before the update.  An attribute, not a `param_groups` entry (state_dict() stays
+        that of torch.optim.Adam); it may be edited between steps and replays — it travels with the per-step scalars —
+        but not switched between None and a value under a captured plan.  `.grad` is left UNCLIPPED: the scaling happens
+        in the update's registers.  `last_grad_norm` / `grad_norms` hold the pre-clip norm(s) on the device."""
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad),
+                         decoupled_weight_decay=bool(decoupled_weight_decay))
+        self.max_grad_norm = max_grad_norm
+        self._clip_value()
+        self._plan = None
+        self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
+        self._touch = 0          # bumped by everything that may re-point .grad or move the step counts outside a replay
 
     def _variant(self):
         """-> (clip, amsgrad, decoupled): what selects the launches of a step, the key of a plan.  The two switches are
@@ -208,20 +382,6 @@ class Adam(torch.optim.Adam):
                 dev_clips=[devbuf[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4] for i in range(slots)],
                 norms=torch.zeros(slots, dtype=torch.float32, device=dev))
 
-    def _stage(self, active):
-        """Advance the step counts; write this step's scalars and pointers into the staging buffer."""
-        self.prepare_replay()
-        self._write_ptrs(active)
-
-    def _write_ptrs(self, active, slot=0):
-        grads = [p.grad for p, _ in active]
-        for gr, (p, _) in zip(grads, active):
-            if gr.dtype != torch.float32 or not gr.is_contiguous() or gr.device != p.device:
-                raise lib.BmnasError('bmnas.optim.Adam: gradients must be contiguous fp32 on the parameter device')
-        tab = self._plan['tabs'][slot]
-        tab['param'] = [p.data_ptr() for p, _ in active]
-        tab['grad'] = [gr.data_ptr() for gr in grads]
-
     def _launch(self, slot=0):
         pl = self._plan
         if not pl.get('poke') and slot == 0:
@@ -241,68 +401,6 @@ class Adam(torch.optim.Adam):
         else:
             lib.adam_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot])
 
-    def wait_staging(self):
-        """Block until the last launch has consumed the pinned staging buffer (the host may run
-        ahead of the GPU; rewriting the buffer earlier would change a step still in flight)."""
-        if self._plan is not None and self._plan.get('event') is not None:
-            self._plan['event'].synchronize()
-
-    def mark_launched(self, force=False):
-        """Record, on the current stream, that everything queued so far (a step() or a graph
-        replay that contains one) has read the staging buffer.  (Poke-mode plans: their replays do not read it —
-        nothing to record, and nothing for the next call to wait for: the host may run ahead of the GPU.)"""
-        pl = self._plan
-        if pl.get('poke') and not force:
-            return
-        if pl.get('event') is None:
-            pl['event'] = torch.cuda.Event()
-        pl['event'].record()
-
-    # ------------------------------------------------------------------ torch.optim API
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        active = self._active()
-        if not active:
-            return loss
-        key = self._variant()                   # (first: groups that disagree on a switch are refused before anything moves)
-        self._touch += 1
-        if torch.cuda.is_current_stream_capturing():
-            if self._plan is None or self._plan['ids'] != tuple(id(p) for p, _ in active) or self._plan['key'] != key:
-                raise lib.BmnasError('bmnas.optim.Adam: call capture_safe() before capturing step() in a graph')
-            slot = self._plan['cap_slot']
-            if slot >= self._plan['slots']:
-                raise lib.BmnasError('bmnas.optim.Adam: more captured steps than capture_safe(slots=...) planned')
-            self._write_ptrs(active, slot)      # the capture's static gradient tensors (of THIS step of the graph)
-            self._plan['active'] = active
-            self._plan.setdefault('slot_grads', {})[slot] = [p.grad for p, _ in active]
-            self._launch(slot)                  # scalars are refreshed by prepare_replay()
-            self._plan['cap_slot'] = slot + 1
-            return loss
-        ids = tuple(id(p) for p, _ in active)
-        if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids or self._plan['key'] != key:
-            # never stage an eager step through a captured plan: its graph re-reads those buffers
-            eager = getattr(self, '_eager_plan', None)
-            if eager is not None and eager['ids'] == ids and eager['key'] == key:
-                self._switch(eager)
-            else:
-                self._build(active)
-                self._eager_plan = self._plan
-        if self._plan['gen'] != self._gen:
-            self._switch(self._plan)
-        self.wait_staging()
-        self._stage(active)
-        self._launch()
-        self.mark_launched()
-        return loss
-
-    def zero_grad(self, set_to_none=True):
-        self._touch += 1         # .grad re-pointed / dropped: a captured plan re-attaches its static tensors next time
-        return super().zero_grad(set_to_none)
-
     def state_dict(self):
         self._flush_counts()
         return super().state_dict()
@@ -317,60 +415,6 @@ class Adam(torch.optim.Adam):
         self._plan = None
         self._eager_plan = None
         self._gen += 1
-
-    # ------------------------------------------------------------------ hipGraph support
-    def capture_safe(self, poke=False, slots=1):
-        """Build a plan OF ITS OWN from the gradients that exist NOW (static tensors of the step
-        being captured) so that step() inside `torch.cuda.graph` issues only stream work: one
-        pinned H2D copy and one launch.  The captured graph keeps reading this plan's staging
-        buffers, so the plan is never reused for eager steps: take it with `captured_plan()` after
-        the capture and call `activate(plan)` + `prepare_replay()` before every replay."""
-        active = self._active()
-        self.wait_staging()
-        self._build(active, slots)
-        self._write_ptrs(active)
-        self._plan['captured'] = True
-        # "poke" mode (round 5): the captured step holds NO H2D copy node.  The descriptor table is uploaded once after the
-        # capture (and again whenever activate() / load_state_dict changed it); the per-step scalars — 32 bytes per row —
-        # travel by value in the launch that copies the batch into the step's static tensors (bmnas_copy_batch's blob,
-        # replay_blob()).  A captured copy node cost 4.7 us per optimizer step.
-        self._plan['poke'] = bool(poke) and self._plan['hyp_all'].nbytes <= lib.copy_blob_max()
-        if slots > 1 and not self._plan['poke']:
-            raise lib.BmnasError(f'bmnas.optim.Adam: {slots} captured steps x {len(self._plan["groups"])} scalar rows do not '
-                                 'fit the by-value blob of the batch-copy launch')
-
-    def captured_plan(self):
-        """The plan a capture has just baked into a graph, with the pointer table as captured
-        (parameters, static gradient tensors) snapshotted."""
-        pl = self._plan
-        if pl is None or not pl.get('captured'):
-            raise lib.BmnasError('bmnas.optim.Adam: no captured plan (capture_safe() + a captured step() first)')
-        if pl['cap_slot'] != pl['slots']:
-            raise lib.BmnasError(f'bmnas.optim.Adam: the capture holds {pl["cap_slot"]} step(s), the plan was built for '
-                                 f'{pl["slots"]}')
-        pl['snap_param'] = [t['param'].copy() for t in pl['tabs']]
-        pl['snap_grad'] = [t['grad'].copy() for t in pl['tabs']]
-        # keeps every slot's static gradient tensors alive; .grad is re-attached to the LAST step's (what a sequence of
-        # eager steps leaves behind)
-        pl['static_grads'] = pl['slot_grads'][pl['slots'] - 1]
-        pl['tab_dirty'] = True                                       # poke mode: upload before the first replay
-        return pl
-
-    def replay_blob(self):
-        """Poke mode, after prepare_replay(): -> (device tensor, host bytes) of this replay's scalar rows for
-        bmnas_copy_batch's blob; uploads the descriptor table first when it changed (eagerly, on the current stream, i.e.
-        in front of the replay).  None: the captured step carries its own H2D copy node."""
-        pl = self._plan
-        if not pl.get('poke'):
-            return None
-        if pl.get('tab_dirty'):
-            self.wait_staging()
-            pl['dev'].copy_(pl['pin'], non_blocking=True)
-            self.mark_launched(force=True)       # the pinned buffer must not be rewritten before this copy has read it
-            self.wait_staging()                  # (rare: once after a capture / load_state_dict)
-            pl['tab_dirty'] = False
-        h = pl['hyp_all']
-        return pl['dev_hyp'][:h.nbytes], h.tobytes()
 
     def _switch(self, plan):
         """Make `plan` current: step counts travel through the per-parameter `step` tensors, the
@@ -391,34 +435,6 @@ class Adam(torch.optim.Adam):
         if plan['gen'] != self._gen:
             self._state_ptrs(plan)
             plan['gen'] = self._gen
-
-    def activate(self, plan):
-        """Make `plan` (from captured_plan()) the current one before its graph is replayed.  Eager
-        steps in between — a ragged last batch, the Architect's eager path — run on a plan of their
-        own, so the staging buffers the graph reads are intact; but they advanced the step counts
-        and re-pointed `.grad`.  The counts are carried over, the capture-time parameter / gradient
-        pointers are restored and `.grad` is re-attached to the static tensors the graph writes."""
-        # fast path (every replay of a training loop): this plan is current, no eager step / zero_grad / load_state_dict
-        # happened since its last activation — nothing to restore
-        if self._plan is plan and plan['gen'] == self._gen and plan.get('stamp') == self._touch:
-            if not plan.get('poke'):
-                # the captured step carries an H2D copy node that reads this plan's pinned staging buffer (capture_safe()
-                # without poke, or more scalar rows than the blob holds): prepare_replay() is about to rewrite that
-                # buffer, so the previous replay's copy must have read it first
-                self.wait_staging()
-            return
-        gen = plan['gen']
-        self._switch(plan)
-        if plan['gen'] != gen:
-            plan['tab_dirty'] = True             # load_state_dict replaced the moment tensors: new pointers in the table
-        for tab, sp, sg in zip(plan['tabs'], plan['snap_param'], plan['snap_grad']):
-            if plan.get('poke') and ((tab['param'] != sp).any() or (tab['grad'] != sg).any()):
-                plan['tab_dirty'] = True
-            tab['param'] = sp
-            tab['grad'] = sg
-        for (p, _), gr in zip(plan['active'], plan['static_grads']):
-            p.grad = gr
-        plan['stamp'] = self._touch
 
     def prepare_replay(self, slot=0):
         """Advance the step count and publish the current learning rates for the next replay
@@ -471,6 +487,222 @@ class AdamW(Adam):
         super().__setstate__(state)
         for group in self.param_groups:
             group['decoupled_weight_decay'] = True
+
+
+class SGD(_OneLaunch, torch.optim.SGD):
+    """torch.optim.SGD with the update of every tensor in one `bmnas_sgd_multi` launch: the weight optimizer DARTS-style
+    searches run with (reference models/search/darts/train_search.py:84-88: SGD(lr, momentum, weight_decay), clipped at
+    :158).  Same constructor, `param_groups` and per-parameter state (`momentum_buffer` only) as torch's class, so
+    checkpoints travel both ways; `max_grad_norm` and the capture protocol are bmnas.optim.Adam's.
+
+    A scalar row is { -lr, mu, 1 - dampening, mu_n, weight_decay }: lr, momentum, dampening and weight_decay are per
+    group and may change between steps and replays.  torch's first step of a tensor (`buf = clone(g)`, no dampening) is a
+    ROW, not a kernel branch: mu = 0 and damp1 = 1 over a zero-filled buffer.  Rows are keyed by (group, first step or
+    not).  A tensor's next step is its first iff its state holds no `momentum_buffer`: the zero buffer a plan allocates
+    ahead of the step (capture_safe() must, the graph bakes its address) waits in `_pending` and enters `state` only
+    when a step that writes it is staged — state_dict() never shows an unstepped buffer as a stepped one.
+    One launch is one kernel: all groups agree on `momentum != 0` and on `nesterov`; `maximize` is refused."""
+    _NAME = 'bmnas.optim.SGD'
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=None, *,
+                 maximize=False):
+        if maximize:
+            raise lib.BmnasError('bmnas.optim.SGD: maximize=True is not supported (the kernel descends)')
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                         nesterov=bool(nesterov))
+        self.max_grad_norm = max_grad_norm
+        self._clip_value()
+        self._plan = None
+        self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
+        self._touch = 0          # bumped by everything that may re-point .grad outside a replay
+        self._pending = {}       # parameter -> zero momentum buffer that no staged step has written yet
+
+    def _variant(self):
+        """-> (clip, momentum != 0, nesterov): what selects the launches of a step, the key of a plan."""
+        return (self._clip_value() is not None,) + self._switches()
+
+    def _switches(self):
+        """-> (momentum != 0, nesterov) of the param_groups, which must agree on each; refuses `maximize`."""
+        first = None
+        for g in self.param_groups:
+            if g.get('maximize', False):
+                raise lib.BmnasError('bmnas.optim.SGD: maximize=True is not supported (the kernel descends)')
+            sw = (g['momentum'] != 0, bool(g.get('nesterov', False)))
+            if first is None:
+                first = sw
+            elif sw != first:
+                name = 'momentum' if sw[0] != first[0] else 'nesterov'
+                raise lib.BmnasError(f"bmnas.optim.SGD: param_groups disagree on '{name}'"
+                                     f"{' being zero' if name == 'momentum' else ''} (one launch updates every "
+                                     'group with one kernel: per-group mixing is not supported)')
+        return first or (False, False)
+
+    def _stepped(self, p):
+        """Whether a step has written p's momentum buffer (or a checkpoint restored one): its next step is no first one."""
+        st = self.state.get(p)
+        return st is not None and st.get('momentum_buffer') is not None
+
+    def _buffer(self, p):
+        """p's momentum buffer: the stepped one of `state`, else a zero buffer kept OUT of `state` until a step is staged."""
+        if self._stepped(p):
+            return self.state[p]['momentum_buffer']
+        if p not in self._pending:
+            self._pending[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return self._pending[p]
+
+    def _state_ptrs(self, plan):
+        """(Re)write the momentum-buffer pointers of every descriptor table of `plan` from the CURRENT tensors, validated
+        (without momentum: null, never dereferenced)."""
+        ptrs = []
+        for p, _ in plan['active']:
+            if not plan['momentum']:
+                ptrs.append(0)
+                continue
+            t = self._buffer(p)
+            if t.device != p.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                raise lib.BmnasError(f'bmnas.optim.SGD: momentum_buffer must be contiguous fp32 on {p.device}, of the '
+                                     "parameter's size")
+            ptrs.append(t.data_ptr())
+        for tab in plan['tabs']:
+            tab['exp_avg'] = ptrs
+            tab['exp_avg_sq'] = 0
+
+    def _build(self, active, slots=1):
+        """Adam._build's staging layout — scalar rows (+ max_grad_norm) per slot, then a descriptor table per slot, in ONE
+        pinned buffer and its device copy — with rows keyed by (group, first step or not); `count` of a row is how many
+        steps were staged for its tensors (0: the next one is their first)."""
+        clip, momentum, nesterov = self._variant()
+        dev = active[0][0].device
+        E = lib.adam_chunk_elems()
+        rows, row_idx, row_of, chunks = [], {}, [], []
+        for i, (p, gi) in enumerate(active):
+            if not p.is_cuda:
+                raise lib.BmnasError('bmnas.optim.SGD needs parameters on the GPU (HIP kernel, no CPU path)')
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise lib.BmnasError(f'bmnas.optim.SGD: parameter must be contiguous fp32 on {dev}')
+            key = (gi, 1.0 if not momentum or self._stepped(p) else 0.0)
+            if key not in row_idx:
+                row_idx[key] = len(rows)
+                rows.append(key)
+            row_of.append(row_idx[key])
+            chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
+        row_bytes = len(rows) * 32
+        hyp_slot = row_bytes + (16 if clip else 0)
+        hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
+        tab_bytes = len(active) * _DESC.itemsize
+        nbytes = hyp_bytes + slots * tab_bytes
+        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+        host = pin.numpy()
+        tabs = [host[hyp_bytes + i * tab_bytes:hyp_bytes + (i + 1) * tab_bytes].view(_DESC) for i in range(slots)]
+        for tab in tabs:
+            tab['numel'] = [p.numel() for p, _ in active]
+            tab['hyp_row'] = row_of
+        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        hyps = [host[i * hyp_slot:i * hyp_slot + row_bytes].view(np.float32).reshape(len(rows), 8) for i in range(slots)]
+        self._plan = dict(ids=tuple(id(p) for p, _ in active), active=active, row_of=row_of, gen=self._gen,
+                          groups=[gi for gi, _ in rows], count=[c for _, c in rows],
+                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * hyp_slot], tab=tabs[0], tabs=tabs,
+                          dev=devbuf, dev_hyp=devbuf[:hyp_bytes],
+                          dev_hyps=[devbuf[i * hyp_slot:(i + 1) * hyp_slot] for i in range(slots)],
+                          dev_tab=devbuf[hyp_bytes:hyp_bytes + tab_bytes],
+                          dev_tabs=[devbuf[hyp_bytes + i * tab_bytes:hyp_bytes + (i + 1) * tab_bytes]
+                                    for i in range(slots)],
+                          chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev),
+                          n_chunks=len(chunks), slots=slots, cap_slot=0, clip=clip, momentum=momentum,
+                          nesterov=nesterov, key=(clip, momentum, nesterov),
+                          flags=(lib.SGD_MOMENTUM if momentum else 0) | (lib.SGD_NESTEROV if nesterov else 0))
+        self._state_ptrs(self._plan)
+        if clip:
+            parts = lib.grad_norm_parts()
+            self._plan.update(
+                n_parts=min(len(chunks), parts),
+                partials=[torch.empty(parts, dtype=torch.float32, device=dev) for _ in range(slots)],
+                clips=[host[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4].view(np.float32) for i in range(slots)],
+                dev_clips=[devbuf[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4] for i in range(slots)],
+                norms=torch.zeros(slots, dtype=torch.float32, device=dev))
+
+    def _stage(self, active):
+        """The gradients are validated (and their pointers written) FIRST: prepare_replay() moves the pending zero
+        buffers into `state`, and a step refused after that — a non-contiguous or non-fp32 gradient — would leave an
+        unstepped buffer shown as a stepped one."""
+        self._write_ptrs(active)
+        self.prepare_replay()
+
+    def _launch(self, slot=0):
+        pl = self._plan
+        if not pl.get('poke') and slot == 0:
+            pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
+        if pl['clip']:
+            lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
+            lib.sgd_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], pl['flags'],
+                          pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
+        else:
+            lib.sgd_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], pl['flags'])
+
+    def load_state_dict(self, state_dict):
+        if any(g.get('maximize', False) for g in state_dict['param_groups']):
+            raise lib.BmnasError('bmnas.optim.SGD: the checkpoint has maximize=True, which is not supported (the kernel '
+                                 'descends)')
+        super().load_state_dict(state_dict)
+        # the buffers are new objects (or gone: a checkpoint from before the first step): eager steps rebuild their plan,
+        # a captured plan re-reads pointers and first-step status in activate()
+        self._pending = {}
+        self._plan = None
+        self._eager_plan = None
+        self._gen += 1
+
+    def _switch(self, plan):
+        """Make `plan` current: whether a row's next step is a first one is re-read from the state, the buffer pointers
+        are re-read when load_state_dict() replaced the state tensors."""
+        if self._plan is not plan:
+            counts = {}
+            for (p, _), r in zip(plan['active'], plan['row_of']):
+                c = 1.0 if not plan['momentum'] or self._stepped(p) else 0.0
+                if counts.setdefault(r, c) != c:
+                    raise lib.BmnasError('bmnas.optim.SGD: parameters that shared their first-step status when this plan '
+                                         'was built have diverged (an eager step on a subset?); re-capture the graph')
+            for r, c in counts.items():
+                plan['count'][r] = c
+            self._plan = plan
+        if not plan.get('poke'):
+            self.wait_staging()              # the plan's last launch has consumed its pinned buffer
+        if plan['gen'] != self._gen:
+            self._state_ptrs(plan)
+            plan['gen'] = self._gen
+
+    def prepare_replay(self, slot=0):
+        """Publish the current learning rates, momenta, dampenings and weight decays for the next step or replay, and
+        count it: a row whose tensors have not stepped gets torch's first-step rule (mu = 0, damp1 = 1 over the zero
+        buffer), and their buffers enter `state` — the step staged here writes them.  slot: as for Adam."""
+        pl = self._plan
+        h = pl['hyps'][slot]
+        c = self._clip_value()
+        if (c is not None) != pl['clip']:
+            raise lib.BmnasError('bmnas.optim.SGD: max_grad_norm was switched between None and a value under a plan built '
+                                 'for the other (a captured step holds the launches of one of them); re-capture the graph')
+        if self._switches() != pl['key'][1:]:
+            raise lib.BmnasError("bmnas.optim.SGD: 'momentum' was switched between zero and non-zero, or 'nesterov' was "
+                                 'switched, under a plan built for the other value (a captured step holds the launches of '
+                                 'one of them); re-capture the graph')
+        if c is not None:
+            pl['clips'][slot][0] = c
+        for r, gi in enumerate(pl['groups']):
+            g = self.param_groups[gi]
+            mu = float(g['momentum'])
+            first = pl['momentum'] and pl['count'][r] == 0
+            pl['count'][r] += 1.0
+            h[r] = (-float(g['lr']), 0.0 if first else mu, 1.0 if first else 1 - g['dampening'], mu,
+                    float(g['weight_decay']), 0.0, 0.0, 0.0)
+        if pl['momentum'] and self._pending:
+            for p, _ in pl['active']:
+                if p in self._pending:
+                    self.state[p]['momentum_buffer'] = self._pending.pop(p)
+
+    def staged_lrs(self, slot=0):
+        """The learning rate of every scalar row of `slot`, as prepare_replay() STAGED it (the fp32 value the launch of
+        that step reads)."""
+        pl = self._plan
+        return [float(-pl['hyps'][slot][r][0]) for r in range(len(pl['groups']))]
 
 
 _CLIP_CACHE = {}

@@ -18,6 +18,18 @@
 // refreshes before every launch: a captured hipGraph replays with new learning rates / step
 // counts without re-capture.
 // HBM-streaming: 4 reads + 3 writes per element = 28 B/param; amsgrad: 5 reads + 4 writes = 36 B/param.
+//
+// Multi-tensor SGD with momentum (bmnas_sgd_multi; the weight optimizer of the DARTS drivers, reference
+// models/search/darts/train_search.py:84-88 and train.py:78, clipped at train_search.py:158) walks the same descriptor
+// table, chunk list and 8-float rows.  Arithmetic = torch.optim.SGD (torch 2.10's _single_tensor_sgd; maximize off),
+// operation by operation, every operation rounded on its own:
+//   g   = c * grad                                   (clipping only)
+//   g   = g + wd * p                                 (only if wd != 0)
+//   buf = buf * mu + damp1 * g                       (momentum; torch's first step, buf = clone(g), is the row
+//                                                     mu = 0, damp1 = 1 over a zero-filled buffer: no branch)
+//   g   = nesterov ? g + mu_n * buf : buf
+//   p   = p + neg_lr * g
+// HBM-streaming: 2 reads + 1 write per element = 12 B/param; with momentum 3 reads + 2 writes = 20 B/param.
 #include "common.hpp"
 #include <cstring>
 #include "../../include/bmnas_hip.h"
@@ -210,6 +222,82 @@ __global__ __launch_bounds__(256) void grad_scale_multi_k(const bmnas_adam_tenso
   }
 }
 
+// ---- multi-tensor SGD (torch.optim.SGD) ---------------------------------------------------------------------------
+// A row of `hyp`: { -lr, mu, 1 - dampening, mu_n, weight_decay, 0, 0, 0 }.  mu multiplies the buffer, mu_n the nesterov
+// term: both are the group's momentum, except in a first-step row (mu = 0, damp1 = 1: buf = 0 * 0 + 1 * g = g).
+struct SgdHyp {
+  float neg_lr, mu, damp1, mu_n, wd;
+};
+
+// No contraction anywhere in the update: torch issues every operation as a launch of its own, each rounded once, and a
+// term that is switched off by its scalar (damp1 == 1, c == 1) must leave the bits of the sequence without it —
+// fma(damp1, g, buf * mu) would round differently from buf * mu + g.
+template <bool MOMENTUM, bool NESTEROV>
+__device__ __forceinline__ void sgd1(float& p, float g, float& buf, const SgdHyp& h) {
+#pragma clang fp contract(off)
+  if (h.wd != 0.f) g = g + h.wd * p;
+  if constexpr (MOMENTUM) {
+    buf = buf * h.mu + h.damp1 * g;
+    g = NESTEROV ? g + h.mu_n * buf : buf;
+  }
+  p = p + h.neg_lr * g;
+}
+
+// One workgroup's chunk, as adam_chunk.  exp_avg of a descriptor is the momentum buffer; exp_avg_sq is not read, and
+// with MOMENTUM false neither is exp_avg (both may be null).
+template <bool CLIP, bool MOMENTUM, bool NESTEROV>
+__device__ __forceinline__ void sgd_chunk(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                          const int32_t* __restrict__ chunks, const float* __restrict__ hyp, float c) {
+  const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
+  const bmnas_adam_tensor_t t = tensors[ti];
+  const float* hr = hyp + 8 * t.hyp_row;
+  SgdHyp h;
+  h.neg_lr = hr[0]; h.mu = hr[1]; h.damp1 = hr[2]; h.mu_n = hr[3]; h.wd = hr[4];
+  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
+  if (e >= t.numel) return;
+  uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad;
+  if constexpr (MOMENTUM) al |= (uintptr_t)t.exp_avg;
+  if ((al & 15) == 0 && e + 4 <= t.numel) {
+    float4 p = ld4(t.param + e);
+    float4 g = ld4(t.grad + e);
+    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MOMENTUM) b = ld4(t.exp_avg + e);
+    if constexpr (CLIP) g = make_float4(mul_alone(g.x, c), mul_alone(g.y, c), mul_alone(g.z, c), mul_alone(g.w, c));
+    sgd1<MOMENTUM, NESTEROV>(p.x, g.x, b.x, h);
+    sgd1<MOMENTUM, NESTEROV>(p.y, g.y, b.y, h);
+    sgd1<MOMENTUM, NESTEROV>(p.z, g.z, b.z, h);
+    sgd1<MOMENTUM, NESTEROV>(p.w, g.w, b.w, h);
+    st4_wtg<5>(t.param + e, p);
+    if constexpr (MOMENTUM) st4_wtg<5>(t.exp_avg + e, b);
+  } else {
+    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
+    for (int64_t i = e; i < end; ++i) {
+      float p = t.param[i], g = t.grad[i], b = 0.f;
+      if constexpr (MOMENTUM) b = t.exp_avg[i];
+      if constexpr (CLIP) g = mul_alone(g, c);
+      sgd1<MOMENTUM, NESTEROV>(p, g, b, h);
+      t.param[i] = p;
+      if constexpr (MOMENTUM) t.exp_avg[i] = b;
+    }
+  }
+}
+
+// One instantiation per launch: all tensors of an optimizer agree on the switches.
+template <bool CLIP, bool MOMENTUM, bool NESTEROV>
+__global__ __launch_bounds__(256) void sgd_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
+                                                   const int32_t* __restrict__ chunks, const float* __restrict__ hyp,
+                                                   const float* __restrict__ partials, int n_parts,
+                                                   const float* __restrict__ clip, float* __restrict__ norm_out) {
+  float c = 1.f;
+  if constexpr (CLIP) {
+    __shared__ float red[4];
+    float norm;
+    c = clip_coef(partials, n_parts, clip, red, norm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  }
+  sgd_chunk<CLIP, MOMENTUM, NESTEROV>(tensors, chunks, hyp, c);
+}
+
 }  // namespace
 
 extern "C" int bmnas_adam_chunk_elems(void) { return kChunk; }
@@ -286,6 +374,33 @@ extern "C" int bmnas_grad_scale_multi(const bmnas_adam_tensor_t* tensors, const 
   if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;
   hipLaunchKernelGGL(grad_scale_multi_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, partials,
                      n_parts, clip, norm_out);
+  BMNAS_CHECK_LAUNCH();
+  return 0;
+}
+
+// `.grad` is NOT written, as in bmnas_adam_multi_clip.
+extern "C" int bmnas_sgd_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                               const float* hyp, int flags, const float* partials, int n_parts, const float* clip,
+                               float* norm_out, void* stream) {
+  if (flags & ~(BMNAS_SGD_MOMENTUM | BMNAS_SGD_NESTEROV)) return BMNAS_E_ARG;
+  if (flags == BMNAS_SGD_NESTEROV) return BMNAS_E_ARG;                 // nesterov is a momentum method
+  const bool clipped = partials != nullptr;
+  if ((clip != nullptr) != clipped || (norm_out != nullptr) != clipped) return BMNAS_E_ARG;
+  if (!tensors || !chunks || !hyp || n_chunks < 0) return BMNAS_E_ARG;
+  if (clipped && (n_chunks == 0 || n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts))) return BMNAS_E_ARG;
+  if (n_chunks == 0) return 0;
+#define BMNAS_SGD(C, M, N)                                                                                        \
+  hipLaunchKernelGGL((sgd_multi_k<C, M, N>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, \
+                     hyp, partials, n_parts, clip, norm_out)
+  switch ((clipped ? 4 : 0) | flags) {
+    case 0: BMNAS_SGD(false, false, false); break;
+    case 1: BMNAS_SGD(false, true, false); break;
+    case 3: BMNAS_SGD(false, true, true); break;
+    case 4: BMNAS_SGD(true, false, false); break;
+    case 5: BMNAS_SGD(true, true, false); break;
+    default: BMNAS_SGD(true, true, true); break;
+  }
+#undef BMNAS_SGD
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

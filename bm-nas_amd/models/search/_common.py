@@ -3,7 +3,7 @@
 import torch
 import torch.nn as nn
 import torch.optim as op
-from bmnas.optim import Adam          # torch.optim.Adam semantics, one HIP launch per step
+from bmnas.optim import SGD, Adam     # torch.optim.Adam / SGD semantics, one HIP launch per step
 
 import models.auxiliary.scheduler as sc
 from bmnas import dist as bdist
@@ -127,6 +127,21 @@ class HyperNetBase(nn.Module):
         return self.fusion_net.arch_parameters()
 
 
+def _make_optimizer(args, prefix, params, lr, weight_decay, max_grad_norm, betas=(0.9, 0.999)):
+    """The weight (prefix '') or alpha (prefix 'arch_') optimizer of search_setup: bmnas.optim.Adam with the arguments it
+    always had unless args.<prefix>optimizer says 'sgd'."""
+    kind = getattr(args, prefix + 'optimizer', 'adam')
+    if kind == 'adam':
+        return Adam(params, lr=lr, betas=betas, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                    amsgrad=bool(getattr(args, prefix + 'amsgrad', False)),
+                    decoupled_weight_decay=bool(getattr(args, prefix + 'decoupled_weight_decay', False)))
+    if kind == 'sgd':
+        return SGD(params, lr=lr, momentum=getattr(args, prefix + 'momentum', 0.9),
+                   dampening=getattr(args, prefix + 'dampening', 0), weight_decay=weight_decay,
+                   nesterov=bool(getattr(args, prefix + 'nesterov', False)), max_grad_norm=max_grad_norm)
+    raise ValueError(f"args.{prefix}optimizer must be 'adam' or 'sgd', got {kind!r}")
+
+
 def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_decay):
     """Optimizers, scheduler, device placement, data parallelism and the Architect — the body of
     the reference's train_darts_model between model construction and the trainer call
@@ -139,16 +154,18 @@ def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_d
     # reference's argument sets have none of them): torch.optim.Adam's two switches for the weight / alpha optimizer —
     # the running maximum of the second moment, and AdamW's decay on the parameter instead of the gradient — in the same
     # one launch (bmnas_adam_multi_ex), captured steps included; absent, the optimizers are the ones they always were
-    optimizer = Adam(model.central_params(), lr=args.eta_max, weight_decay=weight_decay,
-                     max_grad_norm=getattr(args, 'grad_clip', None), amsgrad=bool(getattr(args, 'amsgrad', False)),
-                     decoupled_weight_decay=bool(getattr(args, 'decoupled_weight_decay', False)))
+    # args.optimizer / args.arch_optimizer in {'adam', 'sgd'} (optional, default 'adam'; the reference's argument sets have
+    # neither): 'sgd' is DARTS' weight optimizer (models/search/darts/train_search.py:84-88), bmnas.optim.SGD with
+    # args.momentum (default 0.9), args.dampening, args.nesterov — arch_momentum / arch_dampening / arch_nesterov for the
+    # alpha optimizer — on one bmnas_sgd_multi launch; grad_clip / arch_grad_clip, the scheduler and bdist.attach apply
+    # to it unchanged
+    optimizer = _make_optimizer(args, '', model.central_params(), lr=args.eta_max, weight_decay=weight_decay,
+                                max_grad_norm=getattr(args, 'grad_clip', None))
     scheduler = sc.LRCosineAnnealingScheduler(args.eta_max, args.eta_min, args.Ti, args.Tm,
                                               num_batches_per_epoch)
-    arch_optimizer = Adam(model.arch_parameters(), lr=args.arch_learning_rate, betas=(0.5, 0.999),
-                             weight_decay=args.arch_weight_decay,
-                             max_grad_norm=getattr(args, 'arch_grad_clip', None),
-                             amsgrad=bool(getattr(args, 'arch_amsgrad', False)),
-                             decoupled_weight_decay=bool(getattr(args, 'arch_decoupled_weight_decay', False)))
+    arch_optimizer = _make_optimizer(args, 'arch_', model.arch_parameters(), lr=args.arch_learning_rate,
+                                     weight_decay=args.arch_weight_decay,
+                                     max_grad_norm=getattr(args, 'arch_grad_clip', None), betas=(0.5, 0.999))
     if data_parallel_world(args) > 1:
         # one process per GPU: the unchanged mains pass cuda:0 to every rank
         # (main_darts_searchable_mmimdb.py:86), so the rank's own device comes from LOCAL_RANK,

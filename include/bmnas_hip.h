@@ -929,6 +929,35 @@ int bmnas_adam_multi_ex(const bmnas_adam_tensor_t* tensors, const int32_t* chunk
                         const float* hyp, float* const* max_exp_avg_sq, int flags,
                         const float* partials, int n_parts, const float* clip, float* norm_out, void* stream);
 
+/* ---- multi-tensor SGD with momentum (torch.optim.SGD) in one launch ----------------------------------------
+ * The weight optimizer of the DARTS drivers (models/search/darts/train_search.py:84-88, train.py:78; clipped at
+ * train_search.py:158).  bmnas_sgd_multi walks the descriptor table, the (tensor, chunk) list and the 8-float rows of
+ * bmnas_adam_multi; `exp_avg` of a descriptor is torch's `momentum_buffer`, `exp_avg_sq` is not read and may be NULL,
+ * so bmnas_grad_sqnorm_multi serves it unchanged.  Per element, torch 2.10's _single_tensor_sgd with maximize off,
+ * every operation rounded on its own (no fused multiply-add):
+ *     clipping:              g = c * grad                      (c == 1 leaves the unclipped bits)
+ *     wd != 0:               g = g + wd * p
+ *     BMNAS_SGD_MOMENTUM:    buf = buf * mu + damp1 * g
+ *                            g = BMNAS_SGD_NESTEROV ? g + mu_n * buf : buf
+ *     p = p + neg_lr * g
+ *   hyp row: { -lr, mu, damp1 = 1 - dampening, mu_n, weight_decay, 0, 0, 0 }.  mu and mu_n are both the group's
+ *     momentum — except in the row of a tensor's FIRST step, where torch sets buf = clone(g): the host stages mu = 0
+ *     and damp1 = 1 over a zero-filled buffer (mu_n keeps the momentum), so the kernel has no branch for it and a
+ *     captured graph needs no second instantiation.
+ *   flags: BMNAS_SGD_MOMENTUM | BMNAS_SGD_NESTEROV, one kernel instantiation per launch.  Without BMNAS_SGD_MOMENTUM
+ *     `exp_avg` is never dereferenced (NULL is fine).
+ *   partials / n_parts / clip / norm_out: as for bmnas_adam_multi_clip; the launch clips iff partials != NULL, and
+ *     the three pointers are all set or all NULL.  `.grad` is NOT written.
+ *   Reads param, grad (+ buf); writes param (+ buf, + norm_out when clipping): 12 B per parameter, 20 B with momentum.
+ *   BMNAS_E_ARG (nothing launched): NULL tensors / chunks / hyp; n_chunks < 0; unknown flag bits; BMNAS_SGD_NESTEROV
+ *   without BMNAS_SGD_MOMENTUM; partials / clip / norm_out not all set or all NULL; clipping with n_chunks == 0 or an
+ *   n_parts that is not the G of the norm launch. */
+#define BMNAS_SGD_MOMENTUM 1
+#define BMNAS_SGD_NESTEROV 2
+int bmnas_sgd_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                    const float* hyp, int flags, const float* partials, int n_parts, const float* clip,
+                    float* norm_out, void* stream);
+
 /* ---- a batch into a captured step's static tensors (bmnas.graph._copy_batch_in) -------------------
  * The reference hands every batch over with `.to(device)` per tensor (train_searchable/mmimdb.py:60-63,
  * ntu.py:60-66, ego.py:60-66); a replayed step reads its inputs from fixed addresses, so a batch that is
