@@ -256,6 +256,10 @@ SIGNATURES = {
     'bmnas_adam_multi_ex': ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_grad_scale_multi': ([_P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_sgd_multi': ([_P, _P, _I, _P, _I, _P, _I, _P, _P, _P], _I),
+    'bmnas_unroll_virtual_step': ([_P, _P, _I, _P, _I, _P], _I),
+    'bmnas_unroll_perturb': ([_P, _P, _I, _P, _I, _P, C.c_float, _P, _P], _I),
+    'bmnas_unroll_restore': ([_P, _P, _I, _P], _I),
+    'bmnas_unroll_combine': ([_P, _P, _I, _P, _P, _P], _I),
     'bmnas_copy_batch_max': ([], _I),
     'bmnas_copy_blob_max': ([], _I),
     'bmnas_copy_batch': ([_PP, _PP, C.POINTER(C.c_longlong), _I, _P, _P, _I, _P, C.c_ulonglong, _P], _I),
@@ -1165,6 +1169,36 @@ def sgd_multi(table, chunks, n_chunks, hyp, flags, partials=None, n_parts=0, cli
     p = lambda t: None if t is None else t.data_ptr()
     _check(load().bmnas_sgd_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), int(flags),
                                   p(partials), n_parts, p(clip), p(norm_out), _stream()), 'sgd_multi')
+
+
+UNROLL_MOMENTUM = 1                          # BMNAS_UNROLL_* (include/bmnas_hip.h)
+
+
+def unroll_virtual_step(table, chunks, n_chunks, hyp, flags):
+    """DARTS' virtual weight step over `table` (bmnas_adam_tensor_t[]: exp_avg the momentum buffer — read only, NULL
+    without UNROLL_MOMENTUM —, exp_avg_sq the backup): bak = p; p = p + neg_eta * ((buf * mu +) g (+ wd * p)).
+    hyp: float32 device (rows, 8) holding { -eta, mu, weight_decay, 0, ... }."""
+    _check(load().bmnas_unroll_virtual_step(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), int(flags),
+                                            _stream()), 'unroll_virtual_step')
+
+
+def unroll_perturb(table, chunks, n_chunks, partials, n_parts, r, sign, R_out):
+    """p = bak + (sign * R) * grad with R = r[0] / sqrt(sum(partials[:n_parts])) (grad_sqnorm_multi's partials over the
+    same table); r, R_out: fp32 device scalars (R_out receives R); sign: +1 or -1."""
+    _check(load().bmnas_unroll_perturb(table.data_ptr(), chunks.data_ptr(), n_chunks, _ptr(partials), n_parts,
+                                       r.data_ptr(), float(sign), R_out.data_ptr(), _stream()), 'unroll_perturb')
+
+
+def unroll_restore(table, chunks, n_chunks):
+    """p = bak for every tensor of `table`."""
+    _check(load().bmnas_unroll_restore(table.data_ptr(), chunks.data_ptr(), n_chunks, _stream()), 'unroll_restore')
+
+
+def unroll_combine(table, chunks, n_chunks, hyp, R):
+    """Over a table of architecture tensors (param = dalpha, grad = g+, exp_avg = g-): dalpha -= eta * (g+ - g-) / (2 R);
+    hyp[0] = eta and R are fp32 device scalars."""
+    _check(load().bmnas_unroll_combine(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), R.data_ptr(),
+                                       _stream()), 'unroll_combine')
 
 
 def copy_blob_max():

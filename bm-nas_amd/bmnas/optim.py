@@ -30,6 +30,11 @@ by-value scalar rows and norm launch are Adam's, the update is one `bmnas_sgd_mu
 what it means for Adam.  `_OneLaunch` holds what the two classes share; each class says which state tensors a descriptor
 points at (`_state_ptrs`), what a scalar row holds (`_build`'s row key, `prepare_replay`) and which launch to issue
 (`_launch`).
+
+`UnrolledStep` (beside `clip_grad_norm_`, at the end) is no optimizer: it holds the weight-side arithmetic of DARTS'
+unrolled architecture step — virtual weight step, +-R perturbation, restore, and the combine over alpha — on the kernels
+of csrc/unroll.hip, over the same descriptor table, chunk list and norm launch, reading a weight optimizer's groups and
+momentum buffers without writing them.
 """
 import math
 
@@ -749,3 +754,277 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     lib.grad_sqnorm_multi(ent['tab'], ent['chunks'], ent['n_chunks'], ent['partials'])
     lib.grad_scale_multi(ent['tab'], ent['chunks'], ent['n_chunks'], ent['partials'], n_parts, ent['clip'], norm)
     return norm[0]
+
+
+class UnrolledStep:
+    """The weight-side arithmetic of DARTS' unrolled (second-order) architecture step (Liu et al. 2019, eq. 7-8; the
+    reference still passes `unrolled=args.unrolled` at models/search/darts/train_search.py:151) on the kernels of
+    csrc/unroll.hip.  `models.search.darts.architect.Architect` drives it:
+
+        virtual_step(g)       bak = w;  w = w - eta (moment + g + wd w)          g = grad_w L_train(w, alpha)
+        perturb(v, +1 / -1)   w = bak + (+-R) v,  R = r / ||v||                   v = grad_w' L_val(w', alpha)
+        restore()             w = bak
+        combine(da, gp, gn)   da -= eta (gp - gn) / (2 R)                         gp / gn = grad_alpha L_train(w+ / w-)
+
+    It owns the plan: the descriptor tables of the weights and of alpha, the chunk lists, the norm partials, ONE
+    persistent backup tensor per weight tensor (+4 B per parameter, where DARTS copies the whole model) and one pinned
+    staging buffer with its device copy.  Pointers and scalars go up in one pinned async copy per call — skipped when the
+    bytes are those the device already holds —, guarded by an event; R, the norm and eta reach the kernels through device
+    memory: no call synchronises with the host.  Eager only.
+
+    The weight tensors are the network optimizer's own (`for g in param_groups for p in g['params']`); `grads`, `v` are
+    lists in that order.  A tensor whose gradient is None in the virtual pass is left out of every launch of that step.
+    A scalar row is per (group, has momentum_buffer): wd is the group's `weight_decay`, mu the group's `momentum` when
+    `state[p]` holds a `momentum_buffer` and 0 otherwise — DARTS' try / except.  A bmnas.optim.Adam weight optimizer (the
+    BM-NAS default) therefore gets the plain step w' = w - eta (g + wd w), as DARTS' code gives any optimizer without
+    momentum buffers.  One eta, as in DARTS: every group must hold the same `lr` when the step runs.  The weight
+    optimizer's max_grad_norm, dampening, nesterov, amsgrad and decoupled weight decay play no part in the virtual step,
+    and its state — moments, buffers, step counts — is read, never written."""
+
+    def __init__(self, network_optimizer, arch_parameters, r=1e-2):
+        if network_optimizer is None:
+            raise lib.BmnasError('bmnas.optim.UnrolledStep needs the network (weight) optimizer')
+        self.optimizer = network_optimizer
+        self.arch = list(arch_parameters)
+        self.r = float(r)
+        self._bak, self._zero = {}, {}
+        self._plan = None
+        self._normed = False             # the norm of v has been taken since the last virtual_step()
+        self._stepped = False            # the weights hold w' or w+-, not w: restore() is owed
+        self.uploads = 0                # pinned H2D copies issued so far (a skipped one does not count)
+
+    @property
+    def weights(self):
+        return [p for g in self.optimizer.param_groups for p in g['params']]
+
+    def eta(self):
+        """The one learning rate of the virtual step; BmnasError when the weight groups disagree."""
+        lrs = [float(g['lr']) for g in self.optimizer.param_groups]
+        if any(lr != lrs[0] for lr in lrs):
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep: the weight optimizer\'s groups hold different learning rates '
+                                 f'{lrs}; DARTS\' unrolled step has one eta (per-group eta is not supported)')
+        return lrs[0]
+
+    def row_of(self, p, group):
+        """-> (has momentum_buffer, mu, wd) of one weight tensor."""
+        st = self.optimizer.state.get(p)
+        has = st is not None and torch.is_tensor(st.get('momentum_buffer'))
+        return has, (float(group.get('momentum', 0.0)) if has else 0.0), float(group['weight_decay'])
+
+    # ------------------------------------------------------------------ plan
+    @staticmethod
+    def _eager(what):
+        if torch.cuda.is_current_stream_capturing():
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep.{what} is eager only (it stages descriptor tables per call); '
+                                 'the unrolled architecture step cannot be captured in a graph')
+
+    def _aligned(self, vals, what):
+        ws = self.weights
+        vals = list(vals)
+        if len(vals) != len(ws):
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep: {len(vals)} {what} for {len(ws)} weight tensors')
+        return vals
+
+    @staticmethod
+    def _check_like(t, p, what):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != p.device or t.numel() != p.numel():
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep: {what} must be contiguous fp32 on the parameter device, of '
+                                 "the parameter's size")
+
+    def _zeros(self, p):
+        if p not in self._zero:
+            self._zero[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return self._zero[p]
+
+    def _build(self, active, key):
+        """active: [(p, group index, has momentum_buffer)] of this step.  One pinned buffer and its device copy:
+        scalar rows | r, eta | weight table | alpha table."""
+        dev = active[0][0].device
+        E = lib.adam_chunk_elems()
+        rows, row_idx, row_of, chunks = [], {}, [], []
+        for i, (p, gi, has) in enumerate(active):
+            if not p.is_cuda:
+                raise lib.BmnasError('bmnas.optim.UnrolledStep needs parameters on the GPU (HIP kernel, no CPU path)')
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise lib.BmnasError(f'bmnas.optim.UnrolledStep: parameter must be contiguous fp32 on {dev}')
+            if p not in self._bak:
+                self._bak[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
+            if (gi, has) not in row_idx:
+                row_idx[(gi, has)] = len(rows)
+                rows.append((gi, has))
+            row_of.append(row_idx[(gi, has)])
+            chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
+        for a in self.arch:
+            if a.device != dev or a.dtype != torch.float32:
+                raise lib.BmnasError(f'bmnas.optim.UnrolledStep: architecture tensors must be fp32 on {dev}')
+        row_bytes = len(rows) * 32
+        hyp_bytes = (row_bytes + 16 + 63) // 64 * 64
+        wtab_bytes, atab_bytes = len(active) * _DESC.itemsize, len(self.arch) * _DESC.itemsize
+        nbytes = hyp_bytes + wtab_bytes + atab_bytes
+        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+        host = pin.numpy()
+        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        wtab = host[hyp_bytes:hyp_bytes + wtab_bytes].view(_DESC)
+        wtab['param'] = [p.data_ptr() for p, _, _ in active]
+        wtab['exp_avg_sq'] = [self._bak[p].data_ptr() for p, _, _ in active]
+        wtab['numel'] = [p.numel() for p, _, _ in active]
+        wtab['hyp_row'] = row_of
+        parts = lib.grad_norm_parts()
+        self._plan = dict(
+            key=key, active=active, rows=rows, pin=pin, host=host, dev=devbuf, sent=None, event=None,
+            hyp=host[:row_bytes].view(np.float32).reshape(len(rows), 8),
+            scal=host[row_bytes:row_bytes + 16].view(np.float32),
+            wtab=wtab, atab=host[hyp_bytes + wtab_bytes:].view(_DESC),
+            dev_hyp=devbuf[:hyp_bytes], dev_r=devbuf[row_bytes:row_bytes + 4], dev_eta=devbuf[row_bytes + 4:row_bytes + 8],
+            dev_wtab=devbuf[hyp_bytes:hyp_bytes + wtab_bytes], dev_atab=devbuf[hyp_bytes + wtab_bytes:],
+            chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev), n_chunks=len(chunks),
+            n_parts=min(len(chunks), parts), partials=torch.empty(parts, dtype=torch.float32, device=dev),
+            R=torch.zeros(1, dtype=torch.float32, device=dev),
+            flags=lib.UNROLL_MOMENTUM if any(has for _, _, has in active) else 0, achunks={})
+
+    def _wait(self):
+        """Block until the last upload has read the pinned buffer (the host may run ahead of the GPU)."""
+        ev = self._plan['event']
+        if ev is not None:
+            ev.synchronize()
+
+    def _upload(self):
+        """One pinned async copy of everything staged — unless the device already holds exactly these bytes."""
+        pl = self._plan
+        if pl['sent'] is not None and np.array_equal(pl['sent'], pl['host']):
+            return
+        pl['dev'].copy_(pl['pin'], non_blocking=True)
+        if pl['event'] is None:
+            pl['event'] = torch.cuda.Event()
+        pl['event'].record()
+        pl['sent'] = pl['host'].copy()
+        self.uploads += 1
+
+    # ------------------------------------------------------------------ the four calls
+    @torch.no_grad()
+    def virtual_step(self, grads):
+        """bak = w; w = w - eta (moment + g + wd w) for every weight tensor whose entry of `grads` is not None."""
+        eta = self.eta()                                   # (first: refused before anything moves)
+        grads = self._aligned(grads, 'gradients')
+        active, gs, i = [], [], 0
+        for gi, g in enumerate(self.optimizer.param_groups):
+            for p in g['params']:
+                gr = grads[i]
+                i += 1
+                if gr is None:
+                    continue
+                self._check_like(gr, p, 'gradients')
+                active.append((p, gi, self.row_of(p, g)[0]))
+                gs.append(gr)
+        if not active:
+            raise lib.BmnasError('bmnas.optim.UnrolledStep: no weight tensor has a gradient')
+        if not all(p.is_cuda for p, _, _ in active):
+            raise lib.BmnasError('bmnas.optim.UnrolledStep needs parameters on the GPU (HIP kernel, no CPU path)')
+        self._eager('virtual_step')
+        key = tuple((id(p), gi, has) for p, gi, has in active)
+        if self._plan is None or self._plan['key'] != key:
+            self._build(active, key)
+        pl = self._plan
+        self._wait()
+        bufs = []
+        for p, gi, has in active:
+            buf = self.optimizer.state[p]['momentum_buffer'] if has else None
+            if buf is not None:
+                self._check_like(buf, p, 'momentum_buffer')
+            bufs.append(0 if buf is None else buf.data_ptr())
+        for r, (gi, has) in enumerate(pl['rows']):
+            g = self.optimizer.param_groups[gi]
+            pl['hyp'][r] = (-eta, float(g.get('momentum', 0.0)) if has else 0.0, float(g['weight_decay']), 0, 0, 0, 0, 0)
+        pl['scal'][:] = (self.r, eta, 0.0, 0.0)
+        pl['wtab']['param'] = [p.data_ptr() for p, _, _ in active]
+        pl['wtab']['grad'] = [gr.data_ptr() for gr in gs]
+        pl['wtab']['exp_avg'] = bufs
+        self._upload()
+        lib.unroll_virtual_step(pl['dev_wtab'], pl['chunks'], pl['n_chunks'], pl['dev_hyp'], pl['flags'])
+        self._normed = False
+        self._stepped = True
+
+    def _need_step(self, what):
+        if self._plan is None or not self._stepped:
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep.{what}: call virtual_step() first')
+
+    @torch.no_grad()
+    def perturb(self, v, sign):
+        """w = bak + (sign R) v with R = r / ||v||; the norm is taken once, on the first call after virtual_step()."""
+        self._need_step('perturb')
+        self._eager('perturb')
+        if sign not in (1, -1):
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep.perturb: sign must be +1 or -1, got {sign!r}')
+        pl = self._plan
+        by_param = dict(zip(self.weights, self._aligned(v, 'vectors')))
+        vs = []
+        for p, _, _ in pl['active']:
+            t = by_param[p]
+            if t is None:
+                t = self._zeros(p)               # no validation gradient: the tensor is not perturbed
+            self._check_like(t, p, 'vectors')
+            vs.append(t)
+        self._wait()
+        pl['wtab']['grad'] = [t.data_ptr() for t in vs]
+        self._upload()
+        if not self._normed:
+            lib.grad_sqnorm_multi(pl['dev_wtab'], pl['chunks'], pl['n_chunks'], pl['partials'])
+            self._normed = True
+        lib.unroll_perturb(pl['dev_wtab'], pl['chunks'], pl['n_chunks'], pl['partials'], pl['n_parts'], pl['dev_r'],
+                           sign, pl['R'])
+
+    @torch.no_grad()
+    def restore(self):
+        """w = bak."""
+        self._need_step('restore')
+        self._eager('restore')
+        pl = self._plan
+        lib.unroll_restore(pl['dev_wtab'], pl['chunks'], pl['n_chunks'])
+        self._stepped = False
+
+    @property
+    def R(self):
+        """1-element fp32 device tensor: R of the most recent perturb()."""
+        return None if self._plan is None else self._plan['R']
+
+    @torch.no_grad()
+    def combine(self, dalpha, gp, gn):
+        """dalpha[i] -= eta (gp[i] - gn[i]) / (2 R), in place; -> the list.  Lists follow `arch_parameters`; an entry
+        that is None in all three stays None, one that is None in some counts as zeros."""
+        pl = self._plan
+        if pl is None or not self._normed:
+            raise lib.BmnasError('bmnas.optim.UnrolledStep.combine: no perturb() has set R')
+        self._eager('combine')
+        lists = [list(dalpha), list(gp), list(gn)]
+        if any(len(x) != len(self.arch) for x in lists):
+            raise lib.BmnasError(f'bmnas.optim.UnrolledStep.combine: lists of {len(self.arch)} entries expected')
+        out, idx, cols = list(lists[0]), [], []
+        for i, a in enumerate(self.arch):
+            trio = [x[i] for x in lists]
+            if all(t is None for t in trio):
+                continue
+            trio = [torch.zeros_like(a, memory_format=torch.contiguous_format) if t is None else t for t in trio]
+            for t in trio:
+                self._check_like(t, a, 'architecture gradients')
+            out[i] = trio[0]
+            idx.append(i)
+            cols.append(trio)
+        if not idx:
+            return out
+        ck = tuple(idx)
+        if ck not in pl['achunks']:
+            E = lib.adam_chunk_elems()
+            ch = [(j, c) for j, i in enumerate(idx) for c in range((self.arch[i].numel() + E - 1) // E)]
+            pl['achunks'][ck] = (torch.tensor(ch, dtype=torch.int32).reshape(-1, 2).to(pl['dev'].device), len(ch))
+        chunks, n = pl['achunks'][ck]
+        self._wait()
+        tab = pl['atab']
+        tab[:] = np.zeros((), dtype=_DESC)
+        m = len(idx)
+        tab['param'][:m] = [c[0].data_ptr() for c in cols]
+        tab['grad'][:m] = [c[1].data_ptr() for c in cols]
+        tab['exp_avg'][:m] = [c[2].data_ptr() for c in cols]
+        tab['numel'][:m] = [c[0].numel() for c in cols]
+        self._upload()
+        lib.unroll_combine(pl['dev_atab'], chunks, n, pl['dev_eta'], pl['R'])
+        return out

@@ -159,6 +159,11 @@ def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_d
     # args.momentum (default 0.9), args.dampening, args.nesterov — arch_momentum / arch_dampening / arch_nesterov for the
     # alpha optimizer — on one bmnas_sgd_multi launch; grad_clip / arch_grad_clip, the scheduler and bdist.attach apply
     # to it unchanged
+    # args.unrolled (optional, DARTS' `--unrolled`, which the reference still parses at main_darts_found_ntu.py:48 and
+    # models/search/darts/train_search.py:42) / args.unrolled_r (default 1e-2): the Architect runs DARTS' unrolled
+    # second-order step (architect.Architect._step_unrolled) with the weight optimizer built here — its learning rate is
+    # the step's eta, its weight_decay and momentum buffers enter the virtual step —, eagerly, single-process only; the
+    # trainer loop then hands it one training batch per dev batch.  Absent: the first-order step, as it always was
     optimizer = _make_optimizer(args, '', model.central_params(), lr=args.eta_max, weight_decay=weight_decay,
                                 max_grad_norm=getattr(args, 'grad_clip', None))
     scheduler = sc.LRCosineAnnealingScheduler(args.eta_max, args.eta_min, args.Ti, args.Tm,
@@ -179,5 +184,5 @@ def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_d
         bdist.broadcast_state(model, model.arch_parameters())
         bdist.attach(optimizer)
         bdist.attach(arch_optimizer)
-    architect = Architect(model, args, criterion, arch_optimizer)
+    architect = Architect(model, args, criterion, arch_optimizer, network_optimizer=optimizer)
     return optimizer, scheduler, architect, Plotter(args)

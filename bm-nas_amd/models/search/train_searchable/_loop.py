@@ -233,6 +233,23 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     stats = run.stats = dict(graph_replays=0, eager_steps=0, forward_replays=0, k_step_replays=0)
     best = dict(best_dev=None, best_dev_genotype=None, best_dev_epoch=0, best_test=None,
                 best_test_genotype=None, best_test_epoch=0, last_genotype=None, nan_abort=False)
+    # the unrolled architecture step (architect.unrolled) draws one training batch per dev batch from an iterator of its
+    # own over the training loader, restarted when exhausted
+    unrolled = status == 'search' and architect is not None and bool(getattr(architect, 'unrolled', False))
+    train_iter = None
+
+    def next_train():
+        nonlocal train_iter
+        for _ in range(2):
+            if train_iter is None:
+                train_iter = iter(dataloaders['train'])
+            try:
+                return unpack(next(train_iter), device)
+            except StopIteration:
+                train_iter = None
+                stats['unrolled_train_restarts'] = stats.get('unrolled_train_restarts', 0) + 1
+        raise RuntimeError('the training loader yields no batch')
+
     for epoch in range(num_epochs):
         logger.info('Epoch: {}'.format(epoch))
         logger.info('EXP: {}'.format(args.save))
@@ -279,7 +296,15 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 if status == 'search' and phase in ('dev', 'test') and architect is not None:
                     # (captured: the metric forward below rides at the end of the architecture step's replay — one
                     # batch copy and one hipGraph launch for both; None: it did not, evaluate it here)
-                    got = architect.step(inputs, labels, logger, metric=not learn and use_graph and f_graphs.on)
+                    if unrolled:
+                        # DARTS' unrolled step (train_search.py:151: `architect.step(input, target, input_search,
+                        # target_search, ...)`): one training batch beside the dev batch; eager, returns None — the
+                        # metric forward below runs through f_graphs
+                        x_train, y_train = next_train()
+                        got = architect.step(inputs, labels, logger, input_train=x_train, target_train=y_train)
+                        stats['unrolled_steps'] = stats.get('unrolled_steps', 0) + 1
+                    else:
+                        got = architect.step(inputs, labels, logger, metric=not learn and use_graph and f_graphs.on)
                 if learn and use_graph:
                     if w_graph is None and w_attempts < 3:
                         w_attempts += 1
@@ -377,7 +402,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
             # which batches wait for a k-step replay: the weight steps of a learning phase; the (architecture step +
             # metric forward) pairs of a search's dev phase
             arch_phase = (status == 'search' and phase in ('dev', 'test') and architect is not None and not learn
-                          and f_graphs.on and hasattr(architect, 'step_k'))
+                          and f_graphs.on and hasattr(architect, 'step_k') and not unrolled)
             group = k_batches if learn else (k_arch_batches if arch_phase else None)
             held, held_w = [], []                       # batches waiting for their k-step replay (+ their shard weights)
 

@@ -958,6 +958,43 @@ int bmnas_sgd_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, i
                     const float* hyp, int flags, const float* partials, int n_parts, const float* clip,
                     float* norm_out, void* stream);
 
+/* ---- unrolled (second-order) architecture step of DARTS (csrc/unroll.hip) -----------------------------------
+ * The reference still passes `unrolled=args.unrolled` to its Architect (models/search/darts/train_search.py:151,
+ * the flag at :42 and main_darts_found_ntu.py:48) and keeps `network_weight_decay` for it
+ * (models/search/darts/architect.py:11), but the unrolled body is gone; this is DARTS' (Liu et al. 2019, eq. 7-8):
+ *     w' = w - eta (moment + grad + wd w);  (dalpha, v) = grad_(alpha, w') L_val(w', alpha);  R = r / ||v||
+ *     dalpha -= eta (grad_alpha L_train(w + R v) - grad_alpha L_train(w - R v)) / (2 R)
+ * Four launches over the descriptor table, the (tensor, chunk) list and the 8-float rows of bmnas_adam_multi, every
+ * operation rounded on its own (no fused multiply-add).  A descriptor's columns mean here: `param` = w, `grad` = the
+ * vector of the pass (the train gradient, then v), `exp_avg` = the weight optimizer's momentum_buffer (may be NULL),
+ * `exp_avg_sq` = a backup tensor of w's size — so bmnas_grad_sqnorm_multi serves ||v|| unchanged.
+ *   bmnas_unroll_virtual_step: hyp row { -eta, mu, weight_decay, 0... }.  Per element
+ *       bak = p;  d = g;  wd != 0: d = g + wd * p;  BMNAS_UNROLL_MOMENTUM: d = buf * mu + d;  p = p + neg_eta * d
+ *     (`theta.sub(eta, moment + dtheta)`, dtheta = grad + wd * theta, moment = momentum_buffer * momentum).  buf is
+ *     read, never written; without the flag `exp_avg` is never dereferenced, and with it a descriptor whose `exp_avg`
+ *     is NULL (a tensor that has no momentum_buffer yet beside tensors that have one) takes no momentum term.
+ *     16 B per parameter, 20 B with momentum.
+ *   bmnas_unroll_perturb: norm = sqrt(sum of partials[0 .. n_parts)) in the fixed order of bmnas_adam_multi_clip's
+ *     coefficient; R = r[0] / norm (NO epsilon: a zero norm gives inf, then NaN, as DARTS' code does);
+ *     p = bak + (sign * R) * v.  sign: +1 or -1, by value; r: DEVICE float; R_out: DEVICE float, receives R.  Every w
+ *     is formed from the backup, never by an add / sub(2R) / add chain.  n_parts must be the G of the norm launch.
+ *   bmnas_unroll_restore: p = bak.  `grad` is not read.
+ *   bmnas_unroll_combine, over a table of architecture tensors: `param` = dalpha (read and written), `grad` = g+,
+ *     `exp_avg` = g-; hyp[0] = eta and R (the float bmnas_unroll_perturb wrote) are DEVICE floats.  Per element
+ *       d = gp - gn;  ig = d / (2 * R);  out = da - eta * ig            (`(x - y).div_(2R)`, `g.sub_(eta, ig)`)
+ *   BMNAS_E_ARG (nothing launched): a NULL pointer (`exp_avg` / `exp_avg_sq` live in the table and are not seen by the
+ *   host); unknown flag bits; n_chunks < 0; a sign other than +1 / -1; an n_parts that is not the G of the norm launch.
+ *   n_chunks == 0 is a no-op, except for bmnas_unroll_perturb, which needs a norm (BMNAS_E_ARG). */
+#define BMNAS_UNROLL_MOMENTUM 1
+int bmnas_unroll_virtual_step(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                              const float* hyp, int flags, void* stream);
+int bmnas_unroll_perturb(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                         const float* partials, int n_parts, const float* r, float sign, float* R_out,
+                         void* stream);
+int bmnas_unroll_restore(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks, void* stream);
+int bmnas_unroll_combine(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                         const float* hyp, const float* R, void* stream);
+
 /* ---- a batch into a captured step's static tensors (bmnas.graph._copy_batch_in) -------------------
  * The reference hands every batch over with `.to(device)` per tensor (train_searchable/mmimdb.py:60-63,
  * ntu.py:60-66, ego.py:60-66); a replayed step reads its inputs from fixed addresses, so a batch that is
