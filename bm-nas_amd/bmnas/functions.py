@@ -428,6 +428,92 @@ class SdpaLnThruFn(Function):
         return dx, dy, dw, db, None, None
 
 
+# ------------------------------------------------------------------ multi-head attention
+def mha_runs(roles):
+    """The projection GEMMs of a multi-head attention whose q / k / v roles read the unique sources roles[0..2]:
+    one per maximal run of CONSECUTIVE roles with the same source -> [(first role, end role, source index)].
+    (0, 0, 0): one GEMM with M = 3C; (0, 1, 1): M = C and M = 2C; (0, 1, 2) and (0, 1, 0): three."""
+    runs, r0 = [], 0
+    for r in range(1, 4):
+        if r == 3 or roles[r] != roles[r0]:
+            runs.append((r0, r, roles[r0]))
+            r0 = r
+    return runs
+
+
+class MhaFn(Function):
+    """Attention.forward (reference operations.py:67-86): nn.MultiheadAttention over (b, C, L) tensors, tokens = the L
+    positions.  in_proj as bmnas_conv1x1_fwd launches (mha_runs), the per-head core (csrc/mha.hip), out_proj as one
+    more; the backward mirrors it launch for launch.  `roles`: for q, k, v the index of its tensor among the unique
+    `srcs` — a tensor that plays two roles is passed once and receives ONE gradient, summed by the data-gradient
+    launches' accumulate bit instead of by the engine."""
+
+    @staticmethod
+    def forward(ctx, heads, p, training, roles, W, bi, Wo, bo, *srcs):
+        _require_gpu(srcs[0], 'multi-head attention')
+        srcs = [_c(_f32(s)) for s in srcs]
+        b, C, L = srcs[0].shape
+        dev = srcs[0].device
+        W, bi, Wo, bo = _c(W).view(3 * C, C), _c(bi), _c(Wo).view(C, C), _c(bo)
+        runs = mha_runs(roles)
+        proj, views = [], [None] * 3
+        for r0, r1, _ in runs:
+            U = torch.empty((b, (r1 - r0) * C, L), device=dev, dtype=torch.float32)
+            proj.append(U)
+            for r in range(r0, r1):
+                views[r] = U[:, (r - r0) * C:(r - r0 + 1) * C]
+        O = torch.empty((b, C, L), device=dev, dtype=torch.float32)
+        P = torch.empty((b, heads, L, L), device=dev, dtype=torch.float32)
+        out = torch.empty((b, C, L), device=dev, dtype=torch.float32)
+        drop = K.DROP.make(p, P.numel(), training)
+        for (r0, r1, si), U in zip(runs, proj):
+            lib.conv1x1_fwd([srcs[si]], C, W[r0 * C:r1 * C], C, bi[r0 * C:r1 * C], U, None, b, L, (r1 - r0) * C)
+        lib.mha_core_fwd(views[0], views[1], views[2], O, P, b, C, L, heads, drop)
+        lib.conv1x1_fwd([O], C, Wo, C, bo, out, None, b, L, C)
+        ctx.heads, ctx.runs, ctx.drop = heads, runs, drop
+        ctx.srcs, ctx.W, ctx.Wo, ctx.proj, ctx.views, ctx.O, ctx.P = srcs, W, Wo, proj, views, O, P
+        if any(ctx.needs_input_grad):
+            ZERO_POOL.announce(4 * C * C + 4 * C)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        srcs, W, Wo, O, P, runs = ctx.srcs, ctx.W, ctx.Wo, ctx.O, ctx.P, ctx.runs
+        b, C, L = O.shape
+        dev = O.device
+        g = _c(g)
+        want_w = any(ctx.needs_input_grad[4:8])
+        if want_w:
+            # the weight gradients are accumulated with atomics: one zero-filled slab, taken before the first launch
+            zero = ZERO_POOL.take(4 * C * C + 4 * C, dev)
+            dWin, dWo = zero[:3 * C * C].view(3 * C, C), zero[3 * C * C:4 * C * C].view(C, C)
+            dbin, dbo = zero[4 * C * C:4 * C * C + 3 * C], zero[4 * C * C + 3 * C:]
+        else:
+            dWin = dWo = dbin = dbo = None
+        dO = torch.empty_like(O)
+        dproj, dviews = [], [None] * 3
+        for (r0, r1, _), U in zip(runs, ctx.proj):
+            dU = torch.empty_like(U)
+            dproj.append(dU)
+            for r in range(r0, r1):
+                dviews[r] = dU[:, (r - r0) * C:(r - r0 + 1) * C]
+        dsrcs = [torch.empty_like(s) if ctx.needs_input_grad[8 + i] else None for i, s in enumerate(srcs)]
+        lib.conv1x1_bwd_data(g, Wo, C, [dO], C, 0, b, L, C)
+        if want_w:
+            lib.conv1x1_bwd_weight(g, [O], C, dWo, C, dbo, 0, b, L, C)
+        v = ctx.views
+        lib.mha_core_bwd(dO, v[0], v[1], v[2], P, dviews[0], dviews[1], dviews[2], b, C, L, ctx.heads, ctx.drop)
+        written = set()
+        for (r0, r1, si), dU in zip(runs, dproj):
+            M = (r1 - r0) * C
+            if dsrcs[si] is not None:
+                lib.conv1x1_bwd_data(dU, W[r0 * C:r1 * C], C, [dsrcs[si]], C, 1 if si in written else 0, b, L, M)
+                written.add(si)
+            if want_w:
+                lib.conv1x1_bwd_weight(dU, [srcs[si]], C, dWin[r0 * C:r1 * C], C, dbin[r0 * C:r1 * C], 0, b, L, M)
+        return (None, None, None, None, dWin, dbin, dWo, dbo, *dsrcs)
+
+
 # ------------------------------------------------- conv1x1 + BN + {GLU | ReLU} + dropout
 class _ZeroPool:
     """Zero-filled scratch for the gradients that the standalone conv + BatchNorm modules accumulate with

@@ -325,6 +325,10 @@ SIGNATURES = {
     'bmnas_fc_found_bwd_reduce': ([C.POINTER(FcEdge), _I, _PP, _I, _I, _I, _P], _I),
     'bmnas_fc_found_bwd_du': ([C.POINTER(FcEdge), _I, _PP, _I, _I, _I, _I, _P], _I),
     'bmnas_fc_found_bwd_gemm': ([C.POINTER(FcEdge), _I, _PP, C.POINTER(C.c_uint32), _I, _I, _I, _I, _P], _I),
+    'bmnas_mha_ok': ([_I, _I, _I, _I], _I),
+    'bmnas_mha_core_fwd': ([_P, _P, _P, _I64, _I64, _I64, _P, _P, _I, _I, _I, _I, Dropout, _P], _I),
+    'bmnas_mha_core_bwd': ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I, _I,
+                            Dropout, _P], _I),
 }
 
 _lib = None
@@ -1511,3 +1515,32 @@ def fc_found_bwd_gemm(arr, dxs, dx_edges, b, Cc, L):
     _check(load().bmnas_fc_found_bwd_gemm(arr, len(arr), _ptrs(dxs), masks, len(dxs), b, Cc, L, _stream()),
            'fc_found_bwd_gemm')
     FC_EDGE_LAUNCHES['bwd'] += 1
+
+
+# ------------------------------------------------------------------ multi-head attention core (csrc/mha.hip)
+def mha_ok(b, Cc, L, heads):
+    """Whether the attention-core kernels take this shape (bmnas_mha_ok; host only)."""
+    return bool(load().bmnas_mha_ok(int(b), int(Cc), int(L), int(heads)))
+
+
+def _strided(t):
+    """(device address, sample stride in floats) of a projected operand: a (b, C, L) fp32 tensor whose channel and
+    position strides are (L, 1) — a contiguous tensor or a row range of a stacked GEMM output."""
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 3, (t.device, t.dtype, t.dim())
+    assert t.stride(2) == 1 and t.stride(1) == t.shape[2], t.stride()
+    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2])
+
+
+def mha_core_fwd(q, k, v, O, P, b, Cc, L, heads, drop):
+    """O = per-head softmax(q^T k / sqrt(d)) applied to v, P = the probabilities before dropout."""
+    (qp, qs), (kp, ks), (vp, vs) = _strided(q), _strided(k), _strided(v)
+    _check(load().bmnas_mha_core_fwd(qp, kp, vp, qs, ks, vs, _ptr(O), _ptr(P), b, Cc, L, heads, drop, _stream()),
+           'mha_core_fwd')
+
+
+def mha_core_bwd(dO, q, k, v, P, dq, dk, dv, b, Cc, L, heads, drop):
+    """dq / dk / dv (strided like q / k / v, overwritten in full) from dO and the saved P."""
+    (qp, qs), (kp, ks), (vp, vs) = _strided(q), _strided(k), _strided(v)
+    (dqp, dqs), (dkp, dks), (dvp, dvs) = _strided(dq), _strided(dk), _strided(dv)
+    _check(load().bmnas_mha_core_bwd(_ptr(dO), qp, kp, vp, qs, ks, vs, _ptr(P), dqp, dkp, dvp, dqs, dks, dvs, b, Cc,
+                                     L, heads, drop, _stream()), 'mha_core_bwd')

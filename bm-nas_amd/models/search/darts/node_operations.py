@@ -16,10 +16,11 @@ from bmnas.functions import (ConvBnActFn, ConvBnActThruFn, MixSumFn, NodeMixedFn
 
 from .genotypes import *  # noqa: F401,F403
 from .genotypes import STEP_STEP_PRIMITIVES
+from .operations import _MHA_CLASSES, Attention
 
 # every node operation takes two (b, C, L) inputs and returns one (b, C, L) output
 # (CatConvMish is not registered, as in the reference: `STEP_STEP_OPS['CatConvMish'] = lambda C, L, args:
-# CatConvMish(C, args)` adds it)
+# CatConvMish(C, args)` adds it; likewise MultiHeadAttn, the two-input form of operations.Attention)
 STEP_STEP_OPS = {
     'Sum': lambda C, L, args: Sum(),
     'ScaleDotAttn': lambda C, L, args: ScaledDotAttn(C, L),
@@ -122,6 +123,23 @@ class ScaledDotAttn(nn.Module):
         `add` launches)."""
         return SdpaLnThruFn.apply(x, y, self.ln.weight, self.ln.bias, self.dropout.p, self.training)
 
+
+class MultiHeadAttn(Attention):
+    """The reference's Attention (operations.py:67-86, "step node operation") in the two-input form of a step-node
+    primitive: the query comes from x, keys and values from y — ScaledDotAttn's roles, with learned projections and
+    `args.num_heads` heads (the reference mains' commented-out --num_heads; 2 when args has none).  state_dict keys as
+    Attention's (attn.*).  Not registered, like CatConvMish: `STEP_STEP_OPS['MultiHeadAttn'] = lambda C, L, args:
+    MultiHeadAttn(C, L, args)` adds it.  In an edited STEP_STEP_PRIMITIVES list NodeMixedOp keeps its composed sum, with
+    this term on its own kernels (bmnas.functions.MhaFn) inside it."""
+
+    def __init__(self, C, L, args):
+        super().__init__(C, getattr(args, 'num_heads', 2), args.drpt)
+
+    def forward(self, x, y):
+        return Attention.forward(self, x, y, y)
+
+
+_MHA_CLASSES.append(MultiHeadAttn)
 
 _DEFAULT_PRIMS = ['Sum', 'ScaleDotAttn', 'LinearGLU', 'ConcatFC']
 _BUILTIN = {'Sum': Sum, 'ScaleDotAttn': ScaledDotAttn, 'LinearGLU': LinearGLU, 'ConcatFC': ConcatFC,

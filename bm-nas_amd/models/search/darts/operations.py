@@ -8,14 +8,16 @@ kernel (bmnas_mixsum_fwd/bwd).  FC_Relu / FC_Mish are not in the default search 
 sum over the incoming edges of a cell / node step runs them on the grouped kernels of
 csrc/fcedge.hip (bmnas.functions.FcEdgeSumFn) — general_edge_sum below.  The fc_relu / fc_mish edges of a FOUND
 cell (each with an output of its own) run on the same file's grouped kernels through found_fc_route /
-found_fc_apply (bmnas.functions.FoundFcEdgesFn).
+found_fc_apply (bmnas.functions.FoundFcEdgesFn).  Attention (:67-86, the reference's unregistered "step node operation":
+nn.MultiheadAttention over (b, C, L) tensors) runs on projection GEMMs and the per-head core of csrc/mha.hip
+(bmnas.functions.MhaFn; attention_route).
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from bmnas import lib
-from bmnas.functions import FC_KINDS, FcEdgeSumFn, FoundFcEdgesFn, MixSumFn
+from bmnas.functions import FC_KINDS, FcEdgeSumFn, FoundFcEdgesFn, MhaFn, MixSumFn
 
 from .genotypes import *  # noqa: F401,F403
 from .genotypes import PRIMITIVES
@@ -72,6 +74,72 @@ class FC_Mish(_FCBase):
 
     def _act(self, x):
         return self.mish(x)
+
+
+# False: Attention.forward always takes the reference's own composition around nn.MultiheadAttention (A/B timing, tests)
+MHA_NATIVE = True
+# the classes whose forward IS the reference's: Attention here, MultiHeadAttn in node_operations.py.  Anybody else's
+# subclass may have changed what forward means and keeps the composed route.
+_MHA_CLASSES = []
+
+
+def attention_route(module, q, k, v):
+    """Which path Attention.forward(q, k, v) takes: 'native' (bmnas.functions.MhaFn: projection GEMMs + the per-head
+    core of csrc/mha.hip) or 'composed' (the reference's transposes around self.attn(..., need_weights=False)) — for a
+    subclass, an edited self.attn (kdim / vdim, bias=False, add_bias_kv, add_zero_attn, batch_first), inputs that are
+    not three fp32 (b, C, L) tensors of one shape and device, or a shape outside lib.mha_ok.  Host logic only: CPU
+    tensors are routed like any others, and the native forward then refuses them."""
+    if not MHA_NATIVE or type(module) not in _MHA_CLASSES:
+        return 'composed'
+    a = module.attn
+    if type(a) is not nn.MultiheadAttention or type(a.out_proj) is not nn.modules.linear.NonDynamicallyQuantizableLinear:
+        return 'composed'
+    if (not a._qkv_same_embed_dim or a.in_proj_weight is None or a.in_proj_bias is None or a.out_proj.bias is None
+            or a.bias_k is not None or a.bias_v is not None or a.add_zero_attn or a.batch_first):
+        return 'composed'
+    ts = (q, k, v)
+    if not all(torch.is_tensor(t) and t.dim() == 3 and t.dtype == torch.float32 for t in ts):
+        return 'composed'
+    if any(t.shape != q.shape or t.device != q.device for t in ts):
+        return 'composed'
+    params = (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias)
+    if any(w.dtype != torch.float32 or w.device != q.device for w in params):
+        return 'composed'
+    b, C, L = q.shape
+    if C != a.embed_dim or a.head_dim * a.num_heads != a.embed_dim or not 0.0 <= a.dropout < 1.0:
+        return 'composed'
+    if not lib.mha_ok(b, C, L, a.num_heads):
+        return 'composed'
+    return 'native'
+
+
+class Attention(nn.Module):
+    """Multi-head attention over (b, C, L) tensors: the L positions are the tokens, the C channels the features
+    (reference operations.py:67-86, "step node operation").  Parameters, their initialisation and the state_dict keys
+    are nn.MultiheadAttention's (attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, attn.out_proj.bias); the
+    forward runs on the gfx950 kernels (attention_route)."""
+
+    def __init__(self, embed_dim, num_heads, drpt):
+        super().__init__()
+        self.attn = nn.MultiheadAttention(embed_dim, num_heads, drpt)
+
+    def forward(self, q, k, v):
+        if attention_route(self, q, k, v) == 'composed':
+            q, k, v = (t.transpose(0, 1).transpose(0, 2) for t in (q, k, v))
+            out = self.attn(q, k, v, need_weights=False)[0]
+            return out.transpose(0, 2).transpose(0, 1)
+        a = self.attn
+        uniq, roles = [], []
+        for t in (q, k, v):
+            i = next((j for j, u in enumerate(uniq) if u is t), len(uniq))
+            if i == len(uniq):
+                uniq.append(t)
+            roles.append(i)
+        return MhaFn.apply(a.num_heads, a.dropout, a.training, tuple(roles), a.in_proj_weight, a.in_proj_bias,
+                           a.out_proj.weight, a.out_proj.bias, *uniq)
+
+
+_MHA_CLASSES.append(Attention)
 
 
 class FusionMixedOp(nn.Module):

@@ -1145,6 +1145,32 @@ int bmnas_fc_found_bwd_du(const bmnas_fc_edge_t* edges, int E, const float* cons
 int bmnas_fc_found_bwd_gemm(const bmnas_fc_edge_t* edges, int E, float* const* dxs, const uint32_t* dx_edges,
                             int n_dx, int b, int C, int L, void* stream);
 
+/* ---- Multi-head attention core -----------------------------------------------------------------------------------
+ * Attention.forward (reference operations.py:67-86) wraps nn.MultiheadAttention over (b, C, L) tensors, tokens = the
+ * L positions, features = the C channels.  Its three in_proj and its out_proj products are 1x1 convolutions
+ * (bmnas_conv1x1_fwd / _bwd_data / _bwd_weight); these two entry points are what lies between them.  Per sample s and
+ * head a (channels a d .. a d + d - 1, d = C / heads) of the PROJECTED q, k, v:
+ *   S[i][j] = sum_c q[s, a d + c, i] k[s, a d + c, j] / sqrt(d),  P = softmax_j(S),  P' = dropout(P),
+ *   O[s, a d + c, i] = sum_j P'[i][j] v[s, a d + c, j].
+ * q / k / v are given by pointer and SAMPLE STRIDE in floats (*_ss >= C L, a multiple of 4; channel and position
+ * strides are L and 1): rows of one (b, 3C, L) GEMM output, of a (b, 2C, L) and a (b, C, L) one, or three buffers.
+ * O is (b, C, L); P is (b, heads, L, L) and receives the softmax output BEFORE dropout (saved for the backward).  `drop`
+ * is a site over the b heads L L probabilities, flat element e = ((s heads + a) L + i) L + j (bmnas_dropout_mask
+ * exports exactly this site).  All pointers 16-byte aligned (BMNAS_E_ARG otherwise).
+ * bmnas_mha_ok (host only): L in {4, 8, 16}, C % 16 == 0, 16 <= C <= 512, heads divides C, d % 4 == 0, b >= 1 and
+ * b heads <= 2^24; outside it both calls return BMNAS_E_LIMIT and launch nothing.
+ * One wave per tile of 16 / L (sample, head) problems, four tiles per workgroup; no atomics (bit-stable from run to
+ * run), no host synchronisation, one launch on `stream` per call. */
+int bmnas_mha_ok(int b, int C, int L, int heads);
+int bmnas_mha_core_fwd(const float* q, const float* k, const float* v, int64_t q_ss, int64_t k_ss, int64_t v_ss,
+                       float* O, float* P, int b, int C, int L, int heads, bmnas_dropout_t drop, void* stream);
+/* dO: gradient of O, (b, C, L) contiguous; P as saved by the forward; the mask is regenerated from `drop`.
+ *   dV = P'^T dO_h,  dP = mask o (dO_h V^T),  dS = P o (dP - rowsum(dP o P)),  dQ = dS K / sqrt(d),  dK = dS^T Q / sqrt(d).
+ * dq / dk / dv (pointer + sample stride, as q / k / v) are overwritten in full; they must not overlap the inputs. */
+int bmnas_mha_core_bwd(const float* dO, const float* q, const float* k, const float* v, int64_t q_ss, int64_t k_ss,
+                       int64_t v_ss, const float* P, float* dq, float* dk, float* dv, int64_t dq_ss, int64_t dk_ss,
+                       int64_t dv_ss, int b, int C, int L, int heads, bmnas_dropout_t drop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
