@@ -2019,7 +2019,7 @@ extern "C" int bmnas_conv1x1_fwd_sdpa(const float* const* srcs, int n_src, int C
   ConvArgs a{};
   if (int e = conv_fwd_args(a, srcs, n_src, C_src, W, ldw, fold_cols, bias, U, part, stat_shards, b, L, M)) return e;
   SdpaFwdArgs s{};
-  if (int e = geom(b, C, L, &s.G)) return e;
+  if (int e = sdpa_geom(b, C, L, &s.G)) return e;
   if (b == 0) return 0;
   if (null_src(a.act, n_src)) return BMNAS_E_ARG;
   s.x = x; s.y = y; s.ln_w = ln_w; s.ln_b = ln_b; s.out = out; s.xhat = xhat; s.stats = stats;
@@ -2141,7 +2141,7 @@ extern "C" int bmnas_conv1x1_bwd_all_sdpa(const float* dU, const float* W, int l
   ConvArgs a{};
   if (int e = conv_bwd_args(a, dU, W, ldw, fold_cols, dsrcs, n_src, C_src, accumulate_mask, b, L, M)) return e;
   SdpaBwdArgs s{};
-  if (int e = geom(b, C, L, &s.G)) return e;
+  if (int e = sdpa_geom(b, C, L, &s.G)) return e;
   if (b == 0) return 0;
   s.g = g; s.gscale = gscale; s.x = x; s.y = y; s.ln_w = ln_w; s.xhat = xhat; s.stats = stats;
   s.dx = dx; s.dy = dy; s.acc_mask = sdpa_accumulate_mask; s.drop = to_cfg(drop);

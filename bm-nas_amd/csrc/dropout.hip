@@ -2,8 +2,7 @@
 // to element e of that site's (b, C, L) output, written out so that a checker can replay the same step on the
 // CPU under the SAME masks (nn.Dropout's generator cannot be matched bit for bit; the Philox stream can be
 // exported).  Audit / test entry point: nothing on the hypernet path launches it.
-#include "common.hpp"
-#include "../../include/bmnas_hip.h"
+#include "drop_cfg.hpp"
 
 namespace {
 
@@ -25,11 +24,10 @@ __global__ __launch_bounds__(256) void dropout_mask_k(DropCfg d, int64_t n4, int
 
 extern "C" int bmnas_dropout_mask(bmnas_dropout_t drop, int64_t n_elem, float* out, void* stream) {
   if (!out || n_elem <= 0) return BMNAS_E_ARG;
-  DropCfg d;
-  d.thr = drop.thr; d.scale = drop.scale; d.seed = drop.seed; d.offset = drop.offset; d.step = drop.step;
   const int64_t n4 = (n_elem + 3) / 4;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(dropout_mask_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d, n4, n_elem, out);
+  hipLaunchKernelGGL(dropout_mask_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, to_cfg(drop), n4, n_elem,
+                     out);
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

@@ -18,8 +18,7 @@
 //   forward   fc_sep_fwd_k         BatchNorm finalisation in the launch, out_e = drop_e(scale act_e(U_e) + shift)
 //   backward  fc_sep_bwd_reduce_k  dBN.weight / dBN.bias of every edge from its own incoming gradient
 //             fc_sep_bwd_du_k      dU_e = BatchNorm input gradient * act_e'(U_e), dbias_e
-#include "common.hpp"
-#include "../../include/bmnas_hip.h"
+#include "drop_cfg.hpp"
 #include "mish.hpp"
 
 namespace {
@@ -643,9 +642,8 @@ int check_common(const bmnas_fc_edge_t* edges, int n, int F, int P, int b, int C
 }
 
 DropCfg common_drop(const bmnas_fc_edge_t* edges) {
-  const bmnas_dropout_t& d = edges[0].fc[0].drop;
-  DropCfg c;
-  c.thr = d.thr; c.scale = d.scale; c.seed = d.seed; c.offset = 0; c.step = d.step;
+  DropCfg c = to_cfg(edges[0].fc[0].drop);
+  c.offset = 0;
   return c;
 }
 

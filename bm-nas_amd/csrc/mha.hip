@@ -5,20 +5,22 @@
 //
 // Decomposition.  A (sample, head) problem is an L x L score matrix over a contraction of d = C / heads channels,
 // L <= 16: far too small for a workgroup, and with b * heads of them a launch is latency bound (d = 96 at
-// MM-IMDB is 24 MFMA k-steps).  As in sdpa_body.hpp, 16 / L problems are packed on the 16-wide MFMA dimension of one
-// "tile" (a block-diagonal mask keeps them apart), so that at L = 4 every lane still loads a useful operand
-// element; unlike there, ONE WAVE owns a tile end to end (the channel contraction is d, not C: splitting it over four
-// waves would buy 6 k-steps per wave at the price of an LDS reduction and two barriers) and a 256-thread workgroup
-// carries four independent tiles.  Problem p = s * heads + a lives at channel offset a * d of sample s; row r of
-// a tile is (problem tile * spw + (r >> Lb), position r & (L - 1)).
-//   S^T[j][i] = sum_c K[c][j] Q[c][i]     v_mfma_f32_16x16x4_f32, dword operand loads straight from global
-//   P = softmax_j(S / sqrt(d))            a lane holds S[i = lane & 15][j = 4 (lane >> 4) + r]: in-lane + xor 16 / 32
-//   O[c][i] = sum_j P'[i][j] V[c][j]      per 16-channel chunk: V as float4 along l, O leaves as float4 along l
+// MM-IMDB is 24 MFMA k-steps).  16 / L problems are packed on the 16-wide MFMA dimension of one "tile" (a
+// block-diagonal mask keeps them apart), so that at L = 4 every lane still loads a useful operand element: the packed
+// tile of attn_tile.hpp, whose per-lane arithmetic (contraction over channels, masked softmax and its backward, product
+// over positions) this file shares with the ScaleDotAttn bodies of sdpa_body.hpp.  Unlike there, ONE WAVE owns a tile
+// end to end (the channel contraction is d, not C: splitting it over four waves would buy 6 k-steps per wave at the
+// price of an LDS reduction and two barriers) and a 256-thread workgroup carries four independent tiles.  Problem
+// p = s * heads + a lives at channel offset a * d of sample s; row r of a tile is (problem tile * spw + (r >> Lb),
+// position r & (L - 1)).
+//   S^T[j][i] = sum_c K[c][j] Q[c][i]     contract_channels: dword operand loads straight from global
+//   P = softmax_j(S / sqrt(d))            tile_softmax: a lane holds S[i = lane & 15][j = 4 (lane >> 4) + r]
+//   O[c][i] = sum_j P'[i][j] V[c][j]      tile_apply per 16-channel chunk: V as float4 along l, O leaves as float4 along l
 // The backward runs the same two shapes of product: dP like S (over channels), dV / dQ / dK like O (over positions),
 // with P' and dS transposed through a wave-private 16 x 17 LDS image.  No atomics, no cross-wave reduction: every
 // output element has one writer and one summation order, so the results are bit-stable from run to run.
-#include "common.hpp"
-#include "../../include/bmnas_hip.h"
+#include "attn_tile.hpp"
+#include "drop_cfg.hpp"
 
 namespace {
 
@@ -40,43 +42,10 @@ struct MhaResult {
   int64_t ss;
 };
 
-inline DropCfg mha_cfg(const bmnas_dropout_t& d) {
-  DropCfg c;
-  c.thr = d.thr; c.scale = d.scale; c.seed = d.seed; c.offset = d.offset; c.step = d.step;
-  return c;
-}
-
 // float offset of channel 0 / position 0 of problem p inside an operand
 __device__ __forceinline__ int64_t prob_off(const MhaGeom& G, int p, int64_t ss) {
   const int s = p / G.heads, a = p - s * G.heads;
   return (int64_t)s * ss + (int64_t)a * G.d * G.L;
-}
-
-// acc[r] = sum_c A[c][row lo] * B[c][row lo'] as T^T[j = 4h + r][i = lo]: A supplies the rows j, B the columns i.
-// ab / bb point at (problem of row lo, position of row lo); one k-step is 4 channels.
-__device__ __forceinline__ void contract_channels(const float* __restrict__ ab, const float* __restrict__ bb, int d,
-                                                  int L, int h, float out[4]) {
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const int steps = d >> 2;
-  const int64_t st = (int64_t)4 * L;
-  int t = 0;
-  for (; t + 3 < steps; t += 4) {                 // 8 loads in flight, then 4 MFMAs
-    const int64_t o0 = (int64_t)(4 * t + h) * L;
-    const float a0 = ab[o0], b0 = bb[o0];
-    const float a1 = ab[o0 + st], b1 = bb[o0 + st];
-    const float a2 = ab[o0 + 2 * st], b2 = bb[o0 + 2 * st];
-    const float a3 = ab[o0 + 3 * st], b3 = bb[o0 + 3 * st];
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b3, acc1, 0, 0, 0);
-  }
-  for (; t < steps; ++t) {
-    const int64_t o0 = (int64_t)(4 * t + h) * L;
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ab[o0], bb[o0], acc0, 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) out[r] = acc0[r] + acc1[r];
 }
 
 // What a lane is, in a tile
@@ -116,27 +85,11 @@ __global__ __launch_bounds__(64 * kMhaWaves) void mha_core_fwd_k(MhaOperand q, M
   if (tile >= G.tiles) return;                      // (no barrier in this kernel: a spare wave may leave)
   const MhaLane m = mha_lane(G, tile, lane);
 
-  float sc[4];
-  contract_channels(k.p + prob_off(G, m.p_lo, k.ss) + m.pos_lo, q.p + prob_off(G, m.p_lo, q.ss) + m.pos_lo, G.d, G.L,
-                    m.h, sc);
+  float raw[4], p[4];
+  contract_channels(k.p + prob_off(G, m.p_lo, k.ss) + m.pos_lo, q.p + prob_off(G, m.p_lo, q.ss) + m.pos_lo, 0,
+                    G.d >> 2, G.L, m.h, raw);
   // lane holds S[i = lo][j = 4h + r]; keep only the j of the problem of row i
-  float mx = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    sc[r] = m.same ? sc[r] * G.inv : -INFINITY;
-    mx = fmaxf(mx, sc[r]);
-  }
-  mx = xor32_max(xor16_max(mx));
-  float p[4], den = 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    p[r] = m.same ? __expf(sc[r] - mx) : 0.f;
-    den += p[r];
-  }
-  den = xor32_sum(xor16_sum(den));
-  const float rden = 1.f / den;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) p[r] *= rden;
+  tile_softmax(raw, G.inv, m.same, p);
   if (m.same && m.v_lo) {
     st4(P + m.pe, make_float4(p[0], p[1], p[2], p[3]));                    // saved BEFORE dropout
     const float4 dm = drop_mult4(drop_rt, (uint64_t)m.pe);
@@ -153,11 +106,7 @@ __global__ __launch_bounds__(64 * kMhaWaves) void mha_core_fwd_k(MhaOperand q, M
     const bool vc = c < G.d;
     const int cc = vc ? c : G.d - 1;
     const float4 vv = ld4(vb + (int64_t)cc * G.L);
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[0], vv.x, o, 0, 0, 0);
-    o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[1], vv.y, o, 0, 0, 0);
-    o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[2], vv.z, o, 0, 0, 0);
-    o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[3], vv.w, o, 0, 0, 0);
+    const f32x4 o = tile_apply(p, vv, f32x4{0.f, 0.f, 0.f, 0.f});
     if (vc && m.v_h) st4(ob + (int64_t)c * G.L, make_float4(o[0], o[1], o[2], o[3]));
   }
 }
@@ -186,21 +135,16 @@ __global__ __launch_bounds__(64 * kMhaWaves) void mha_core_bwd_k(const float* __
   }
   // dP[i = lo][j = 4h + r] = mask * sum_c dO[c][i] V[c][j]
   float dP[4];
-  contract_channels(v.p + prob_off(G, m.p_lo, v.ss) + m.pos_lo, dO + prob_off(G, m.p_lo, oss) + m.pos_lo, G.d, G.L,
-                    m.h, dP);
-  float rowdot = 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    dP[r] *= pm[r];
-    rowdot += dP[r] * p[r];
-  }
-  rowdot = xor32_sum(xor16_sum(rowdot));
+  contract_channels(v.p + prob_off(G, m.p_lo, v.ss) + m.pos_lo, dO + prob_off(G, m.p_lo, oss) + m.pos_lo, 0,
+                    G.d >> 2, G.L, m.h, dP);
   float ds[4], pd[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    ds[r] = p[r] * (dP[r] - rowdot) * G.inv;        // dS / sqrt(d): what dQ and dK contract with
+    dP[r] *= pm[r];
     pd[r] = p[r] * pm[r];                           // P'
   }
+  tile_softmax_bwd(p, dP, G.inv, ds);               // dS / sqrt(d): what dQ and dK contract with
+  // (the transposes stay written out, as in sdpa_bwd_body: see the note there)
   float* tP = tr[wave][0];
   float* tS = tr[wave][1];
 #pragma unroll
@@ -227,22 +171,10 @@ __global__ __launch_bounds__(64 * kMhaWaves) void mha_core_bwd_k(const float* __
     const bool vc = c < G.d;
     const int64_t co = (int64_t)(vc ? c : G.d - 1) * G.L;
     const float4 gv = ld4(dO + go + co), kv = ld4(k.p + ko + co), qv = ld4(q.p + qo + co);
-    f32x4 av = {0.f, 0.f, 0.f, 0.f}, aq = {0.f, 0.f, 0.f, 0.f}, ak = {0.f, 0.f, 0.f, 0.f};
-    // dV[c][j] = sum_i P'[i][j] dO[c][i]
-    av = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[0], gv.x, av, 0, 0, 0);
-    av = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[1], gv.y, av, 0, 0, 0);
-    av = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[2], gv.z, av, 0, 0, 0);
-    av = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[3], gv.w, av, 0, 0, 0);
-    // dQ[c][i] = sum_j dS[i][j] K[c][j]
-    aq = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[0], kv.x, aq, 0, 0, 0);
-    aq = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[1], kv.y, aq, 0, 0, 0);
-    aq = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[2], kv.z, aq, 0, 0, 0);
-    aq = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[3], kv.w, aq, 0, 0, 0);
-    // dK[c][j] = sum_i dS[i][j] Q[c][i]
-    ak = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[0], qv.x, ak, 0, 0, 0);
-    ak = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[1], qv.y, ak, 0, 0, 0);
-    ak = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[2], qv.z, ak, 0, 0, 0);
-    ak = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[3], qv.w, ak, 0, 0, 0);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 av = tile_apply(pw, gv, zero);      // dV[c][j] = sum_i P'[i][j] dO[c][i]
+    const f32x4 aq = tile_apply(ds, kv, zero);      // dQ[c][i] = sum_j dS[i][j] K[c][j]
+    const f32x4 ak = tile_apply(dsw, qv, zero);     // dK[c][j] = sum_i dS[i][j] Q[c][i]
     if (vc && live) {
       st4(dv.p + vo + co, make_float4(av[0], av[1], av[2], av[3]));
       st4(dq.p + dqo + co, make_float4(aq[0], aq[1], aq[2], aq[3]));
@@ -282,7 +214,7 @@ extern "C" int bmnas_mha_core_fwd(const float* q, const float* k, const float* v
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(O) || !aligned16(P)) return BMNAS_E_ARG;
   const int groups = (G.tiles + kMhaWaves - 1) / kMhaWaves;
   hipLaunchKernelGGL(mha_core_fwd_k, dim3(groups), dim3(64 * kMhaWaves), 0, (hipStream_t)stream, MhaOperand{q, q_ss},
-                     MhaOperand{k, k_ss}, MhaOperand{v, v_ss}, O, P, G, mha_cfg(drop));
+                     MhaOperand{k, k_ss}, MhaOperand{v, v_ss}, O, P, G, to_cfg(drop));
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -304,7 +236,7 @@ extern "C" int bmnas_mha_core_bwd(const float* dO, const float* q, const float* 
   const int groups = (G.tiles + kMhaWaves - 1) / kMhaWaves;
   hipLaunchKernelGGL(mha_core_bwd_k, dim3(groups), dim3(64 * kMhaWaves), 0, (hipStream_t)stream, dO,
                      MhaOperand{q, q_ss}, MhaOperand{k, k_ss}, MhaOperand{v, v_ss}, P, MhaResult{dq, dq_ss},
-                     MhaResult{dk, dk_ss}, MhaResult{dv, dv_ss}, G, mha_cfg(drop));
+                     MhaResult{dk, dk_ss}, MhaResult{dv, dv_ss}, G, to_cfg(drop));
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

@@ -5,7 +5,7 @@
 #include "common.hpp"
 #include "bn_fin.hpp"
 #include "mix_terms.hpp"
-#include "../../include/bmnas_hip.h"
+#include "drop_cfg.hpp"
 
 namespace {
 
@@ -14,12 +14,6 @@ __device__ __forceinline__ float row_sum(float v, int l4n) {
   if (l4n >= 2) v += lane_xor1(v);
   if (l4n >= 4) v += lane_xor2(v);
   return v;
-}
-
-inline DropCfg to_cfg(const bmnas_dropout_t& d) {
-  DropCfg c;
-  c.thr = d.thr; c.scale = d.scale; c.seed = d.seed; c.offset = d.offset; c.step = d.step;
-  return c;
 }
 
 // bmnas_bn_fin_t -> BnFin; < 0 on a bad descriptor

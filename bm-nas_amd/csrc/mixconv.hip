@@ -13,7 +13,7 @@
 // output tiles is 2 K elements each — nothing against a launch.
 #include "bn_fin.hpp"
 #include "mix_terms.hpp"
-#include "../../include/bmnas_hip.h"
+#include "drop_cfg.hpp"
 
 namespace {
 
@@ -153,12 +153,6 @@ __global__ __launch_bounds__(256) void mix_conv_fwd_k(MixConvArgs a) {
   }
 }
 
-inline DropCfg mc_cfg(const bmnas_dropout_t& d) {
-  DropCfg c;
-  c.thr = d.thr; c.scale = d.scale; c.seed = d.seed; c.offset = d.offset; c.step = d.step;
-  return c;
-}
-
 }  // namespace
 
 extern "C" int bmnas_node_mix_conv_fwd_ok(int b, int C, int L, int n_src) {
@@ -202,7 +196,7 @@ extern "C" int bmnas_node_mix_conv_fwd(const float* x, const float* y, const flo
     }
     a.fin = f;
   }
-  a.dglu = mc_cfg(drop_glu); a.dfc = mc_cfg(drop_fc);
+  a.dglu = to_cfg(drop_glu); a.dfc = to_cfg(drop_fc);
   a.W = W; a.bias = bias; a.V = V; a.stat = stat; a.stat_shards = stat_shards; a.ldw = ldw; a.nsrc = n_src;
   a.b = b; a.C = C; a.L = L;
   a.Lb = L == 4 ? 2 : (L == 8 ? 3 : 4);

@@ -57,7 +57,7 @@ extern "C" int bmnas_sdpa_ln_fwd(const float* x, const float* y, const float* ln
                                  int C, int L, bmnas_dropout_t drop, void* stream) {
   if (!x || !y || !ln_w || !ln_b || !out || !xhat || !stats || b < 0) return BMNAS_E_ARG;
   SdpaGeom G;
-  if (int e = geom(b, C, L, &G)) return e;
+  if (int e = sdpa_geom(b, C, L, &G)) return e;
   if (b == 0) return 0;
   const int groups = (b + G.spw - 1) / G.spw;
 #define SDPA_F(K)                                                                                     \
@@ -75,7 +75,7 @@ extern "C" int bmnas_sdpa_ln_bwd(const float* g, const float* gscale, const floa
                                  int b, int C, int L, bmnas_dropout_t drop, void* stream) {
   if (!g || !x || !y || !ln_w || !xhat || !stats || !dx || b < 0) return BMNAS_E_ARG;
   SdpaGeom G;
-  if (int e = geom(b, C, L, &G)) return e;
+  if (int e = sdpa_geom(b, C, L, &G)) return e;
   if (b == 0) return 0;
   const size_t lds = sdpa_bwd_lds(C);
   const int groups = (b + G.spw - 1) / G.spw;

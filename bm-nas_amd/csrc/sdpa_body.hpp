@@ -1,10 +1,10 @@
 // Device-side bodies of the K3 kernels (see sdpa.hip for the design notes).  Kept in a header so
 // that the same code can run as its own launch (sdpa.hip) or share a launch with the conv GEMM
 // that consumes the same input (conv1x1.hip: the 128 attention workgroups only fill half of the
-// 256 CUs, the GEMM tiles fill the rest).
+// 256 CUs, the GEMM tiles fill the rest).  The per-lane arithmetic of the packed score tile is attn_tile.hpp's.
 #pragma once
-#include "common.hpp"
-#include "../../include/bmnas_hip.h"
+#include "attn_tile.hpp"
+#include "drop_cfg.hpp"
 
 namespace {
 
@@ -40,14 +40,6 @@ __device__ __forceinline__ float wg_sample_sum(float v, int L, int Lb, float (*r
   return red[0][slot] + red[1][slot] + red[2][slot] + red[3][slot];
 }
 
-// One MFMA k-step of the channel contraction: A = yb[c][.] (rows j), B = xb[c][.] (cols i)
-#define SDPA_KSTEP(ACC, T)                                                         \
-  do {                                                                             \
-    const int64_t o_ = (int64_t)(4 * (T) + h) * G.L;                               \
-    const float a_ = v_lo ? yb[o_] : 0.f, b_ = v_lo ? xb[o_] : 0.f;                \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(a_, b_, ACC, 0, 0, 0);              \
-  } while (0)
-
 // Softmax probabilities P[i = lo][j = 4h + r] of this tile group, identical in all 4 waves.
 __device__ __forceinline__ void attn_probs(const float* __restrict__ x, const float* __restrict__ y,
                                            const SdpaGeom& G, int g, int wave, int lane, float4* ldsS,
@@ -57,54 +49,20 @@ __device__ __forceinline__ void attn_probs(const float* __restrict__ x, const fl
   // block-diagonal mask keeps them away from real rows and nothing of theirs is stored
   int s_lo = g * G.spw + (lo >> G.Lb);
   s_lo = s_lo < G.b ? s_lo : G.b - 1;
-  const bool v_lo = true;
   const int64_t base = ((int64_t)s_lo * G.C) * G.L + (lo & (G.L - 1));
   const float* xb = x + base;
   const float* yb = y + base;
   const int per = G.C / 16;                       // k-steps (of 4 channels) per wave
-  const int t0 = wave * per, t1 = t0 + per;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  int t = t0;
-  for (; t + 3 < t1; t += 4) {                    // 8 loads in flight, then 4 MFMAs
-    const int64_t o0 = (int64_t)(4 * t + h) * G.L, st = (int64_t)4 * G.L;
-    const float a0 = v_lo ? yb[o0] : 0.f, b0 = v_lo ? xb[o0] : 0.f;
-    const float a1 = v_lo ? yb[o0 + st] : 0.f, b1 = v_lo ? xb[o0 + st] : 0.f;
-    const float a2 = v_lo ? yb[o0 + 2 * st] : 0.f, b2 = v_lo ? xb[o0 + 2 * st] : 0.f;
-    const float a3 = v_lo ? yb[o0 + 3 * st] : 0.f, b3 = v_lo ? xb[o0 + 3 * st] : 0.f;
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b3, acc1, 0, 0, 0);
-  }
-  for (; t < t1; ++t) SDPA_KSTEP(acc0, t);
-  ldsS[wave * 64 + lane] = make_float4(acc0[0] + acc1[0], acc0[1] + acc1[1], acc0[2] + acc1[2],
-                                       acc0[3] + acc1[3]);
+  const int t0 = wave * per, t1 = t0 + per;       // (t1 as t0 + per: the compiler then sees a wave-uniform trip count)
+  float part[4];                                  // this wave's quarter of C: A = y (rows j), B = x (cols i)
+  contract_channels(yb, xb, t0, t1, G.L, h, part);
+  ldsS[wave * 64 + lane] = make_float4(part[0], part[1], part[2], part[3]);
   __syncthreads();
   const float4 s0 = ldsS[lane], s1 = ldsS[64 + lane], s2 = ldsS[128 + lane], s3 = ldsS[192 + lane];
   const float raw[4] = {(s0.x + s1.x) + (s2.x + s3.x), (s0.y + s1.y) + (s2.y + s3.y),
                         (s0.z + s1.z) + (s2.z + s3.z), (s0.w + s1.w) + (s2.w + s3.w)};
   // lane holds S[i = lo][j = 4h + r]; keep only j in the same sample as i
-  const float inv = 1.f / sqrtf((float)G.C);
-  const bool same = ((4 * h) >> G.Lb) == (lo >> G.Lb);
-  float sc[4], mx = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    sc[r] = same ? raw[r] * inv : -INFINITY;
-    mx = fmaxf(mx, sc[r]);
-  }
-  mx = xor16_max(mx);
-  mx = xor32_max(mx);
-  float den = 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    p[r] = same ? __expf(sc[r] - mx) : 0.f;
-    den += p[r];
-  }
-  den = xor16_sum(den);
-  den = xor32_sum(den);
-  const float rden = 1.f / den;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) p[r] *= rden;
+  tile_softmax(raw, 1.f / sqrtf((float)G.C), ((4 * h) >> G.Lb) == (lo >> G.Lb), p);
 }
 
 // g = tile group (one workgroup of 256 threads each)
@@ -148,11 +106,7 @@ __device__ __forceinline__ void sdpa_fwd_body(const int g, const float* __restri
     const int ch = wave + 4 * k;
     od[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (ch < nch) {                                      // wave-uniform
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[0], yv[k].x, o, 0, 0, 0);
-      o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[1], yv[k].y, o, 0, 0, 0);
-      o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[2], yv[k].z, o, 0, 0, 0);
-      o = __builtin_amdgcn_mfma_f32_16x16x4f32(p[3], yv[k].w, o, 0, 0, 0);
+      const f32x4 o = tile_apply(p, yv[k], f32x4{0.f, 0.f, 0.f, 0.f});   // o[c][i] = sum_j P[i][j] y[c][j]
       const int64_t e = ((int64_t)sh * G.C + ch * 16 + lo) * G.L + l0;
       const float4 m = v_h ? drop_mult4(drop_rt, (uint64_t)e) : make_float4(0.f, 0.f, 0.f, 0.f);
       od[k] = make_float4(o[0] * m.x, o[1] * m.y, o[2] * m.z, o[3] * m.w);
@@ -279,7 +233,6 @@ __device__ __forceinline__ void sdpa_bwd_body(
   {
     int s_lo = g * G.spw + (lo >> G.Lb);
     s_lo = s_lo < G.b ? s_lo : G.b - 1;                  // clamped; dO of padded samples is zero
-    const bool v_lo = true;
     const float* yb = y + ((int64_t)s_lo * G.C) * G.L + (lo & (G.L - 1));
     const int per = G.C / 16;
     const int t0 = wave * per, t1 = t0 + per;
@@ -287,14 +240,14 @@ __device__ __forceinline__ void sdpa_bwd_body(
     int t = t0;
     for (; t + 1 < t1; t += 2) {
       const int c0 = 4 * t + h, c1 = c0 + 4;
-      const float a0 = v_lo ? yb[(int64_t)c0 * G.L] : 0.f, a1 = v_lo ? yb[(int64_t)c1 * G.L] : 0.f;
+      const float a0 = yb[(int64_t)c0 * G.L], a1 = yb[(int64_t)c1 * G.L];
       const float b0 = dOt[c0 * 17 + lo], b1 = dOt[c1 * 17 + lo];
       acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc1, 0, 0, 0);
     }
     if (t < t1) {
       const int c0 = 4 * t + h;
-      const float a0 = v_lo ? yb[(int64_t)c0 * G.L] : 0.f;
+      const float a0 = yb[(int64_t)c0 * G.L];
       acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, dOt[c0 * 17 + lo], acc0, 0, 0, 0);
     }
     __syncthreads();                                   // ldsS is being reused
@@ -304,15 +257,10 @@ __device__ __forceinline__ void sdpa_bwd_body(
     const float4 q0 = ldsS[lane], q1 = ldsS[64 + lane], q2 = ldsS[128 + lane], q3 = ldsS[192 + lane];
     const float dP[4] = {(q0.x + q1.x) + (q2.x + q3.x), (q0.y + q1.y) + (q2.y + q3.y),
                          (q0.z + q1.z) + (q2.z + q3.z), (q0.w + q1.w) + (q2.w + q3.w)};
-    float rowdot = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rowdot += dP[r] * p[r];
-    rowdot = xor16_sum(rowdot);
-    rowdot = xor32_sum(rowdot);
-    const float inv = 1.f / sqrtf((float)G.C);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ds[r] = p[r] * (dP[r] - rowdot) * inv;
+    tile_softmax_bwd(p, dP, 1.f / sqrtf((float)G.C), ds);
   }
+  // (the transposes through the 16 x 17 images stay written out: as helpers taking a float* they cost every
+  // sdpa_ln_bwd_k instantiation two VGPRs, and KCH = 2 a wave of occupancy)
 #pragma unroll
   for (int r = 0; r < 4; ++r) tS[wave][lo * 17 + 4 * h + r] = ds[r];
   __syncthreads();
@@ -326,21 +274,11 @@ __device__ __forceinline__ void sdpa_bwd_body(
     const int ch = wave + 4 * k;
     if (ch >= nch) continue;                                     // wave-uniform
     const int64_t e = ((int64_t)sh * G.C + ch * 16 + lo) * G.L + l0;
-    f32x4 ax = {0.f, 0.f, 0.f, 0.f}, ay = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     // dx[c][i]  = sum_j dS[i][j] y[c][j]
-    ax = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[0], yv[k].x, ax, 0, 0, 0);
-    ax = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[1], yv[k].y, ax, 0, 0, 0);
-    ax = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[2], yv[k].z, ax, 0, 0, 0);
-    ax = __builtin_amdgcn_mfma_f32_16x16x4f32(ds[3], yv[k].w, ax, 0, 0, 0);
-    // dy[c][j]  = sum_i dS[i][j] x[c][i] + sum_i P[i][j] dO[c][i]
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[0], xv[k].x, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[1], xv[k].y, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[2], xv[k].z, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(dsw[3], xv[k].w, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[0], dv[k].x, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[1], dv[k].y, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[2], dv[k].z, ay, 0, 0, 0);
-    ay = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[3], dv[k].w, ay, 0, 0, 0);
+    const f32x4 ax = tile_apply(ds, yv[k], zero);
+    // dy[c][j]  = sum_i dS[i][j] x[c][i] + sum_i P[i][j] dO[c][i], in this order on one accumulator
+    const f32x4 ay = tile_apply(pw, dv[k], tile_apply(dsw, xv[k], zero));
     if (v_h) {
       float4 rx = make_float4(ax[0], ax[1], ax[2], ax[3]);
       float4 ry = make_float4(ay[0], ay[1], ay[2], ay[3]);
@@ -356,19 +294,12 @@ __device__ __forceinline__ void sdpa_bwd_body(
   }
 }
 
-inline int geom(int b, int C, int L, SdpaGeom* G) {
+inline int sdpa_geom(int b, int C, int L, SdpaGeom* G) {
   if (!(L == 4 || L == 8 || L == 16) || C % 16 != 0 || C < 16) return BMNAS_E_SHAPE;
   if (C > 4 * kMaxCh * 16) return BMNAS_E_LIMIT;
   G->b = b; G->C = C; G->L = L; G->Lb = ilog2_exact(L); G->spw = 16 / L;
   return 0;
 }
-
-inline DropCfg to_cfg(const bmnas_dropout_t& d) {
-  DropCfg c;
-  c.thr = d.thr; c.scale = d.scale; c.seed = d.seed; c.offset = d.offset; c.step = d.step;
-  return c;
-}
-
 
 inline size_t sdpa_bwd_lds(int C) { return kSdpaBwdFixedLds + (size_t)C * 17 * 4; }
 
