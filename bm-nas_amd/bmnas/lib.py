@@ -1150,10 +1150,9 @@ def adam_multi_ex(table, chunks, n_chunks, hyp, max_exp_avg_sq, flags, partials=
     float* per descriptor of `table` (the running maxima; None without ADAM_AMSGRAD).  ADAM_DECOUPLED: slot 5 of a `hyp`
     row holds float(1 - lr * weight_decay) instead of weight_decay.  Clips iff partials is given (then clip and norm_out
     too, as for adam_multi_clip).  flags == 0 runs the kernels of adam_multi / adam_multi_clip."""
-    p = lambda t: None if t is None else t.data_ptr()
-    _check(load().bmnas_adam_multi_ex(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), p(max_exp_avg_sq),
-                                      int(flags), p(partials), n_parts, p(clip), p(norm_out), _stream()),
-           'adam_multi_ex')
+    _check(load().bmnas_adam_multi_ex(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(),
+                                      _opt(max_exp_avg_sq), int(flags), _opt(partials), n_parts, _opt(clip),
+                                      _opt(norm_out), _stream()), 'adam_multi_ex')
 
 
 def grad_scale_multi(table, chunks, n_chunks, partials, n_parts, clip, norm_out):
@@ -1170,9 +1169,8 @@ def sgd_multi(table, chunks, n_chunks, hyp, flags, partials=None, n_parts=0, cli
     exp_avg_sq unused) in one launch; flags = SGD_MOMENTUM | SGD_NESTEROV.  hyp: float32 device (rows, 8) holding
     { -lr, mu, 1 - dampening, mu_n, weight_decay, 0, 0, 0 } (a first-step row: mu = 0, damp1 = 1 over a zero buffer).
     Clips iff partials is given (then clip and norm_out too, as for adam_multi_clip).  `.grad` is NOT written."""
-    p = lambda t: None if t is None else t.data_ptr()
     _check(load().bmnas_sgd_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), int(flags),
-                                  p(partials), n_parts, p(clip), p(norm_out), _stream()), 'sgd_multi')
+                                  _opt(partials), n_parts, _opt(clip), _opt(norm_out), _stream()), 'sgd_multi')
 
 
 UNROLL_MOMENTUM = 1                          # BMNAS_UNROLL_* (include/bmnas_hip.h)

@@ -27,15 +27,18 @@ is one kernel instantiation: all groups of an optimizer must agree on each switc
 `SGD` is torch.optim.SGD (momentum, dampening, nesterov, L2 weight decay; DARTS' weight optimizer, reference
 models/search/darts/train_search.py:84-88) on the same machinery: the descriptor table, chunk list, staging buffer,
 by-value scalar rows and norm launch are Adam's, the update is one `bmnas_sgd_multi` launch, and `max_grad_norm` means
-what it means for Adam.  `_OneLaunch` holds what the two classes share; each class says which state tensors a descriptor
-points at (`_state_ptrs`), what a scalar row holds (`_build`'s row key, `prepare_replay`) and which launch to issue
-(`_launch`).
+what it means for Adam.  `_OneLaunch` holds what the two classes share — the plan builder over `staging_layout` (the one
+place that knows the staging buffer's byte offsets), the switch between plans, the copy and norm launch that open a step,
+the refusals that open `prepare_replay` —; each class says which state tensors a descriptor points at (`_state_ptrs`),
+what keys a scalar row (`_row_count`) and what it holds (`prepare_replay`), which entries of the plan are its own
+(`_plan_fields`) and which launch updates (`_update`).
 
 `UnrolledStep` (beside `clip_grad_norm_`, at the end) is no optimizer: it holds the weight-side arithmetic of DARTS'
 unrolled architecture step — virtual weight step, +-R perturbation, restore, and the combine over alpha — on the kernels
 of csrc/unroll.hip, over the same descriptor table, chunk list and norm launch, reading a weight optimizer's groups and
 momentum buffers without writing them.
 """
+import collections
 import math
 
 import numpy as np
@@ -49,11 +52,66 @@ _DESC = np.dtype([('param', '<u8'), ('grad', '<u8'), ('exp_avg', '<u8'), ('exp_a
 assert _DESC.itemsize == 48
 
 
+StagingLayout = collections.namedtuple(
+    'StagingLayout', 'row_bytes hyp_slot hyp_bytes tab_bytes tab_slot nbytes rows_at clip_at tab_at tail_at')
+
+
+def staging_layout(n_rows, n_tensors, slots=1, clip=False, tail_ptrs_per_tensor=0):
+    """The byte offsets of a plan's ONE staging buffer (pinned, and its device copy) — the one place that knows them; they
+    are baked into captured graphs, into the poke-mode blob and into what the kernels read behind a descriptor table.
+
+        scalar region   per slot: n_rows rows of 8 floats (32 bytes each), then — when clipping — max_grad_norm in 16
+                        bytes of its own (the next slot's rows stay 16-byte aligned).  The slots are packed back to back:
+                        the whole region travels by value in poke mode.  Rounded up to 64 bytes (`hyp_bytes`).
+        table region    per slot: n_tensors descriptors of 48 bytes (bmnas_adam_tensor_t) — the table is shared with the
+                        norm launch and stays 48 bytes per tensor —, then 8 * tail_ptrs_per_tensor bytes per tensor
+                        (AMSGrad: one `float*` per descriptor, max_exp_avg_sq), which so travel with the table's upload.
+
+    slots > 1: a captured graph that holds `slots` consecutive optimizer steps (bmnas.graph.GraphedTrainStep(k=...)): every
+    step has its own scalar rows and its own descriptor table (each step's backward leaves its gradients in tensors of
+    its own).  -> sizes (`hyp_slot`, `tab_slot`: a slot's stride in its region) and, per slot, where its rows, its clip
+    scalar (None without clipping), its table and its tail pointers start."""
+    row_bytes = n_rows * 32
+    hyp_slot = row_bytes + (16 if clip else 0)
+    hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
+    tab_bytes = n_tensors * _DESC.itemsize
+    tab_slot = tab_bytes + n_tensors * 8 * tail_ptrs_per_tensor
+    rows_at = [i * hyp_slot for i in range(slots)]
+    tab_at = [hyp_bytes + i * tab_slot for i in range(slots)]
+    return StagingLayout(row_bytes, hyp_slot, hyp_bytes, tab_bytes, tab_slot, hyp_bytes + slots * tab_slot, rows_at,
+                         [o + row_bytes for o in rows_at] if clip else None, tab_at, [o + tab_bytes for o in tab_at])
+
+
+def _chunk_list(numels, device):
+    """-> (int32 tensor (n, 2) on `device`, n): one (tensor index, chunk index) per workgroup of a multi-tensor launch."""
+    E = lib.adam_chunk_elems()
+    chunks = [(i, c) for i, n in enumerate(numels) for c in range((n + E - 1) // E)]
+    return torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(device), len(chunks)
+
+
 class _OneLaunch:
-    """What bmnas.optim.Adam and bmnas.optim.SGD share: the eager step over a plan, the captured plan and its replay
-    protocol (capture_safe / captured_plan / activate / prepare_replay / replay_blob / wait_staging / mark_launched),
-    and max_grad_norm.  Mixed in FRONT of the torch optimizer class.  The class supplies `_NAME`, `_variant()` (the key
-    of a plan, clipping first), `_build(active, slots)`, `_switch(plan)`, `_launch(slot)` and `prepare_replay(slot)`."""
+    """What bmnas.optim.Adam and bmnas.optim.SGD share: the plan and its builder (`_build`, over `staging_layout`), the
+    eager step over a plan, the captured plan and its replay protocol (capture_safe / captured_plan / activate /
+    prepare_replay / replay_blob / wait_staging / mark_launched), switching between plans, and max_grad_norm.  Mixed in
+    FRONT of the torch optimizer class.  The class supplies `_NAME`, `_SHARED` (what the tensors of a row share, for
+    `_switch`'s refusal), `_variant()` (the key of a plan: clipping first, then `_switches()`), `_row_count(p, switches)`
+    (a tensor's row count as the state has it now), `_plan_fields(switches)`, `_state_ptrs(plan)`, `_update(...)` (the
+    launch of the update) and `prepare_replay(slot)`."""
+
+    def _init_one_launch(self, max_grad_norm):
+        self.max_grad_norm = max_grad_norm
+        self._clip_value()
+        self._plan = None
+        self._eager_plan = None
+        self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
+        self._touch = 0          # bumped by everything that may re-point .grad or move the step counts outside a replay
+
+    def _state_replaced(self):
+        """After load_state_dict(): the state tensors are new objects (or gone) — eager steps rebuild their plan, a captured
+        plan (held by its GraphedTrainStep) re-reads pointers and counts in activate()."""
+        self._plan = None
+        self._eager_plan = None
+        self._gen += 1
 
     def _clip_value(self):
         """max_grad_norm as a float (validated), or None."""
@@ -81,6 +139,105 @@ class _OneLaunch:
     # ------------------------------------------------------------------ plan
     def _active(self):
         return [(p, gi) for gi, g in enumerate(self.param_groups) for p in g['params'] if p.grad is not None]
+
+    def _flush_counts(self):
+        """Write the plan's row counts back into the optimizer's state, where the state keeps them (Adam's `step`)."""
+
+    def _build(self, active, slots=1):
+        """The plan of `slots` consecutive steps over `active`, in ONE staging buffer (staging_layout).  Tensors of one group
+        with the same `_row_count` share a row of scalars; `count` of a row is that count, advanced by prepare_replay()."""
+        key = self._variant()
+        clip, sw = key[0], key[1:]
+        self._flush_counts()
+        dev = active[0][0].device
+        rows, row_idx, row_of = [], {}, []
+        for p, gi in active:
+            if not p.is_cuda:
+                raise lib.BmnasError(f'{self._NAME} needs parameters on the GPU (HIP kernel, no CPU path)')
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise lib.BmnasError(f'{self._NAME}: parameter must be contiguous fp32 on {dev}')
+            rk = (gi, self._row_count(p, sw))
+            if rk not in row_idx:
+                row_idx[rk] = len(rows)
+                rows.append(rk)
+            row_of.append(row_idx[rk])
+        fields, tail = self._plan_fields(sw)
+        lay = staging_layout(len(rows), len(active), slots, clip, tail)
+        pin = torch.zeros(lay.nbytes, dtype=torch.uint8).pin_memory()
+        host = pin.numpy()
+        devbuf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=dev)
+        tabs = [host[o:o + lay.tab_bytes].view(_DESC) for o in lay.tab_at]
+        for tab in tabs:
+            tab['numel'] = [p.numel() for p, _ in active]
+            tab['hyp_row'] = row_of
+        hyps = [host[o:o + lay.row_bytes].view(np.float32).reshape(len(rows), 8) for o in lay.rows_at]
+        chunks, n_chunks = _chunk_list([p.numel() for p, _ in active], dev)
+        self._plan = dict(ids=tuple(id(p) for p, _ in active), active=active, row_of=row_of, gen=self._gen,
+                          groups=[gi for gi, _ in rows], count=[c for _, c in rows],
+                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * lay.hyp_slot], tabs=tabs,
+                          dev=devbuf, dev_hyp=devbuf[:lay.hyp_bytes],
+                          dev_hyps=[devbuf[o:o + lay.hyp_slot] for o in lay.rows_at],
+                          dev_tabs=[devbuf[o:o + lay.tab_bytes] for o in lay.tab_at],
+                          chunks=chunks, n_chunks=n_chunks, slots=slots, cap_slot=0, clip=clip, key=key, **fields)
+        if tail:                 # (Adam's running maxima)
+            size = lay.tab_slot - lay.tab_bytes
+            self._plan.update(maxes=[host[o:o + size].view('<u8') for o in lay.tail_at],
+                              dev_maxes=[devbuf[o:o + size] for o in lay.tail_at])
+        self._state_ptrs(self._plan)
+        if clip:
+            # the norm launch's partials, the max_grad_norm scalars (host + device view) and the norm outputs belong to the
+            # plan: a captured plan's graph reads and writes these addresses for good
+            parts = lib.grad_norm_parts()
+            self._plan.update(
+                n_parts=min(n_chunks, parts),
+                partials=[torch.empty(parts, dtype=torch.float32, device=dev) for _ in range(slots)],
+                clips=[host[o:o + 4].view(np.float32) for o in lay.clip_at],
+                dev_clips=[devbuf[o:o + 4] for o in lay.clip_at],
+                norms=torch.zeros(slots, dtype=torch.float32, device=dev))
+
+    def _switch(self, plan):
+        """Make `plan` current: the row counts are re-read from the state (`_row_count`), the state pointers when
+        load_state_dict() replaced the state tensors."""
+        if self._plan is not plan:
+            self._flush_counts()
+            counts = {}
+            for (p, _), r in zip(plan['active'], plan['row_of']):
+                c = self._row_count(p, plan['key'][1:])
+                if counts.setdefault(r, c) != c:
+                    raise lib.BmnasError(f'{self._NAME}: parameters that shared {self._SHARED} when this plan was built '
+                                         'have diverged (an eager step on a subset?); re-capture the graph')
+            for r, c in counts.items():
+                plan['count'][r] = c
+            self._plan = plan
+        if not plan.get('poke'):
+            self.wait_staging()              # the plan's last launch has consumed its pinned buffer
+        if plan['gen'] != self._gen:
+            self._state_ptrs(plan)
+            plan['gen'] = self._gen
+
+    def _begin_replay(self, slot, switched):
+        """What opens prepare_replay(): refuse a plan built for other launches than the optimizer now asks for, and stage
+        max_grad_norm.  switched: the class' words for its switches having changed."""
+        pl = self._plan
+        c = self._clip_value()
+        if (c is not None) != pl['clip']:
+            raise lib.BmnasError(f'{self._NAME}: max_grad_norm was switched between None and a value under a plan built '
+                                 'for the other (a captured step holds the launches of one of them); re-capture the graph')
+        if self._switches() != pl['key'][1:]:
+            raise lib.BmnasError(f'{self._NAME}: {switched} under a plan built for the other value (a captured step holds '
+                                 'the launches of one of them); re-capture the graph')
+        if c is not None:
+            pl['clips'][slot][0] = c
+
+    def _launch(self, slot=0):
+        pl = self._plan
+        if not pl.get('poke') and slot == 0:
+            pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
+        args, clip_args = (pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot]), ()
+        if pl['clip']:
+            lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
+            clip_args = (pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
+        self._update(pl, slot, args, clip_args)
 
     def _stage(self, active):
         """Advance the step counts; write this step's scalars and pointers into the staging buffer."""
@@ -140,7 +297,7 @@ class _OneLaunch:
         ids = tuple(id(p) for p, _ in active)
         if self._plan is None or self._plan.get('captured') or self._plan['ids'] != ids or self._plan['key'] != key:
             # never stage an eager step through a captured plan: its graph re-reads those buffers
-            eager = getattr(self, '_eager_plan', None)
+            eager = self._eager_plan
             if eager is not None and eager['ids'] == ids and eager['key'] == key:
                 self._switch(eager)
             else:
@@ -243,6 +400,7 @@ class _OneLaunch:
 
 class Adam(_OneLaunch, torch.optim.Adam):
     _NAME = 'bmnas.optim.Adam'
+    _SHARED = 'a step count'
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
                  max_grad_norm=None, *, decoupled_weight_decay=False):
@@ -256,11 +414,7 @@ class Adam(_OneLaunch, torch.optim.Adam):
         in the update's registers.  `last_grad_norm` / `grad_norms` hold the pre-clip norm(s) on the device."""
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad),
                          decoupled_weight_decay=bool(decoupled_weight_decay))
-        self.max_grad_norm = max_grad_norm
-        self._clip_value()
-        self._plan = None
-        self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
-        self._touch = 0          # bumped by everything that may re-point .grad or move the step counts outside a replay
+        self._init_one_launch(max_grad_norm)
 
     def _variant(self):
         """-> (clip, amsgrad, decoupled): what selects the launches of a step, the key of a plan.  The two switches are
@@ -319,92 +473,23 @@ class Adam(_OneLaunch, torch.optim.Adam):
             for (p, _), r in zip(pl['active'], pl['row_of']):
                 self.state[p]['step'].fill_(pl['count'][r])
 
-    def _build(self, active, slots=1):
-        """slots > 1: a captured graph that holds `slots` consecutive optimizer steps (bmnas.graph.GraphedTrainStep(k=...)):
-        every step has its own scalar rows and its own descriptor table (each step's backward leaves its gradients in
-        tensors of its own), all in the ONE staging buffer."""
-        clip, amsgrad, decoupled = self._variant()
-        self._flush_counts()
-        dev = active[0][0].device
-        E = lib.adam_chunk_elems()
-        rows, row_idx, row_of, chunks = [], {}, [], []
-        for i, (p, gi) in enumerate(active):
-            if not p.is_cuda:
-                raise lib.BmnasError('bmnas.optim.Adam needs parameters on the GPU (HIP kernel, no CPU path)')
-            st = self._init_state(p, amsgrad)
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise lib.BmnasError(f'bmnas.optim.Adam: parameter must be contiguous fp32 on {dev}')
-            # parameters of one group with the same step count share a row of scalars
-            key = (gi, float(st['step']))
-            if key not in row_idx:
-                row_idx[key] = len(rows)
-                rows.append(key)
-            row_of.append(row_idx[key])
-            chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
-        # (scalar slots packed back to back — 32 bytes per row —: the whole region travels by value in poke mode)
-        # clipping: max_grad_norm rides behind each slot's rows (16 bytes: the next slot's rows stay 16-byte aligned)
-        # amsgrad: one `float*` per descriptor (max_exp_avg_sq) rides BEHIND each slot's descriptor table — the table
-        # itself is shared with the norm launch and stays 48 bytes per tensor — so it travels with the table's upload
-        row_bytes = len(rows) * 32
-        hyp_slot = row_bytes + (16 if clip else 0)
-        hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
-        tab_bytes = len(active) * _DESC.itemsize
-        tab_slot = tab_bytes + (len(active) * 8 if amsgrad else 0)
-        nbytes = hyp_bytes + slots * tab_slot
-        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-        host = pin.numpy()
-        tabs = [host[hyp_bytes + i * tab_slot:hyp_bytes + i * tab_slot + tab_bytes].view(_DESC) for i in range(slots)]
-        for tab in tabs:
-            tab['numel'] = [p.numel() for p, _ in active]
-            tab['hyp_row'] = row_of
-        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        hyps = [host[i * hyp_slot:i * hyp_slot + row_bytes].view(np.float32).reshape(len(rows), 8) for i in range(slots)]
-        self._plan = dict(ids=tuple(id(p) for p, _ in active), active=active, row_of=row_of, gen=self._gen,
-                          groups=[gi for gi, _ in rows], count=[t for _, t in rows],
-                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * hyp_slot], tab=tabs[0], tabs=tabs,
-                          dev=devbuf, dev_hyp=devbuf[:hyp_bytes],
-                          dev_hyps=[devbuf[i * hyp_slot:(i + 1) * hyp_slot] for i in range(slots)],
-                          dev_tab=devbuf[hyp_bytes:hyp_bytes + tab_bytes],
-                          dev_tabs=[devbuf[hyp_bytes + i * tab_slot:hyp_bytes + i * tab_slot + tab_bytes]
-                                    for i in range(slots)],
-                          chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev),
-                          n_chunks=len(chunks), slots=slots, cap_slot=0, clip=clip, amsgrad=amsgrad,
-                          decoupled=decoupled, key=(clip, amsgrad, decoupled),
-                          flags=(lib.ADAM_AMSGRAD if amsgrad else 0) | (lib.ADAM_DECOUPLED if decoupled else 0))
-        if amsgrad:
-            at = lambda i: hyp_bytes + i * tab_slot + tab_bytes
-            self._plan.update(maxes=[host[at(i):at(i) + len(active) * 8].view('<u8') for i in range(slots)],
-                              dev_maxes=[devbuf[at(i):at(i) + len(active) * 8] for i in range(slots)])
-        self._state_ptrs(self._plan)
-        if clip:
-            # the norm launch's partials, the max_grad_norm scalars (host + device view) and the norm outputs belong to the
-            # plan: a captured plan's graph reads and writes these addresses for good
-            parts = lib.grad_norm_parts()
-            self._plan.update(
-                n_parts=min(len(chunks), parts),
-                partials=[torch.empty(parts, dtype=torch.float32, device=dev) for _ in range(slots)],
-                clips=[host[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4].view(np.float32) for i in range(slots)],
-                dev_clips=[devbuf[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4] for i in range(slots)],
-                norms=torch.zeros(slots, dtype=torch.float32, device=dev))
+    def _row_count(self, p, switches):
+        """p's step count (parameters of one group with the same step count share a row of scalars)."""
+        return float(self._init_state(p, switches[0])['step'])
 
-    def _launch(self, slot=0):
-        pl = self._plan
-        if not pl.get('poke') and slot == 0:
-            pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
-        if pl['clip']:
-            lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
+    def _plan_fields(self, switches):
+        """-> (the plan's own entries, tail pointers per tensor): amsgrad's max_exp_avg_sq pointers ride behind each table."""
+        amsgrad, decoupled = switches
+        return dict(amsgrad=amsgrad, decoupled=decoupled, flags=(lib.ADAM_AMSGRAD if amsgrad else 0) |
+                    (lib.ADAM_DECOUPLED if decoupled else 0)), int(amsgrad)
+
+    def _update(self, pl, slot, args, clip_args):
         if pl['flags']:
-            mx = pl['dev_maxes'][slot] if pl['amsgrad'] else None
-            if pl['clip']:
-                lib.adam_multi_ex(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], mx, pl['flags'],
-                                  pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
-            else:
-                lib.adam_multi_ex(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], mx, pl['flags'])
-        elif pl['clip']:
-            lib.adam_multi_clip(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot],
-                                pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
+            lib.adam_multi_ex(*args, pl['dev_maxes'][slot] if pl['amsgrad'] else None, pl['flags'], *clip_args)
+        elif clip_args:
+            lib.adam_multi_clip(*args, *clip_args)
         else:
-            lib.adam_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot])
+            lib.adam_multi(*args)
 
     def state_dict(self):
         self._flush_counts()
@@ -415,49 +500,16 @@ class Adam(_OneLaunch, torch.optim.Adam):
         for st in self.state.values():
             if torch.is_tensor(st.get('step')) and st['step'].is_cuda:
                 st['step'] = st['step'].cpu()
-        # the moment tensors are new objects: eager steps rebuild their plan, a captured plan
-        # (held by its GraphedTrainStep) re-reads pointers and counts in activate()
-        self._plan = None
-        self._eager_plan = None
-        self._gen += 1
-
-    def _switch(self, plan):
-        """Make `plan` current: step counts travel through the per-parameter `step` tensors, the
-        moment pointers are re-read when load_state_dict() replaced the state tensors."""
-        if self._plan is not plan:
-            self._flush_counts()
-            counts = {}
-            for (p, _), r in zip(plan['active'], plan['row_of']):
-                c = float(self._init_state(p, plan['amsgrad'])['step'])
-                if counts.setdefault(r, c) != c:
-                    raise lib.BmnasError('bmnas.optim.Adam: parameters that shared a step count when this plan was '
-                                         'built have diverged (an eager step on a subset?); re-capture the graph')
-            for r, c in counts.items():
-                plan['count'][r] = c
-            self._plan = plan
-        if not plan.get('poke'):
-            self.wait_staging()              # the plan's last launch has consumed its pinned buffer
-        if plan['gen'] != self._gen:
-            self._state_ptrs(plan)
-            plan['gen'] = self._gen
+        self._state_replaced()
 
     def prepare_replay(self, slot=0):
         """Advance the step count and publish the current learning rates for the next replay
         (call wait_staging() first and mark_launched() after the replay; GraphedTrainStep does).
         slot: which of the graph's consecutive steps these scalars are for — a graph of k steps takes k calls, slot 0
         first, each with the learning rates its step runs with (the scheduler moves them between two calls)."""
+        self._begin_replay(slot, "'amsgrad' / 'decoupled_weight_decay' was switched")
         pl = self._plan
         h = pl['hyps'][slot]
-        c = self._clip_value()
-        if (c is not None) != pl['clip']:
-            raise lib.BmnasError('bmnas.optim.Adam: max_grad_norm was switched between None and a value under a plan built '
-                                 'for the other (a captured step holds the launches of one of them); re-capture the graph')
-        if self._switches() != pl['key'][1:]:
-            raise lib.BmnasError("bmnas.optim.Adam: 'amsgrad' / 'decoupled_weight_decay' was switched under a plan built "
-                                 'for the other value (a captured step holds the launches of one of them); re-capture the '
-                                 'graph')
-        if c is not None:
-            pl['clips'][slot][0] = c
         for r, gi in enumerate(pl['groups']):
             g = self.param_groups[gi]
             pl['count'][r] += 1.0
@@ -508,6 +560,7 @@ class SGD(_OneLaunch, torch.optim.SGD):
     when a step that writes it is staged — state_dict() never shows an unstepped buffer as a stepped one.
     One launch is one kernel: all groups agree on `momentum != 0` and on `nesterov`; `maximize` is refused."""
     _NAME = 'bmnas.optim.SGD'
+    _SHARED = 'their first-step status'
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=None, *,
                  maximize=False):
@@ -515,11 +568,7 @@ class SGD(_OneLaunch, torch.optim.SGD):
             raise lib.BmnasError('bmnas.optim.SGD: maximize=True is not supported (the kernel descends)')
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                          nesterov=bool(nesterov))
-        self.max_grad_norm = max_grad_norm
-        self._clip_value()
-        self._plan = None
-        self._gen = 0            # bumped whenever the state tensors are replaced (load_state_dict)
-        self._touch = 0          # bumped by everything that may re-point .grad outside a replay
+        self._init_one_launch(max_grad_norm)
         self._pending = {}       # parameter -> zero momentum buffer that no staged step has written yet
 
     def _variant(self):
@@ -572,59 +621,14 @@ class SGD(_OneLaunch, torch.optim.SGD):
             tab['exp_avg'] = ptrs
             tab['exp_avg_sq'] = 0
 
-    def _build(self, active, slots=1):
-        """Adam._build's staging layout — scalar rows (+ max_grad_norm) per slot, then a descriptor table per slot, in ONE
-        pinned buffer and its device copy — with rows keyed by (group, first step or not); `count` of a row is how many
-        steps were staged for its tensors (0: the next one is their first)."""
-        clip, momentum, nesterov = self._variant()
-        dev = active[0][0].device
-        E = lib.adam_chunk_elems()
-        rows, row_idx, row_of, chunks = [], {}, [], []
-        for i, (p, gi) in enumerate(active):
-            if not p.is_cuda:
-                raise lib.BmnasError('bmnas.optim.SGD needs parameters on the GPU (HIP kernel, no CPU path)')
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise lib.BmnasError(f'bmnas.optim.SGD: parameter must be contiguous fp32 on {dev}')
-            key = (gi, 1.0 if not momentum or self._stepped(p) else 0.0)
-            if key not in row_idx:
-                row_idx[key] = len(rows)
-                rows.append(key)
-            row_of.append(row_idx[key])
-            chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
-        row_bytes = len(rows) * 32
-        hyp_slot = row_bytes + (16 if clip else 0)
-        hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
-        tab_bytes = len(active) * _DESC.itemsize
-        nbytes = hyp_bytes + slots * tab_bytes
-        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-        host = pin.numpy()
-        tabs = [host[hyp_bytes + i * tab_bytes:hyp_bytes + (i + 1) * tab_bytes].view(_DESC) for i in range(slots)]
-        for tab in tabs:
-            tab['numel'] = [p.numel() for p, _ in active]
-            tab['hyp_row'] = row_of
-        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        hyps = [host[i * hyp_slot:i * hyp_slot + row_bytes].view(np.float32).reshape(len(rows), 8) for i in range(slots)]
-        self._plan = dict(ids=tuple(id(p) for p, _ in active), active=active, row_of=row_of, gen=self._gen,
-                          groups=[gi for gi, _ in rows], count=[c for _, c in rows],
-                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * hyp_slot], tab=tabs[0], tabs=tabs,
-                          dev=devbuf, dev_hyp=devbuf[:hyp_bytes],
-                          dev_hyps=[devbuf[i * hyp_slot:(i + 1) * hyp_slot] for i in range(slots)],
-                          dev_tab=devbuf[hyp_bytes:hyp_bytes + tab_bytes],
-                          dev_tabs=[devbuf[hyp_bytes + i * tab_bytes:hyp_bytes + (i + 1) * tab_bytes]
-                                    for i in range(slots)],
-                          chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev),
-                          n_chunks=len(chunks), slots=slots, cap_slot=0, clip=clip, momentum=momentum,
-                          nesterov=nesterov, key=(clip, momentum, nesterov),
-                          flags=(lib.SGD_MOMENTUM if momentum else 0) | (lib.SGD_NESTEROV if nesterov else 0))
-        self._state_ptrs(self._plan)
-        if clip:
-            parts = lib.grad_norm_parts()
-            self._plan.update(
-                n_parts=min(len(chunks), parts),
-                partials=[torch.empty(parts, dtype=torch.float32, device=dev) for _ in range(slots)],
-                clips=[host[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4].view(np.float32) for i in range(slots)],
-                dev_clips=[devbuf[i * hyp_slot + row_bytes:i * hyp_slot + row_bytes + 4] for i in range(slots)],
-                norms=torch.zeros(slots, dtype=torch.float32, device=dev))
+    def _row_count(self, p, switches):
+        """How many steps were staged for p, as far as a row cares: 0 (the next one is its first) or 1."""
+        return 1.0 if not switches[0] or self._stepped(p) else 0.0
+
+    def _plan_fields(self, switches):
+        momentum, nesterov = switches
+        return dict(momentum=momentum, nesterov=nesterov, flags=(lib.SGD_MOMENTUM if momentum else 0) |
+                    (lib.SGD_NESTEROV if nesterov else 0)), 0
 
     def _stage(self, active):
         """The gradients are validated (and their pointers written) FIRST: prepare_replay() moves the pending zero
@@ -633,64 +637,24 @@ class SGD(_OneLaunch, torch.optim.SGD):
         self._write_ptrs(active)
         self.prepare_replay()
 
-    def _launch(self, slot=0):
-        pl = self._plan
-        if not pl.get('poke') and slot == 0:
-            pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
-        if pl['clip']:
-            lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
-            lib.sgd_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], pl['flags'],
-                          pl['partials'][slot], pl['n_parts'], pl['dev_clips'][slot], pl['norms'][slot:slot + 1])
-        else:
-            lib.sgd_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot], pl['flags'])
+    def _update(self, pl, slot, args, clip_args):
+        lib.sgd_multi(*args, pl['flags'], *clip_args)
 
     def load_state_dict(self, state_dict):
         if any(g.get('maximize', False) for g in state_dict['param_groups']):
             raise lib.BmnasError('bmnas.optim.SGD: the checkpoint has maximize=True, which is not supported (the kernel '
                                  'descends)')
         super().load_state_dict(state_dict)
-        # the buffers are new objects (or gone: a checkpoint from before the first step): eager steps rebuild their plan,
-        # a captured plan re-reads pointers and first-step status in activate()
-        self._pending = {}
-        self._plan = None
-        self._eager_plan = None
-        self._gen += 1
-
-    def _switch(self, plan):
-        """Make `plan` current: whether a row's next step is a first one is re-read from the state, the buffer pointers
-        are re-read when load_state_dict() replaced the state tensors."""
-        if self._plan is not plan:
-            counts = {}
-            for (p, _), r in zip(plan['active'], plan['row_of']):
-                c = 1.0 if not plan['momentum'] or self._stepped(p) else 0.0
-                if counts.setdefault(r, c) != c:
-                    raise lib.BmnasError('bmnas.optim.SGD: parameters that shared their first-step status when this plan '
-                                         'was built have diverged (an eager step on a subset?); re-capture the graph')
-            for r, c in counts.items():
-                plan['count'][r] = c
-            self._plan = plan
-        if not plan.get('poke'):
-            self.wait_staging()              # the plan's last launch has consumed its pinned buffer
-        if plan['gen'] != self._gen:
-            self._state_ptrs(plan)
-            plan['gen'] = self._gen
+        self._pending = {}           # (a checkpoint from before the first step holds no buffers)
+        self._state_replaced()
 
     def prepare_replay(self, slot=0):
         """Publish the current learning rates, momenta, dampenings and weight decays for the next step or replay, and
         count it: a row whose tensors have not stepped gets torch's first-step rule (mu = 0, damp1 = 1 over the zero
         buffer), and their buffers enter `state` — the step staged here writes them.  slot: as for Adam."""
+        self._begin_replay(slot, "'momentum' was switched between zero and non-zero, or 'nesterov' was switched,")
         pl = self._plan
         h = pl['hyps'][slot]
-        c = self._clip_value()
-        if (c is not None) != pl['clip']:
-            raise lib.BmnasError('bmnas.optim.SGD: max_grad_norm was switched between None and a value under a plan built '
-                                 'for the other (a captured step holds the launches of one of them); re-capture the graph')
-        if self._switches() != pl['key'][1:]:
-            raise lib.BmnasError("bmnas.optim.SGD: 'momentum' was switched between zero and non-zero, or 'nesterov' was "
-                                 'switched, under a plan built for the other value (a captured step holds the launches of '
-                                 'one of them); re-capture the graph')
-        if c is not None:
-            pl['clips'][slot][0] = c
         for r, gi in enumerate(pl['groups']):
             g = self.param_groups[gi]
             mu = float(g['momentum'])
@@ -736,15 +700,13 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     key = (dev, float(max_norm), tuple((g.data_ptr(), g.numel()) for g in grads))
     ent = _CLIP_CACHE.get('last')
     if ent is None or ent['key'] != key:
-        E = lib.adam_chunk_elems()
         tab = np.zeros(len(grads), dtype=_DESC)
         tab['grad'] = [g.data_ptr() for g in grads]
         tab['numel'] = [g.numel() for g in grads]
-        chunks = [(i, c) for i, g in enumerate(grads) for c in range((g.numel() + E - 1) // E)]
+        chunks, n_chunks = _chunk_list(tab['numel'].tolist(), dev)
         host = np.concatenate([np.array([max_norm, 0, 0, 0], dtype=np.float32).view(np.uint8), tab.view(np.uint8)])
         buf = torch.from_numpy(host).to(dev)
-        ent = dict(key=key, buf=buf, clip=buf[:4], tab=buf[16:],
-                   chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev), n_chunks=len(chunks),
+        ent = dict(key=key, buf=buf, clip=buf[:4], tab=buf[16:], chunks=chunks, n_chunks=n_chunks,
                    partials=torch.empty(lib.grad_norm_parts(), dtype=torch.float32, device=dev))
         _CLIP_CACHE['last'] = ent
     norm = torch.empty(1, dtype=torch.float32, device=dev)
@@ -840,9 +802,8 @@ class UnrolledStep:
         """active: [(p, group index, has momentum_buffer)] of this step.  One pinned buffer and its device copy:
         scalar rows | r, eta | weight table | alpha table."""
         dev = active[0][0].device
-        E = lib.adam_chunk_elems()
-        rows, row_idx, row_of, chunks = [], {}, [], []
-        for i, (p, gi, has) in enumerate(active):
+        rows, row_idx, row_of = [], {}, []
+        for p, gi, has in active:
             if not p.is_cuda:
                 raise lib.BmnasError('bmnas.optim.UnrolledStep needs parameters on the GPU (HIP kernel, no CPU path)')
             if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
@@ -853,7 +814,6 @@ class UnrolledStep:
                 row_idx[(gi, has)] = len(rows)
                 rows.append((gi, has))
             row_of.append(row_idx[(gi, has)])
-            chunks += [(i, c) for c in range((p.numel() + E - 1) // E)]
         for a in self.arch:
             if a.device != dev or a.dtype != torch.float32:
                 raise lib.BmnasError(f'bmnas.optim.UnrolledStep: architecture tensors must be fp32 on {dev}')
@@ -870,6 +830,7 @@ class UnrolledStep:
         wtab['numel'] = [p.numel() for p, _, _ in active]
         wtab['hyp_row'] = row_of
         parts = lib.grad_norm_parts()
+        chunks, n_chunks = _chunk_list([p.numel() for p, _, _ in active], dev)
         self._plan = dict(
             key=key, active=active, rows=rows, pin=pin, host=host, dev=devbuf, sent=None, event=None,
             hyp=host[:row_bytes].view(np.float32).reshape(len(rows), 8),
@@ -877,9 +838,8 @@ class UnrolledStep:
             wtab=wtab, atab=host[hyp_bytes + wtab_bytes:].view(_DESC),
             dev_hyp=devbuf[:hyp_bytes], dev_r=devbuf[row_bytes:row_bytes + 4], dev_eta=devbuf[row_bytes + 4:row_bytes + 8],
             dev_wtab=devbuf[hyp_bytes:hyp_bytes + wtab_bytes], dev_atab=devbuf[hyp_bytes + wtab_bytes:],
-            chunks=torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev), n_chunks=len(chunks),
-            n_parts=min(len(chunks), parts), partials=torch.empty(parts, dtype=torch.float32, device=dev),
-            R=torch.zeros(1, dtype=torch.float32, device=dev),
+            chunks=chunks, n_chunks=n_chunks, n_parts=min(n_chunks, parts),
+            partials=torch.empty(parts, dtype=torch.float32, device=dev), R=torch.zeros(1, dtype=torch.float32, device=dev),
             flags=lib.UNROLL_MOMENTUM if any(has for _, _, has in active) else 0, achunks={})
 
     def _wait(self):
@@ -1013,9 +973,7 @@ class UnrolledStep:
             return out
         ck = tuple(idx)
         if ck not in pl['achunks']:
-            E = lib.adam_chunk_elems()
-            ch = [(j, c) for j, i in enumerate(idx) for c in range((self.arch[i].numel() + E - 1) // E)]
-            pl['achunks'][ck] = (torch.tensor(ch, dtype=torch.int32).reshape(-1, 2).to(pl['dev'].device), len(ch))
+            pl['achunks'][ck] = _chunk_list([self.arch[i].numel() for i in idx], pl['dev'].device)
         chunks, n = pl['achunks'][ck]
         self._wait()
         tab = pl['atab']

@@ -30,25 +30,15 @@
 //   g   = nesterov ? g + mu_n * buf : buf
 //   p   = p + neg_lr * g
 // HBM-streaming: 2 reads + 1 write per element = 12 B/param; with momentum 3 reads + 2 writes = 20 B/param.
-#include "common.hpp"
+#include "multi_tensor.hpp"
 #include <cstring>
 #include "../../include/bmnas_hip.h"
 
 namespace {
 
-constexpr int kChunk = 1024;      // elements per workgroup (256 lanes x float4)
-
 struct Hyp {
   float neg_step, bc2_sqrt, beta2, eps, wd, w1, w2;
 };
-
-// a * b rounded on its own: the product carries no permission to contract, so the compiler cannot fold it into a
-// neighbouring addition as a fused multiply-add (__fmul_rn is a plain `*` to this compiler, and p * f + s * q became
-// fma(f, p, s * q): with f == 1 that is p + round(s * q), not the fma(s, q, p) of the undecayed step)
-__device__ __forceinline__ float mul_alone(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 // DECOUPLED: h.wd holds f = float(1 - lr * weight_decay) and the decay is a product of its own on the parameter
 // (mul_alone: never contracted into the update's multiply-add, so that f == 1 leaves the bits of the undecayed step); the
@@ -87,13 +77,11 @@ __device__ __forceinline__ void adam_chunk(const bmnas_adam_tensor_t* __restrict
   Hyp h;
   h.neg_step = hr[0]; h.bc2_sqrt = hr[1]; h.beta2 = hr[3]; h.eps = hr[4]; h.wd = hr[5];
   h.w1 = hr[6]; h.w2 = hr[7];
-  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
   float* mx = nullptr;
   if constexpr (AMSGRAD) mx = max_exp_avg_sq[ti];
   uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
   if constexpr (AMSGRAD) al |= (uintptr_t)mx;
-  if ((al & 15) == 0 && e + 4 <= t.numel) {
+  walk_chunk(t.numel, ci, al, [&](int64_t e) {
     float4 p = ld4(t.param + e), m = ld4(t.exp_avg + e), v = ld4(t.exp_avg_sq + e);
     float4 g = ld4(t.grad + e);
     float4 vm = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -107,21 +95,18 @@ __device__ __forceinline__ void adam_chunk(const bmnas_adam_tensor_t* __restrict
     st4_wtg<5>(t.exp_avg + e, m);
     st4_wtg<5>(t.exp_avg_sq + e, v);
     if constexpr (AMSGRAD) st4_wtg<5>(mx + e, vm);
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) {
-      float p = t.param[i], m = t.exp_avg[i], v = t.exp_avg_sq[i];
-      float g = t.grad[i];
-      float vm = 0.f;
-      if constexpr (AMSGRAD) vm = mx[i];
-      if constexpr (CLIP) g = __fmul_rn(g, c);
-      adam1<DECOUPLED, AMSGRAD>(p, g, m, v, vm, h);
-      t.param[i] = p;
-      t.exp_avg[i] = m;
-      t.exp_avg_sq[i] = v;
-      if constexpr (AMSGRAD) mx[i] = vm;
-    }
-  }
+  }, [&](int64_t i) {
+    float p = t.param[i], m = t.exp_avg[i], v = t.exp_avg_sq[i];
+    float g = t.grad[i];
+    float vm = 0.f;
+    if constexpr (AMSGRAD) vm = mx[i];
+    if constexpr (CLIP) g = __fmul_rn(g, c);
+    adam1<DECOUPLED, AMSGRAD>(p, g, m, v, vm, h);
+    t.param[i] = p;
+    t.exp_avg[i] = m;
+    t.exp_avg_sq[i] = v;
+    if constexpr (AMSGRAD) mx[i] = vm;
+  });
 }
 
 __global__ __launch_bounds__(256) void adam_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
@@ -134,8 +119,6 @@ __global__ __launch_bounds__(256) void adam_multi_k(const bmnas_adam_tensor_t* _
 // Two launches, no atomics, no zero-fill: grad_sqnorm_multi_k leaves one partial sum of squares per workgroup of a FIXED
 // grid; every workgroup of the consumer adds the partials in one fixed order, so all of them — and every run, and every
 // data-parallel replica — derive the same bits.
-constexpr int kNormParts = 256;   // partials = lanes of the consumer's one block_sum256
-
 __global__ __launch_bounds__(256) void grad_sqnorm_multi_k(const bmnas_adam_tensor_t* __restrict__ tensors,
                                                            const int32_t* __restrict__ chunks, int n_chunks,
                                                            float* __restrict__ partials) {
@@ -143,29 +126,23 @@ __global__ __launch_bounds__(256) void grad_sqnorm_multi_k(const bmnas_adam_tens
   float acc = 0.f;
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {        // chunks w, w + G, w + 2G, ... in that order
     const bmnas_adam_tensor_t t = tensors[chunks[2 * c]];
-    const int64_t e = (int64_t)chunks[2 * c + 1] * kChunk + threadIdx.x * 4;
-    if (e >= t.numel) continue;
-    if (((uintptr_t)t.grad & 15) == 0 && e + 4 <= t.numel) {
+    walk_chunk(t.numel, chunks[2 * c + 1], (uintptr_t)t.grad, [&](int64_t e) {
       const float4 g = ld4(t.grad + e);
       acc += g.x * g.x;
       acc += g.y * g.y;
       acc += g.z * g.z;
       acc += g.w * g.w;
-    } else {
-      const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-      for (int64_t i = e; i < end; ++i) acc += t.grad[i] * t.grad[i];
-    }
+    }, [&](int64_t i) { acc += t.grad[i] * t.grad[i]; });
   }
   const float total = block_sum256(acc, red);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
-// sqrt(sum of the partials) and torch's coefficient: max_norm / (norm + 1e-6) clamped to <= 1 by a compare and select
+// The norm and torch's coefficient: max_norm / (norm + 1e-6) clamped to <= 1 by a compare and select
 // (a NaN norm gives a NaN coefficient, as torch.clamp does; fminf would give 1).  Every thread of the block gets both.
 __device__ __forceinline__ float clip_coef(const float* __restrict__ partials, int n_parts,
                                            const float* __restrict__ clip, float* red, float& norm) {
-  const float v = ((int)threadIdx.x < n_parts) ? partials[threadIdx.x] : 0.f;
-  norm = sqrtf(block_sum256(v, red));
+  norm = norm_from_partials(partials, n_parts, red);
   const float c = clip[0] / (norm + 1e-6f);
   return (c > 1.f) ? 1.f : c;
 }
@@ -211,15 +188,10 @@ __global__ __launch_bounds__(256) void grad_scale_multi_k(const bmnas_adam_tenso
   if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
   const bmnas_adam_tensor_t t = tensors[chunks[2 * blockIdx.x]];
   float* __restrict__ grad = const_cast<float*>(t.grad);
-  const int64_t e = (int64_t)chunks[2 * blockIdx.x + 1] * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
-  if (((uintptr_t)grad & 15) == 0 && e + 4 <= t.numel) {
+  walk_chunk(t.numel, chunks[2 * blockIdx.x + 1], (uintptr_t)grad, [&](int64_t e) {
     const float4 g = ld4(grad + e);
     st4_wtg<5>(grad + e, make_float4(__fmul_rn(g.x, c), __fmul_rn(g.y, c), __fmul_rn(g.z, c), __fmul_rn(g.w, c)));
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) grad[i] = __fmul_rn(grad[i], c);
-  }
+  }, [&](int64_t i) { grad[i] = __fmul_rn(grad[i], c); });
 }
 
 // ---- multi-tensor SGD (torch.optim.SGD) ---------------------------------------------------------------------------
@@ -253,11 +225,9 @@ __device__ __forceinline__ void sgd_chunk(const bmnas_adam_tensor_t* __restrict_
   const float* hr = hyp + 8 * t.hyp_row;
   SgdHyp h;
   h.neg_lr = hr[0]; h.mu = hr[1]; h.damp1 = hr[2]; h.mu_n = hr[3]; h.wd = hr[4];
-  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
   uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad;
   if constexpr (MOMENTUM) al |= (uintptr_t)t.exp_avg;
-  if ((al & 15) == 0 && e + 4 <= t.numel) {
+  walk_chunk(t.numel, ci, al, [&](int64_t e) {
     float4 p = ld4(t.param + e);
     float4 g = ld4(t.grad + e);
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -269,17 +239,14 @@ __device__ __forceinline__ void sgd_chunk(const bmnas_adam_tensor_t* __restrict_
     sgd1<MOMENTUM, NESTEROV>(p.w, g.w, b.w, h);
     st4_wtg<5>(t.param + e, p);
     if constexpr (MOMENTUM) st4_wtg<5>(t.exp_avg + e, b);
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) {
-      float p = t.param[i], g = t.grad[i], b = 0.f;
-      if constexpr (MOMENTUM) b = t.exp_avg[i];
-      if constexpr (CLIP) g = mul_alone(g, c);
-      sgd1<MOMENTUM, NESTEROV>(p, g, b, h);
-      t.param[i] = p;
-      if constexpr (MOMENTUM) t.exp_avg[i] = b;
-    }
-  }
+  }, [&](int64_t i) {
+    float p = t.param[i], g = t.grad[i], b = 0.f;
+    if constexpr (MOMENTUM) b = t.exp_avg[i];
+    if constexpr (CLIP) g = mul_alone(g, c);
+    sgd1<MOMENTUM, NESTEROV>(p, g, b, h);
+    t.param[i] = p;
+    if constexpr (MOMENTUM) t.exp_avg[i] = b;
+  });
 }
 
 // One instantiation per launch: all tensors of an optimizer agree on the switches.
@@ -316,7 +283,7 @@ extern "C" int bmnas_grad_norm_parts(void) { return kNormParts; }
 extern "C" int bmnas_grad_sqnorm_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
                                        float* partials, void* stream) {
   if (!tensors || !chunks || !partials || n_chunks <= 0) return BMNAS_E_ARG;
-  const int g = n_chunks < kNormParts ? n_chunks : kNormParts;
+  const int g = norm_parts(n_chunks);
   hipLaunchKernelGGL(grad_sqnorm_multi_k, dim3(g), dim3(256), 0, (hipStream_t)stream, tensors, chunks, n_chunks,
                      partials);
   BMNAS_CHECK_LAUNCH();
@@ -329,7 +296,7 @@ extern "C" int bmnas_adam_multi_clip(const bmnas_adam_tensor_t* tensors, const i
                                      const float* hyp, const float* partials, int n_parts, const float* clip,
                                      float* norm_out, void* stream) {
   if (!tensors || !chunks || !hyp || !partials || !clip || !norm_out || n_chunks <= 0) return BMNAS_E_ARG;
-  if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;   // what the norm launch wrote
+  if (n_parts != norm_parts(n_chunks)) return BMNAS_E_ARG;   // what the norm launch wrote
   hipLaunchKernelGGL(adam_multi_clip_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, hyp,
                      partials, n_parts, clip, norm_out);
   BMNAS_CHECK_LAUNCH();
@@ -349,7 +316,7 @@ extern "C" int bmnas_adam_multi_ex(const bmnas_adam_tensor_t* tensors, const int
                    : bmnas_adam_multi(tensors, chunks, n_chunks, hyp, stream);
   }
   if (!tensors || !chunks || !hyp || n_chunks < 0) return BMNAS_E_ARG;
-  if (clipped && (n_chunks == 0 || n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts))) return BMNAS_E_ARG;
+  if (clipped && (n_chunks == 0 || n_parts != norm_parts(n_chunks))) return BMNAS_E_ARG;
   if (n_chunks == 0) return 0;
 #define BMNAS_ADAM_EX(C, D, A)                                                                                       \
   hipLaunchKernelGGL((adam_multi_ex_k<C, D, A>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, \
@@ -371,7 +338,7 @@ extern "C" int bmnas_grad_scale_multi(const bmnas_adam_tensor_t* tensors, const 
                                       const float* partials, int n_parts, const float* clip, float* norm_out,
                                       void* stream) {
   if (!tensors || !chunks || !partials || !clip || !norm_out || n_chunks <= 0) return BMNAS_E_ARG;
-  if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;
+  if (n_parts != norm_parts(n_chunks)) return BMNAS_E_ARG;
   hipLaunchKernelGGL(grad_scale_multi_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, partials,
                      n_parts, clip, norm_out);
   BMNAS_CHECK_LAUNCH();
@@ -387,7 +354,7 @@ extern "C" int bmnas_sgd_multi(const bmnas_adam_tensor_t* tensors, const int32_t
   const bool clipped = partials != nullptr;
   if ((clip != nullptr) != clipped || (norm_out != nullptr) != clipped) return BMNAS_E_ARG;
   if (!tensors || !chunks || !hyp || n_chunks < 0) return BMNAS_E_ARG;
-  if (clipped && (n_chunks == 0 || n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts))) return BMNAS_E_ARG;
+  if (clipped && (n_chunks == 0 || n_parts != norm_parts(n_chunks))) return BMNAS_E_ARG;
   if (n_chunks == 0) return 0;
 #define BMNAS_SGD(C, M, N)                                                                                        \
   hipLaunchKernelGGL((sgd_multi_k<C, M, N>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, \

@@ -13,18 +13,10 @@
 //   restore        p = bak
 //   combine        ig = (gp - gn) / (2 * R);  da = da - eta * ig   ((x - y).div_(2R), g.sub_(eta, ig))
 // HBM-streaming: virtual step 2 reads + 2 writes = 16 B/param (20 B with momentum), perturb 12 B, restore 8 B.
-#include "common.hpp"
+#include "multi_tensor.hpp"
 #include "../../include/bmnas_hip.h"
 
 namespace {
-
-constexpr int kChunk = 1024;      // elements per workgroup (256 lanes x float4): bmnas_adam_chunk_elems()
-constexpr int kNormParts = 256;   // bmnas_grad_norm_parts(): partials = lanes of one block_sum256
-
-__device__ __forceinline__ float mul_alone(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 struct VirtHyp {
   float neg_eta, mu, wd;
@@ -55,8 +47,6 @@ __global__ __launch_bounds__(256) void unroll_virtual_k(const bmnas_adam_tensor_
   const float* hr = hyp + 8 * t.hyp_row;
   VirtHyp h;
   h.neg_eta = hr[0]; h.mu = hr[1]; h.wd = hr[2];
-  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
   float* __restrict__ bak = t.exp_avg_sq;
   uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)bak;
   bool mom = false;
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(256) void unroll_virtual_k(const bmnas_adam_tensor_
     mom = t.exp_avg != nullptr;
     al |= (uintptr_t)t.exp_avg;
   }
-  if ((al & 15) == 0 && e + 4 <= t.numel) {
+  walk_chunk(t.numel, ci, al, [&](int64_t e) {
     const float4 p = ld4(t.param + e);
     const float4 g = ld4(t.grad + e);
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -78,41 +68,32 @@ __global__ __launch_bounds__(256) void unroll_virtual_k(const bmnas_adam_tensor_
     q.w = virt1<MOMENTUM>(p.w, g.w, b.w, mom, h);
     st4_wtg<5>(bak + e, p);
     st4_wtg<5>(t.param + e, q);
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) {
-      const float p = t.param[i], g = t.grad[i];
-      float b = 0.f;
-      if constexpr (MOMENTUM) {
-        if (mom) b = t.exp_avg[i];
-      }
-      bak[i] = p;
-      t.param[i] = virt1<MOMENTUM>(p, g, b, mom, h);
+  }, [&](int64_t i) {
+    const float p = t.param[i], g = t.grad[i];
+    float b = 0.f;
+    if constexpr (MOMENTUM) {
+      if (mom) b = t.exp_avg[i];
     }
-  }
+    bak[i] = p;
+    t.param[i] = virt1<MOMENTUM>(p, g, b, mom, h);
+  });
 }
 
-// sqrt(sum of the partials) in adam.hip's clip_coef order (lane i holds partial i, one block_sum256): every workgroup,
-// every run derives the same bits.  R = r / norm, no epsilon: a zero ||v|| gives inf, and inf * 0 = NaN in the
-// parameters, as DARTS' `R = r / _concat(vector).norm()` does.
+// The norm is the one adam.hip's clip_coef takes (norm_from_partials).  R = r / norm, no epsilon: a zero ||v|| gives
+// inf, and inf * 0 = NaN in the parameters, as DARTS' `R = r / _concat(vector).norm()` does.
 __global__ __launch_bounds__(256) void unroll_perturb_k(const bmnas_adam_tensor_t* __restrict__ tensors,
                                                         const int32_t* __restrict__ chunks,
                                                         const float* __restrict__ partials, int n_parts,
                                                         const float* __restrict__ r, float sign,
                                                         float* __restrict__ R_out) {
   __shared__ float red[4];
-  const float part = ((int)threadIdx.x < n_parts) ? partials[threadIdx.x] : 0.f;
-  const float norm = sqrtf(block_sum256(part, red));
-  const float R = r[0] / norm;
+  const float R = r[0] / norm_from_partials(partials, n_parts, red);
   if (blockIdx.x == 0 && threadIdx.x == 0) R_out[0] = R;
   const float s = mul_alone(sign, R);
   const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
   const bmnas_adam_tensor_t t = tensors[ti];
-  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
   const float* __restrict__ bak = t.exp_avg_sq;
-  const uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)bak;
-  if ((al & 15) == 0 && e + 4 <= t.numel) {
+  walk_chunk(t.numel, ci, (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)bak, [&](int64_t e) {
     const float4 b = ld4(bak + e);
     const float4 v = ld4(t.grad + e);
     float4 q;
@@ -121,10 +102,7 @@ __global__ __launch_bounds__(256) void unroll_perturb_k(const bmnas_adam_tensor_
     q.z = b.z + mul_alone(s, v.z);
     q.w = b.w + mul_alone(s, v.w);
     st4_wtg<5>(t.param + e, q);
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) t.param[i] = bak[i] + mul_alone(s, t.grad[i]);
-  }
+  }, [&](int64_t i) { t.param[i] = bak[i] + mul_alone(s, t.grad[i]); });
 }
 
 // p = bak.  `grad` is not read: a NaN in v cannot leak into w.
@@ -132,15 +110,9 @@ __global__ __launch_bounds__(256) void unroll_restore_k(const bmnas_adam_tensor_
                                                         const int32_t* __restrict__ chunks) {
   const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
   const bmnas_adam_tensor_t t = tensors[ti];
-  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
   const float* __restrict__ bak = t.exp_avg_sq;
-  if ((((uintptr_t)t.param | (uintptr_t)bak) & 15) == 0 && e + 4 <= t.numel) {
-    st4_wtg<5>(t.param + e, ld4(bak + e));
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) t.param[i] = bak[i];
-  }
+  walk_chunk(t.numel, ci, (uintptr_t)t.param | (uintptr_t)bak,
+             [&](int64_t e) { st4_wtg<5>(t.param + e, ld4(bak + e)); }, [&](int64_t i) { t.param[i] = bak[i]; });
 }
 
 __device__ __forceinline__ float comb1(float da, float gp, float gn, float two_R, float eta) {
@@ -158,11 +130,8 @@ __global__ __launch_bounds__(256) void unroll_combine_k(const bmnas_adam_tensor_
   const bmnas_adam_tensor_t t = tensors[ti];
   const float eta = hyp[0];
   const float two_R = mul_alone(2.f, R[0]);
-  const int64_t e = (int64_t)ci * kChunk + threadIdx.x * 4;
-  if (e >= t.numel) return;
   const float* __restrict__ gn = t.exp_avg;
-  const uintptr_t al = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)gn;
-  if ((al & 15) == 0 && e + 4 <= t.numel) {
+  walk_chunk(t.numel, ci, (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)gn, [&](int64_t e) {
     const float4 a = ld4(t.param + e), p = ld4(t.grad + e), n = ld4(gn + e);
     float4 q;
     q.x = comb1(a.x, p.x, n.x, two_R, eta);
@@ -170,10 +139,7 @@ __global__ __launch_bounds__(256) void unroll_combine_k(const bmnas_adam_tensor_
     q.z = comb1(a.z, p.z, n.z, two_R, eta);
     q.w = comb1(a.w, p.w, n.w, two_R, eta);
     st4_wtg<5>(t.param + e, q);
-  } else {
-    const int64_t end = (e + 4 < t.numel) ? e + 4 : t.numel;
-    for (int64_t i = e; i < end; ++i) t.param[i] = comb1(t.param[i], t.grad[i], gn[i], two_R, eta);
-  }
+  }, [&](int64_t i) { t.param[i] = comb1(t.param[i], t.grad[i], gn[i], two_R, eta); });
 }
 
 }  // namespace
@@ -196,7 +162,7 @@ extern "C" int bmnas_unroll_perturb(const bmnas_adam_tensor_t* tensors, const in
                                     void* stream) {
   if (!tensors || !chunks || !partials || !r || !R_out || n_chunks <= 0) return BMNAS_E_ARG;   // (a norm is needed)
   if (!(sign == 1.f || sign == -1.f)) return BMNAS_E_ARG;
-  if (n_parts != (n_chunks < kNormParts ? n_chunks : kNormParts)) return BMNAS_E_ARG;           // what the norm launch wrote
+  if (n_parts != norm_parts(n_chunks)) return BMNAS_E_ARG;           // what the norm launch wrote
   hipLaunchKernelGGL(unroll_perturb_k, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, partials,
                      n_parts, r, sign, R_out);
   BMNAS_CHECK_LAUNCH();

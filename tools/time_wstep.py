@@ -28,7 +28,7 @@ def build(variant):
     xs, y = B.synth_batch(c, batch, dev, 0)
     opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)
     if variant == 'nocopy':
-        opt._launch = lambda: __import__('bmnas').lib.adam_multi(opt._plan['dev_tab'], opt._plan['chunks'],
+        opt._launch = lambda: __import__('bmnas').lib.adam_multi(opt._plan['dev_tabs'][0], opt._plan['chunks'],
                                                                  opt._plan['n_chunks'], opt._plan['dev_hyp'])
     elif variant == 'nostep':
         opt._launch = lambda: None
