@@ -1320,6 +1320,7 @@ extern "C" int bmnas_node_mix_fwd_next(const float* x, const float* y, const flo
   BnFin f;
   if (int e = to_fin(fin, &f)) return e;
   if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+  if (C > 4096 / 3 || (3 * C) % 4) return BMNAS_E_LIMIT;   // bn_fin_fill: four channels per thread, scale | shift in LDS
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * C * L / 4;
 #define NMF(NPv)                                                                                          \
@@ -1356,6 +1357,7 @@ extern "C" int bmnas_node_mix_ln_fwd(const float* x, const float* y, const float
   BnFin f;
   if (int e = to_fin(fin, &f)) return e;
   if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+  if (C > 4096 / 3 || (3 * C) % 4) return BMNAS_E_LIMIT;   // bn_fin_fill, as bmnas_node_mix_fwd_next
   if (b == 0) return 0;
   const size_t fin_lds = (size_t)6 * C * sizeof(float);
   const bool wide = b <= 256 && C * L / 4 >= 512;   // fewer samples than CUs: 8 waves per sample

@@ -464,6 +464,7 @@ extern "C" int bmnas_node_mix_pre_fwd(const float* x, const float* y, const floa
   BnFin f;
   if (int e = to_fin(fin, &f)) return e;
   if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+  if (C > 4096 / 3 || (3 * C) % 4) return BMNAS_E_LIMIT;   // bn_fin_fill, as bmnas_node_mix_fwd_next
   if (b == 0) return 0;
   const int P = lazy_parts(C * L / 4);
   hipLaunchKernelGGL(node_mix_pre_fwd_k, dim3(P, b), dim3(256), (size_t)6 * C * sizeof(float), (hipStream_t)stream,

@@ -311,7 +311,11 @@ typedef struct {
  * NodeMixedOp.forward node_operations.py:118-120 over [Sum, ScaleDotAttn, LinearGLU, ConcatFC]:
  *   s = g0*(x+y) + g1*p1 + g2*drop(glu(BN(U[:, 0:2C]))) + g3*drop(relu(BN(U[:, 2C:3C])))
  * gamma: 4 device floats (softmaxed row).  U: (b, 3C, L) stacked conv output [GLU | ConcatFC],
- * chan: its bn_finalize output (M = 3C).  p1 = attention branch output. */
+ * chan: its bn_finalize output (M = 3C).  p1 = attention branch output.
+ * Limits of the forward entries (bmnas_node_mix_fwd / _fwd_next / _ln_fwd / _pre_fwd; BMNAS_E_LIMIT outside them, after
+ * BMNAS_E_ARG and BMNAS_E_SHAPE): (3 C) % 4 == 0 and 3 C <= 4096 — the in-kernel finalisation gives a thread four
+ * adjacent channels and keeps scale | shift of every conv row in LDS, as bmnas_node_mix_sel_ok states.  The backward
+ * entries read `chan` per channel and take any C. */
 int bmnas_node_mix_fwd(const float* x, const float* y, const float* p1, const float* U, float* chan,
                        bmnas_bn_fin_t fin, const float* gamma, float* out, int b, int C, int L,
                        bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream);
