@@ -166,8 +166,15 @@ class GraphedTrainStep:
                     pass
         return n
 
-    def __init__(self, model, criterion, optimizer, inputs, labels, warmup=2, metric_forward=False, k=1):
-        """k: optimisation steps per replay.  k > 1 captures k CONSECUTIVE steps — each over a static batch of its own,
+    def __init__(self, model, criterion, optimizer, inputs, labels, warmup=2, metric_forward=False, k=1, averaged=None):
+        """averaged: a bmnas.optim.AveragedModel of `model`; its update (`averaged.update_parameters(model)`, one
+        bmnas_avg_multi launch) then follows `optimizer.step()` INSIDE the graph, for each of the k steps.  Its scalar row
+        of a replay, 32 bytes per step, rides behind the optimizer's rows (capture_safe(extra=...)): by value in the
+        batch-copy launch's blob, or through the copy-node fallback when the rows no longer fit it.  Needs the update
+        inside the graph (`in_graph_step`) — without it the argument is dropped, `self.averaged` is None and the caller
+        updates the averager after the host-side step —; an eager step in between (a ragged batch) calls
+        update_parameters itself.
+        k: optimisation steps per replay.  k > 1 captures k CONSECUTIVE steps — each over a static batch of its own,
         each with its own Adam scalars (learning rate, bias corrections: `stage(i, inputs, labels)` per batch, then
         `replay_staged()`) — into one graph: what separates two replays (~4 us of launch gap and ~30 us of host work)
         is then paid once per k batches.  The reference's loop takes its batches one by one
@@ -217,6 +224,9 @@ class GraphedTrainStep:
             raise RuntimeError('metric_forward needs the optimizer step inside the captured graph')
         if self.k > 1 and not self.in_graph_step:
             raise RuntimeError('k steps per replay need the optimizer step inside the captured graph')
+        if averaged is not None and not self.in_graph_step:
+            averaged = None          # the host issues the optimizer step: the caller updates the averager after it
+        self.averaged = averaged     # (None: this step does not update it)
         views = reducer.ensure_bucket() if reducer is not None else None
         # with an averaging collective (RCCL) the captured step is the single-GPU one: unscaled loss, constant
         # unit gradient; otherwise (gloo) the loss is pre-scaled by 1/world and the bucket is summed
@@ -267,6 +277,8 @@ class GraphedTrainStep:
                 reducer.reduced = True                          # the step pre-hook must not reduce again
             if self.in_graph_step and armed[0]:
                 optimizer.step()
+                if averaged is not None:
+                    averaged.update_parameters(model)           # captured: one launch behind the optimizer's
             if self.native:
                 reducer.reduced = False
             if self.metric_forward:
@@ -310,7 +322,13 @@ class GraphedTrainStep:
         try:
             if self.in_graph_step:
                 # no H2D node in the graph: the scalars (of every one of the k steps) ride with the batch copy
-                optimizer.capture_safe(poke=True, slots=self.k)
+                if averaged is None:
+                    optimizer.capture_safe(poke=True, slots=self.k)
+                else:
+                    # the averager's rows ride behind the optimizer's: one blob (or one copy node) carries both
+                    extra = averaged.capture_rows(model, self.k)
+                    optimizer.capture_safe(poke=True, slots=self.k, extra=extra)
+                    averaged.capture_safe(model, *optimizer.rider_rows(), slots=self.k)
             armed[0] = True
             # the step's accumulation arena: cleared, like the dropout step counter advanced, by the launch that copies
             # the batch in front of every replay — no fill / add launches inside the step (bmnas.functions._StepArena)
@@ -321,12 +339,18 @@ class GraphedTrainStep:
             self._batch_in = _BatchIn(flat[:-1], flat[-1], zero=[self._arena], advance=self._g.external)
             # the graph reads THIS plan's staging buffers and writes THESE gradient tensors for good
             self.plan = optimizer.captured_plan() if self.in_graph_step else None
+            # ... and THIS plan's rider rows: the averager may ride in other captured steps too
+            self.avg_plan = averaged.captured_plan() if averaged is not None else None
             self.static_grads = [t.grad for t in self.targets]
+        except BaseException:
+            if averaged is not None:
+                averaged.abandon_capture()
+            raise
         finally:
             model.load_state_dict(state)        # also when the capture fails and the caller stays eager
 
     @staticmethod
-    def try_build(model, criterion, optimizer, inputs, labels, logger=None, metric_forward=False, k=1):
+    def try_build(model, criterion, optimizer, inputs, labels, logger=None, metric_forward=False, k=1, averaged=None):
         """-> a GraphedTrainStep, or False when this step cannot be captured (inputs that are not a
         flat list of tensors, a module that synchronises with the host, ...); callers then keep
         the eager path."""
@@ -335,7 +359,8 @@ class GraphedTrainStep:
             return False
         from .dist import all_ranks_agree
         try:
-            step = GraphedTrainStep(model, criterion, optimizer, inputs, labels, metric_forward=metric_forward, k=k)
+            step = GraphedTrainStep(model, criterion, optimizer, inputs, labels, metric_forward=metric_forward, k=k,
+                                    averaged=averaged)
         except Exception as e:                       # noqa: BLE001 — capture errors are of many types
             torch.cuda.synchronize()
             from . import functions
@@ -391,6 +416,8 @@ class GraphedTrainStep:
         if i != len(self._staged) // (len(self.inputs) + 1):
             raise RuntimeError('GraphedTrainStep.stage: batches must be staged in order, one call per slot')
         opt.prepare_replay(slot=i)
+        if self.averaged is not None:
+            self.averaged.prepare_replay(self.avg_plan, slot=i)
         self._staged += list(inputs) + [labels]
         # (decoded here, right after this slot's rows were written: `count` still is this step's)
         return opt.staged_lrs(slot=i)
@@ -416,6 +443,8 @@ class GraphedTrainStep:
         if self.in_graph_step:
             opt.activate(self.plan)          # an eager step in between must not leak into the replay
             opt.prepare_replay()
+            if self.averaged is not None:
+                self.averaged.prepare_replay(self.avg_plan)
             # ONE launch in front of the replay: the batch into the static tensors + this step's Adam scalars (by value)
             self._batch_in(inputs, labels, opt.replay_blob())
             out = self._g.replay()

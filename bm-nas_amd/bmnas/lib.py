@@ -256,6 +256,7 @@ SIGNATURES = {
     'bmnas_adam_multi_ex': ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_grad_scale_multi': ([_P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_sgd_multi': ([_P, _P, _I, _P, _I, _P, _I, _P, _P, _P], _I),
+    'bmnas_avg_multi': ([_P, _P, _I, _P, _P, _P], _I),
     'bmnas_unroll_virtual_step': ([_P, _P, _I, _P, _I, _P], _I),
     'bmnas_unroll_perturb': ([_P, _P, _I, _P, _I, _P, C.c_float, _P, _P], _I),
     'bmnas_unroll_restore': ([_P, _P, _I, _P], _I),
@@ -1171,6 +1172,20 @@ def sgd_multi(table, chunks, n_chunks, hyp, flags, partials=None, n_parts=0, cli
     Clips iff partials is given (then clip and norm_out too, as for adam_multi_clip).  `.grad` is NOT written."""
     _check(load().bmnas_sgd_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, hyp.data_ptr(), int(flags),
                                   _opt(partials), n_parts, _opt(clip), _opt(norm_out), _stream()), 'sgd_multi')
+
+
+AVG_RAW = 1                                  # BMNAS_AVG_RAW (include/bmnas_hip.h)
+
+
+def avg_multi(table, chunks, n_chunks, rows, n_averaged):
+    """torch's AveragedModel update of every tensor of `table` (bmnas_adam_tensor_t[]: param the AVERAGED tensor, grad the
+    LIVE one) in one launch.  rows: uint8 device tensor holding bmnas_avg_row_t[] (32 bytes: w, omw, flags, -, int64
+    count, -); a row flagged AVG_RAW copies 32-bit words (numel counts words).  n_averaged: int64 device tensor that
+    receives the count of the first tensor's row."""
+    if n_averaged.dtype != torch.int64 or not n_averaged.is_cuda:
+        raise BmnasError('avg_multi: n_averaged must be an int64 device tensor')
+    _check(load().bmnas_avg_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, rows.data_ptr(),
+                                  n_averaged.data_ptr(), _stream()), 'avg_multi')
 
 
 UNROLL_MOMENTUM = 1                          # BMNAS_UNROLL_* (include/bmnas_hip.h)

@@ -37,9 +37,15 @@ what keys a scalar row (`_row_count`) and what it holds (`prepare_replay`), whic
 unrolled architecture step — virtual weight step, +-R perturbation, restore, and the combine over alpha — on the kernels
 of csrc/unroll.hip, over the same descriptor table, chunk list and norm launch, reading a weight optimizer's groups and
 momentum buffers without writing them.
+
+`AveragedModel` (last) is torch.optim.swa_utils.AveragedModel — EMA / SWA of a model's tensors — with the update as one
+`bmnas_avg_multi` launch (csrc/average.hip) over the same descriptor table and chunk list, `param` the averaged tensor and
+`grad` the live one, and no host synchronisation; inside a captured step its scalar rows ride behind the optimizer's
+(`staging_layout(extra_bytes=...)`, `capture_safe(extra=...)`, `rider_rows()`).
 """
 import collections
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -53,16 +59,19 @@ assert _DESC.itemsize == 48
 
 
 StagingLayout = collections.namedtuple(
-    'StagingLayout', 'row_bytes hyp_slot hyp_bytes tab_bytes tab_slot nbytes rows_at clip_at tab_at tail_at')
+    'StagingLayout', 'row_bytes hyp_slot hyp_bytes tab_bytes tab_slot nbytes rows_at clip_at tab_at tail_at extra_at')
 
 
-def staging_layout(n_rows, n_tensors, slots=1, clip=False, tail_ptrs_per_tensor=0):
+def staging_layout(n_rows, n_tensors, slots=1, clip=False, tail_ptrs_per_tensor=0, extra_bytes=0):
     """The byte offsets of a plan's ONE staging buffer (pinned, and its device copy) — the one place that knows them; they
     are baked into captured graphs, into the poke-mode blob and into what the kernels read behind a descriptor table.
 
         scalar region   per slot: n_rows rows of 8 floats (32 bytes each), then — when clipping — max_grad_norm in 16
                         bytes of its own (the next slot's rows stay 16-byte aligned).  The slots are packed back to back:
-                        the whole region travels by value in poke mode.  Rounded up to 64 bytes (`hyp_bytes`).
+                        the whole region travels by value in poke mode.  Behind the last slot, `extra_bytes` (a multiple
+                        of 32; 0: nothing, every offset is what it is without) for a rider's rows — the scalar rows of
+                        a bmnas.optim.AveragedModel updated in the same captured step —, which so travel with the
+                        optimizer's.  Rounded up to 64 bytes (`hyp_bytes`).
         table region    per slot: n_tensors descriptors of 48 bytes (bmnas_adam_tensor_t) — the table is shared with the
                         norm launch and stays 48 bytes per tensor —, then 8 * tail_ptrs_per_tensor bytes per tensor
                         (AMSGrad: one `float*` per descriptor, max_exp_avg_sq), which so travel with the table's upload.
@@ -73,13 +82,16 @@ def staging_layout(n_rows, n_tensors, slots=1, clip=False, tail_ptrs_per_tensor=
     scalar (None without clipping), its table and its tail pointers start."""
     row_bytes = n_rows * 32
     hyp_slot = row_bytes + (16 if clip else 0)
-    hyp_bytes = (slots * hyp_slot + 63) // 64 * 64
+    if extra_bytes < 0 or extra_bytes % 32:
+        raise ValueError('staging_layout: extra_bytes must be a non-negative multiple of 32')
+    hyp_bytes = (slots * hyp_slot + extra_bytes + 63) // 64 * 64
     tab_bytes = n_tensors * _DESC.itemsize
     tab_slot = tab_bytes + n_tensors * 8 * tail_ptrs_per_tensor
     rows_at = [i * hyp_slot for i in range(slots)]
     tab_at = [hyp_bytes + i * tab_slot for i in range(slots)]
     return StagingLayout(row_bytes, hyp_slot, hyp_bytes, tab_bytes, tab_slot, hyp_bytes + slots * tab_slot, rows_at,
-                         [o + row_bytes for o in rows_at] if clip else None, tab_at, [o + tab_bytes for o in tab_at])
+                         [o + row_bytes for o in rows_at] if clip else None, tab_at, [o + tab_bytes for o in tab_at],
+                         slots * hyp_slot)
 
 
 def _chunk_list(numels, device):
@@ -143,9 +155,10 @@ class _OneLaunch:
     def _flush_counts(self):
         """Write the plan's row counts back into the optimizer's state, where the state keeps them (Adam's `step`)."""
 
-    def _build(self, active, slots=1):
+    def _build(self, active, slots=1, extra=0):
         """The plan of `slots` consecutive steps over `active`, in ONE staging buffer (staging_layout).  Tensors of one group
-        with the same `_row_count` share a row of scalars; `count` of a row is that count, advanced by prepare_replay()."""
+        with the same `_row_count` share a row of scalars; `count` of a row is that count, advanced by prepare_replay().
+        extra: bytes behind the scalar rows for a rider (capture_safe)."""
         key = self._variant()
         clip, sw = key[0], key[1:]
         self._flush_counts()
@@ -162,7 +175,7 @@ class _OneLaunch:
                 rows.append(rk)
             row_of.append(row_idx[rk])
         fields, tail = self._plan_fields(sw)
-        lay = staging_layout(len(rows), len(active), slots, clip, tail)
+        lay = staging_layout(len(rows), len(active), slots, clip, tail, extra)
         pin = torch.zeros(lay.nbytes, dtype=torch.uint8).pin_memory()
         host = pin.numpy()
         devbuf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=dev)
@@ -174,7 +187,11 @@ class _OneLaunch:
         chunks, n_chunks = _chunk_list([p.numel() for p, _ in active], dev)
         self._plan = dict(ids=tuple(id(p) for p, _ in active), active=active, row_of=row_of, gen=self._gen,
                           groups=[gi for gi, _ in rows], count=[c for _, c in rows],
-                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:slots * lay.hyp_slot], tabs=tabs,
+                          # hyp_all: what a replay carries by value — every slot's scalar rows and, behind them, a rider's
+                          # `extra` bytes (an AveragedModel's rows; none: the optimizer's rows alone, as ever)
+                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:lay.extra_at + extra], tabs=tabs,
+                          extra=host[lay.extra_at:lay.extra_at + extra],
+                          dev_extra=devbuf[lay.extra_at:lay.extra_at + extra],
                           dev=devbuf, dev_hyp=devbuf[:lay.hyp_bytes],
                           dev_hyps=[devbuf[o:o + lay.hyp_slot] for o in lay.rows_at],
                           dev_tabs=[devbuf[o:o + lay.tab_bytes] for o in lay.tab_at],
@@ -316,15 +333,18 @@ class _OneLaunch:
         return super().zero_grad(set_to_none)
 
     # ------------------------------------------------------------------ hipGraph support
-    def capture_safe(self, poke=False, slots=1):
+    def capture_safe(self, poke=False, slots=1, extra=0):
         """Build a plan OF ITS OWN from the gradients that exist NOW (static tensors of the step
         being captured) so that step() inside `torch.cuda.graph` issues only stream work: one
         pinned H2D copy and one launch.  The captured graph keeps reading this plan's staging
         buffers, so the plan is never reused for eager steps: take it with `captured_plan()` after
-        the capture and call `activate(plan)` + `prepare_replay()` before every replay."""
+        the capture and call `activate(plan)` + `prepare_replay()` before every replay.
+        extra: bytes (a multiple of 32) kept behind the scalar rows for a rider of the same captured step — the rows of a
+        bmnas.optim.AveragedModel (plan['extra'] on the host, plan['dev_extra'] on the device) —: they travel with the
+        optimizer's rows, by value in poke mode, else through the plan's copy node."""
         active = self._active()
         self.wait_staging()
-        self._build(active, slots)
+        self._build(active, slots, extra)
         self._write_ptrs(active)
         self._plan['captured'] = True
         # "poke" mode (round 5): the captured step holds NO H2D copy node.  The descriptor table is uploaded once after the
@@ -333,8 +353,13 @@ class _OneLaunch:
         # replay_blob()).  A captured copy node cost 4.7 us per optimizer step.
         self._plan['poke'] = bool(poke) and self._plan['hyp_all'].nbytes <= lib.copy_blob_max()
         if slots > 1 and not self._plan['poke']:
-            raise lib.BmnasError(f'{self._NAME}: {slots} captured steps x {len(self._plan["groups"])} scalar rows do not '
-                                 'fit the by-value blob of the batch-copy launch')
+            rider = f' and {extra} bytes of averaging rows' if extra else ''
+            raise lib.BmnasError(f'{self._NAME}: {slots} captured steps x {len(self._plan["groups"])} scalar rows{rider} '
+                                 'do not fit the by-value blob of the batch-copy launch')
+
+    def rider_rows(self):
+        """-> (host bytes, device bytes) of the current plan's `extra` region (capture_safe(extra=...))."""
+        return self._plan['extra'], self._plan['dev_extra']
 
     def captured_plan(self):
         """The plan a capture has just baked into a graph, with the pointer table as captured
@@ -986,3 +1011,312 @@ class UnrolledStep:
         self._upload()
         lib.unroll_combine(pl['dev_atab'], chunks, n, pl['dev_eta'], pl['R'])
         return out
+
+
+# bmnas_avg_row_t (include/bmnas_hip.h)
+_AVG_ROW = np.dtype([('w', '<f4'), ('omw', '<f4'), ('flags', '<u4'), ('reserved0', '<u4'), ('count', '<i8'),
+                     ('reserved1', '<i8')])
+assert _AVG_ROW.itemsize == 32
+
+
+def avg_weight(n, decay=None):
+    """The weight of the live tensors, in double, in the update that follows `n` completed ones: 1 for the first (torch's
+    copy), 1 - decay for an EMA, and for SWA the fp32 quotient 1 / (n + 1) as torch's get_swa_multi_avg_fn forms it."""
+    if n == 0:
+        return 1.0
+    if decay is None:
+        return float(np.float32(1.0) / np.float32(n + 1))
+    return 1.0 - float(decay)
+
+
+def avg_row(n, decay=None, raw=False):
+    """-> the bmnas_avg_row_t of that update, as a tuple for a numpy record: w, omw = 1 - w (formed in double, rounded
+    once), flags, 0, the new count n + 1, 0.  A RAW row carries the count and no weights."""
+    if raw:
+        return (0.0, 0.0, lib.AVG_RAW, 0, n + 1, 0)
+    w = avg_weight(n, decay)
+    return (np.float32(w), np.float32(1.0 - w), 0, 0, n + 1, 0)
+
+
+class AveragedModel(torch.optim.swa_utils.AveragedModel):
+    """torch.optim.swa_utils.AveragedModel with `update_parameters` as ONE `bmnas_avg_multi` launch over every tensor and
+    no host synchronisation: EMA of the weights (`decay` in [0, 1]: w = 1 - decay) or SWA (`decay=None`:
+    w = fp32(1 / (n + 1))).  Same structure (`self.module = deepcopy(model)`, buffer `n_averaged`) and the same
+    `state_dict()` keys as torch's class: checkpoints travel both ways.  `avg_fn` / `multi_avg_fn` are not taken.
+
+    torch's `bool(self.n_averaged == 0)` — a host synchronisation per update — is gone: the count is mirrored on the host
+    (re-read from the device ONCE after load_state_dict), the first update is the scalar row w = 1 (a copy for finite
+    values), and the launch stores the new count into `n_averaged`.  So the update can be captured in a hipGraph
+    (bmnas.graph.GraphedTrainStep(averaged=...)): its row rides with the optimizer's rows.
+
+    use_buffers=True averages floating buffers (BatchNorm running statistics) like parameters; False copies every buffer,
+    as torch does.  INTEGER buffers (num_batches_tracked) are always copied — the one difference from torch, whose EMA of
+    an int64 counter is a truncated n * decay + m * (1 - decay) that nothing reads.
+    skip_frozen=True: a parameter with requires_grad=False is copied by the first update and left out of later launches
+    (12 B per frozen parameter per step saved).  Exact as long as such tensors do not change between updates — frozen
+    backbones; NOT if they are loaded or edited after the first update.  Which parameters are frozen is read from
+    `requires_grad` at each eager update and when an update is captured: a tensor frozen LATER keeps the average it had, one
+    unfrozen later joins the launches with whatever its copy holds (a captured update never sees the change) — freeze
+    before the first update.  False (default) is torch's behaviour.
+    A model with non-fp32 floating tensors, tensors off the GPU or non-contiguous ones runs torch's parent class (after
+    lib.note_off_path), where integer buffers follow torch's rule."""
+
+    def __init__(self, model, device=None, decay=None, use_buffers=False, skip_frozen=False):
+        if decay is not None:
+            decay = float(decay)
+            if not 0.0 <= decay <= 1.0:
+                raise ValueError(f'bmnas.optim.AveragedModel: decay must be None (SWA) or in [0, 1], got {decay!r}')
+        multi = torch.optim.swa_utils.get_ema_multi_avg_fn(decay) if decay is not None else None
+        super().__init__(model, device=device, multi_avg_fn=multi, use_buffers=bool(use_buffers))
+        self.decay = decay
+        self.skip_frozen = bool(skip_frozen)
+        # torch leaves `n_averaged` on the CPU unless `device` is given; the launch stores the count, so the buffer lives
+        # where the averaged tensors do (same key, same dtype: checkpoints do not notice)
+        home = next((t.device for t in list(self.module.parameters()) + list(self.module.buffers()) if t.is_cuda), None)
+        if home is not None and self.n_averaged.device != home:
+            self.register_buffer('n_averaged', self.n_averaged.to(home))
+        # modules that keep tensors in shared storage re-point them lazily (node_operations' stacked convs): do it now —
+        # a captured update holds the addresses
+        for m in self.module.modules():
+            settle = getattr(m, 'settle_storage', None)
+            if callable(settle):
+                settle()
+        self._n = 0                  # host mirror of n_averaged; None: re-read it from the device (load_state_dict)
+        self._eager = {}             # (id(model), members) -> eager plan
+        self._checked = None         # (weak reference to a model, off_path(model)): decided once per model, not per update
+        self._capturing = None       # the plan whose updates are being captured (capture_safe() ... captured_plan())
+        self.captures = 0            # captured plans handed out so far
+        self.launches = 0            # bmnas_avg_multi calls issued from Python so far (a replayed update is none)
+
+    # ------------------------------------------------------------------ membership
+    def pairs(self, model):
+        """-> [(averaged tensor, live tensor, 'avg' | 'raw', frozen)] in torch's order (parameters, then buffers)."""
+        out = [(a, p, 'avg', not p.requires_grad) for a, p in zip(self.module.parameters(), model.parameters())]
+        for a, b in zip(self.module.buffers(), model.buffers()):
+            out.append((a, b, 'avg' if self.use_buffers and a.is_floating_point() else 'raw', False))
+        return out
+
+    def members(self, model, with_frozen):
+        """The (averaged, live, kind) triples of a launch: every tensor (with_frozen), or every tensor but the parameters
+        that are frozen NOW (`requires_grad` is read at each eager update and at capture_safe())."""
+        return [(a, p, k) for a, p, k, frozen in self.pairs(model) if with_frozen or not frozen]
+
+    def _main(self, model):
+        """The tensors of an update's one launch: all of them, or — skip_frozen — all but the frozen parameters."""
+        return self.members(model, with_frozen=not self.skip_frozen)
+
+    def off_path(self, model):
+        """Why this pair of models runs torch's parent class, or None."""
+        dev = None
+        if not self.n_averaged.is_cuda:
+            return 'tensors off the GPU'
+        for a, p, kind, _ in self.pairs(model):
+            for t in (a, p):
+                if not t.is_cuda:
+                    return 'tensors off the GPU'
+                dev = dev or t.device
+                if t.device != dev:
+                    return 'tensors on more than one device'
+                if not t.is_contiguous():
+                    return 'non-contiguous tensors'
+            if a.dtype != p.dtype or a.shape != p.shape:
+                return 'the models differ in a dtype or shape'
+            if kind == 'avg' and a.dtype != torch.float32:
+                return f'{a.dtype} tensors to average'
+            if kind == 'raw' and ((a.numel() * a.element_size()) % 4 or a.data_ptr() % 4 or p.data_ptr() % 4):
+                return f'a {a.dtype} buffer that is no whole number of aligned 32-bit words'
+        return None
+
+    def _count(self):
+        if self._n is None:
+            self._n = int(self.n_averaged)           # once after load_state_dict
+        return self._n
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self._n = None
+        return out
+
+    # ------------------------------------------------------------------ plans
+    def _build(self, trio, slots=1, rows=None, dev_rows=None):
+        """The plan of `slots` launches over `trio`: per slot a descriptor table (averaged tensors first, then RAW ones),
+        one chunk list, and the rows — slot s's row at index s and, when both kinds are present, ONE shared RAW row
+        behind them.  rows / dev_rows: where the rows live when they ride in an optimizer's staging buffer (host bytes
+        and their device copy); None: in this plan's own buffer, in front of the tables.  The chunk list lies behind the
+        tables in the same pinned buffer: building a plan and uploading it copies nothing from pageable memory, so even
+        the first update synchronises nothing."""
+        avg = [(a, p) for a, p, k in trio if k == 'avg' and a.numel()]
+        raw = [(a, p) for a, p, k in trio if k == 'raw' and a.numel()]
+        order = avg + raw
+        dev = order[0][0].device
+        n_rows = slots + (1 if avg and raw else 0)
+        own = rows is None
+        row_bytes = (n_rows * 32 + 63) // 64 * 64 if own else 0
+        tab_bytes = len(order) * _DESC.itemsize
+        numels = [a.numel() for a, _ in avg] + [a.numel() * a.element_size() // 4 for a, _ in raw]
+        E = lib.adam_chunk_elems()
+        chunk_list = np.array([(i, c) for i, n in enumerate(numels) for c in range((n + E - 1) // E)],
+                              dtype=np.int32).reshape(-1, 2)
+        n_chunks = len(chunk_list)
+        chunks_at = (row_bytes + slots * tab_bytes + 15) // 16 * 16
+        pin = torch.zeros(chunks_at + n_chunks * 8, dtype=torch.uint8).pin_memory()
+        host = pin.numpy()
+        devbuf = torch.zeros(chunks_at + n_chunks * 8, dtype=torch.uint8, device=dev)
+        host[chunks_at:].view(np.int32)[:] = chunk_list.reshape(-1)
+        if own:
+            rows, dev_rows = host[:n_rows * 32], devbuf[:n_rows * 32]
+        if rows.nbytes != n_rows * 32:
+            raise lib.BmnasError(f'bmnas.optim.AveragedModel: {n_rows} rows need {n_rows * 32} bytes, got {rows.nbytes}')
+        rows = rows.view(_AVG_ROW)
+        tabs = [host[row_bytes + s * tab_bytes:row_bytes + (s + 1) * tab_bytes].view(_DESC) for s in range(slots)]
+        for s, tab in enumerate(tabs):
+            tab['numel'] = numels
+            tab['hyp_row'] = [s] * len(avg) + [slots if avg else s] * len(raw)
+        if avg and raw:
+            rows[slots] = (0.0, 0.0, lib.AVG_RAW, 0, 0, 0)    # (its count is never read: tensor 0 is an averaged one)
+        return dict(order=order, numels=numels, raw_only=not avg, slots=slots, own=own, pin=pin, host=host, dev=devbuf,
+                    rows=rows, dev_rows=dev_rows, tabs=tabs, chunks=devbuf[chunks_at:],
+                    dev_tabs=[devbuf[row_bytes + s * tab_bytes:row_bytes + (s + 1) * tab_bytes] for s in range(slots)],
+                    n_chunks=n_chunks, sent=None, event=None, cap_slot=0)
+
+    @staticmethod
+    def _write_ptrs(pl):
+        for tab in pl['tabs']:
+            tab['param'] = [a.data_ptr() for a, _ in pl['order']]
+            tab['grad'] = [p.data_ptr() for _, p in pl['order']]
+
+    def _write_row(self, pl, slot, n):
+        pl['rows'][slot] = avg_row(n, self.decay, raw=pl['raw_only'])
+
+    @staticmethod
+    def _wait(pl):
+        """Block until the last upload has read the plan's pinned buffer (the host may run ahead of the GPU)."""
+        if pl['event'] is not None:
+            pl['event'].synchronize()
+
+    @staticmethod
+    def _upload(pl):
+        """One pinned async copy of everything staged — unless the device already holds exactly these bytes."""
+        if pl['sent'] is not None and np.array_equal(pl['sent'], pl['host']):
+            return
+        pl['dev'].copy_(pl['pin'], non_blocking=True)
+        if pl['event'] is None:
+            pl['event'] = torch.cuda.Event()
+        pl['event'].record()
+        pl['sent'] = pl['host'].copy()
+
+    def _launch(self, pl, slot=0):
+        lib.avg_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_rows'], self.n_averaged)
+        self.launches += 1
+
+    def _run_eager(self, key, trio, n):
+        """Stage and launch an eager update over `trio` (its plan is kept under `key`)."""
+        order = [(a, p) for a, p, k in trio if k == 'avg' and a.numel()] + \
+                [(a, p) for a, p, k in trio if k == 'raw' and a.numel()]
+        pl = self._eager.get(key)
+        if pl is None or len(pl['order']) != len(order) or any(
+                m != a.numel() * a.element_size() // 4 for m, (a, _) in zip(pl['numels'], order)):
+            pl = self._eager[key] = self._build(trio)
+        self._wait(pl)
+        pl['order'] = order                          # (the tensors may have been re-pointed: addresses are re-read)
+        self._write_ptrs(pl)
+        self._write_row(pl, 0, n)
+        self._upload(pl)
+        self._launch(pl)
+
+    def _copy_frozen(self, model, n):
+        """skip_frozen, first update: the frozen parameters, bitwise, in a launch of their own."""
+        trio = [(a, p, 'raw') for a, p, _, frozen in self.pairs(model) if frozen and a.numel()]
+        if trio:
+            self._run_eager((id(model), 'frozen'), trio, n)
+
+    # ------------------------------------------------------------------ torch's API
+    @torch.no_grad()
+    def update_parameters(self, model):
+        """One launch (the first update of a skip_frozen averager: two), no host synchronisation."""
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            pl = self._capturing
+            if pl is None or pl['model'] is not model or pl['cap_slot'] >= pl['slots']:
+                raise lib.BmnasError('bmnas.optim.AveragedModel: call capture_safe() before capturing update_parameters() '
+                                     'in a graph (once per captured update)')
+            self._launch(pl, pl['cap_slot'])
+            pl['cap_slot'] += 1
+            return
+        if self._checked is None or self._checked[0]() is not model:
+            self._checked = (weakref.ref(model), self.off_path(model))
+        why = self._checked[1]
+        if why is not None:
+            lib.note_off_path('bmnas.optim.AveragedModel', why)
+            self._n = None
+            return super().update_parameters(model)
+        n = self._count()
+        if self.skip_frozen and n == 0:
+            self._copy_frozen(model, n)
+        trio = self._main(model)
+        if any(a.numel() for a, _, _ in trio):
+            self._run_eager((id(model), 'all'), trio, n)
+        else:
+            self.n_averaged.fill_(n + 1)
+        self._n = n + 1
+
+    # ------------------------------------------------------------------ hipGraph support
+    def capture_rows(self, model, slots=1):
+        """How many bytes of rows `slots` captured updates of `model` need behind an optimizer's (capture_safe(extra=...))."""
+        why = self.off_path(model)
+        if why is not None:
+            raise lib.BmnasError(f'bmnas.optim.AveragedModel: a captured update needs the HIP kernel ({why})')
+        trio = self._main(model)
+        kinds = {k for a, _, k in trio if a.numel()}
+        if not kinds:
+            raise lib.BmnasError('bmnas.optim.AveragedModel: nothing to average in a captured update')
+        return (slots + (1 if len(kinds) == 2 else 0)) * 32
+
+    def capture_safe(self, model, rows, dev_rows, slots=1):
+        """Build the plan of `slots` captured updates: the descriptor tables go up NOW (the graph bakes their addresses and
+        those of the tensors), the rows live in `rows` / `dev_rows` — an optimizer plan's `extra` / `dev_extra`, whose
+        upload (by value in front of the replay, or the plan's copy node) carries them.  update_parameters(model) inside
+        `torch.cuda.graph` then issues one launch per call.  Take the plan with captured_plan() after the capture — its
+        holder (bmnas.graph.GraphedTrainStep) passes it to prepare_replay(plan, slot) before every replay: an averager
+        may ride in several captured steps (the loop's one-step and k-step graphs), each with a plan of its own."""
+        if self._capturing is not None:
+            raise lib.BmnasError('bmnas.optim.AveragedModel: capture_safe() while another capture is open (take it with '
+                                 'captured_plan(), or drop it with abandon_capture(), first)')
+        trio = self._main(model)
+        pl = self._build(trio, slots, rows, dev_rows)
+        self._write_ptrs(pl)
+        self._upload(pl)
+        self._wait(pl)
+        pl['model'] = model
+        self._capturing = pl
+
+    def abandon_capture(self):
+        """Drop the plan of a capture that failed."""
+        self._capturing = None
+
+    def captured_plan(self):
+        """The plan a capture has just baked into a graph; closes the capture."""
+        pl = self._capturing
+        if pl is None:
+            raise lib.BmnasError('bmnas.optim.AveragedModel: no open capture (capture_safe() + captured updates first)')
+        if pl['cap_slot'] != pl['slots']:
+            raise lib.BmnasError(f'bmnas.optim.AveragedModel: the capture holds {pl["cap_slot"]} update(s), the plan was '
+                                 f'built for {pl["slots"]}')
+        self._capturing = None
+        self.captures += 1
+        return pl
+
+    def prepare_replay(self, plan, slot=0):
+        """Write the row of update number `slot` of the replay of `plan` (from captured_plan()) into ITS riding rows and
+        count it; the first update of a skip_frozen averager copies the frozen parameters here, eagerly, in front of the
+        replay."""
+        pl = plan
+        if pl is None or pl.get('model') is None or pl['cap_slot'] != pl['slots'] or pl is self._capturing:
+            raise lib.BmnasError('bmnas.optim.AveragedModel: prepare_replay() needs a plan from captured_plan()')
+        if not 0 <= slot < pl['slots']:
+            raise lib.BmnasError(f'bmnas.optim.AveragedModel: slot {slot} of a plan of {pl["slots"]} update(s)')
+        n = self._count()
+        if self.skip_frozen and n == 0:
+            self._copy_frozen(pl['model'], n)
+        self._write_row(pl, slot, n)
+        self._n = n + 1

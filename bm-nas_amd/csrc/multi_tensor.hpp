@@ -1,5 +1,5 @@
-// The walk of the multi-tensor launches over a (tensor, chunk) list, per workgroup — the ONE definition adam.hip and
-// unroll.hip compile — and the norm both derive from the partials of bmnas_grad_sqnorm_multi.
+// The walk of the multi-tensor launches over a (tensor, chunk) list, per workgroup — the ONE definition adam.hip,
+// unroll.hip and average.hip compile — and the norm both derive from the partials of bmnas_grad_sqnorm_multi.
 //
 // A launch has one workgroup of 256 lanes per entry (ti, ci) of the chunk list: chunk ci of tensor ti is elements
 // ci * kChunk .. + kChunk - 1, four consecutive ones per lane.  A lane whose four lie inside the tensor, in a tensor
@@ -16,6 +16,7 @@
 //   unroll_perturb_k    param | grad | exp_avg_sq
 //   unroll_restore_k    param | exp_avg_sq
 //   unroll_combine_k    param | grad | exp_avg
+//   avg_multi_k         param | grad             (param the averaged tensor, grad the live one; RAW rows: as words) average.hip
 // Both lambdas capture by reference and are inlined: every kernel keeps the registers, LDS and occupancy it had with
 // the walk written out (profiles/r19_optim_walk.txt).
 #pragma once

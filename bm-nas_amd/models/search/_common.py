@@ -142,6 +142,46 @@ def _make_optimizer(args, prefix, params, lr, weight_decay, max_grad_norm, betas
     raise ValueError(f"args.{prefix}optimizer must be 'adam' or 'sgd', got {kind!r}")
 
 
+def averaging_options(args, status):
+    """Weight averaging of a found-stage run (optional; the reference's argument sets have none of these):
+      args.ema_decay            a float in [0, 1]: an exponential moving average of the weights, updated after every weight
+                                step and evaluated instead of the live weights — the usual last step of a retraining run
+      args.swa_start            an epoch: stochastic weight averaging, one snapshot at the end of every epoch from this
+                                one on (the scheduler is SGDR with warm restarts: a snapshot per restart is the SWA recipe)
+      args.average_skip_frozen  default True: parameters with requires_grad=False (the frozen backbones) are copied once
+                                and left out of later updates
+    -> None when neither is set, else dict(decay, swa_start, skip_frozen).  Refused in a search (status != 'eval'):
+    averaged weights would not belong to the current alphas."""
+    decay, swa_start = getattr(args, 'ema_decay', None), getattr(args, 'swa_start', None)
+    if decay is None and swa_start is None:
+        return None
+    if status != 'eval':
+        raise ValueError("args.ema_decay / args.swa_start average the weights of a found-stage run (status 'eval') only: "
+                         f"in a search (status {status!r}) the averaged weights would not belong to the current alphas")
+    if decay is not None and swa_start is not None:
+        raise ValueError('args.ema_decay and args.swa_start are two recipes over one averaged model: set one of them')
+    if decay is not None:
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f'args.ema_decay must be in [0, 1], got {decay!r}')
+    else:
+        swa_start = int(swa_start)
+        if swa_start < 0:
+            raise ValueError(f'args.swa_start must be an epoch >= 0, got {swa_start!r}')
+    return dict(decay=decay, swa_start=swa_start, skip_frozen=bool(getattr(args, 'average_skip_frozen', True)))
+
+
+def make_averager(model, args, status):
+    """-> (bmnas.optim.AveragedModel of `model`, its options), or (None, None) without the options.  use_buffers=True:
+    the native BatchNorm kernels fix momentum 0.1, so swa_utils.update_bn's cumulative pass is not available — averaged
+    running statistics stand in for it."""
+    opts = averaging_options(args, status)
+    if opts is None:
+        return None, None
+    from bmnas.optim import AveragedModel
+    return AveragedModel(model, decay=opts['decay'], use_buffers=True, skip_frozen=opts['skip_frozen']), opts
+
+
 def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_decay):
     """Optimizers, scheduler, device placement, data parallelism and the Architect — the body of
     the reference's train_darts_model between model construction and the trainer call

@@ -274,6 +274,13 @@ class NodeMixedOp(nn.Module):
         cfc.bn.num_batches_tracked.data = nbt[1]
         self._stack = Pack(W=W, bias=bias, bn_w=bn_w, bn_b=bn_b, rm=rm, rv=rv, nbt=nbt)
 
+    def settle_storage(self):
+        """Move the conv + BatchNorm tensors into their stacked storage NOW instead of at the next pack(): a deep copy of
+        this module holds clones of the parameters next to a copy of the stack, and whoever keeps the copy's tensor
+        addresses (bmnas.optim.AveragedModel under a captured update) needs them final."""
+        if self._kind('LinearGLU') is not None and self._fc() is not None and not self._stack_ok():
+            self._restack()
+
     def conv_rows(self):
         """M: rows of the one conv GEMM of this op (2C LinearGLU + C ConcatFC | CatConvMish, as present)."""
         return (2 * self.C if 'LinearGLU' in self._prims else 0) + (self.C if self._fc_name() else 0)

@@ -14,7 +14,12 @@ Differences, all on the host side of the hot path:
     single-process runs; `args.hip_graph` / BMNAS_HIP_GRAPH switch it (GraphedTrainStep.enabled);
   * the gradient-free passes — the metric forward of every dev batch after `architect.step`, the
     eval / test passes — are hipGraph replays too (bmnas.graph.GraphedForward, one graph per module
-    mode and batch shape): issued eagerly that forward is host-bound, 0.55-0.86 ms against 0.11 ms.
+    mode and batch shape): issued eagerly that forward is host-bound, 0.55-0.86 ms against 0.11 ms;
+  * optional, found-stage runs (status 'eval') only: weight averaging (models.search._common.averaging_options:
+    args.ema_decay / args.swa_start / args.average_skip_frozen) on bmnas.optim.AveragedModel — an EMA updated after
+    every weight step (inside the replay when the step is captured, eagerly on ragged batches) or an SWA snapshot at
+    the end of every epoch from args.swa_start on; the phases that do not learn then evaluate the AVERAGED module and
+    `best_test_averaged.pt` is saved next to `best_test_model.pt`.  With no option set nothing changes.
 """
 import copy
 import os
@@ -152,6 +157,13 @@ class _ForwardGraphs:
         self.graphs, self.attempts, self.logger = [], 0, logger
         self.replays = 0
 
+    def __deepcopy__(self, memo):
+        """A deep copy of the model (bmnas.optim.AveragedModel) starts without graphs: these read the ORIGINAL's
+        parameters, and a captured graph cannot be copied."""
+        new = _ForwardGraphs.__new__(_ForwardGraphs)
+        new.on, new.graphs, new.attempts, new.logger, new.replays = self.on, [], 0, self.logger, 0
+        return new
+
     @staticmethod
     def of(model, criterion, args, logger=None):
         """The graphs of (model, criterion), kept ON the model across run() / evaluate() calls: a capture costs three
@@ -231,6 +243,17 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     wk_graph, wk_attempts = None, 0
     f_graphs = _ForwardGraphs.of(model, criterion, args, logger)
     stats = run.stats = dict(graph_replays=0, eager_steps=0, forward_replays=0, k_step_replays=0)
+    # weight averaging (found-stage runs only; refused in a search): None without the options — and nothing below changes
+    from models.search._common import make_averager
+    averaged, avg_opts = make_averager(model, args, status)
+    run.averaged = averaged          # (like run.stats: the caller's handle on the averaged model of this run)
+    ema = averaged if averaged is not None and avg_opts['decay'] is not None else None     # updated after every step
+    avg_graphs = _ForwardGraphs.of(averaged.module, criterion, args, logger) if averaged is not None else None
+    if averaged is not None:
+        stats['averaged_updates'] = 0
+        stats['averaged_forwards'] = 0
+    # SWA: the phase after which an epoch's snapshot is taken — its last learning one (train and dev both learn here)
+    swa_phase = ([ph for ph in eval_phases if ph in ('train', 'dev')] or [None])[-1] if averaged is not None else None
     best = dict(best_dev=None, best_dev_genotype=None, best_dev_epoch=0, best_test=None,
                 best_test_genotype=None, best_test_epoch=0, last_genotype=None, nan_abort=False)
     # the unrolled architecture step (architect.unrolled) draws one training batch per dev batch from an iterator of its
@@ -267,15 +290,27 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 model.train()                  # the reference keeps BN/dropout in train mode here
             else:
                 model.eval()
+            learn = phase == 'train' or (phase == 'dev' and status == 'eval')
+            # a phase that does not learn evaluates the averaged weights, once there are any (SWA: from its first snapshot)
+            use_avg = averaged is not None and not learn and stats['averaged_updates'] > 0
+            net, net_graphs = (averaged.module, avg_graphs) if use_avg else (model, f_graphs)
+            if use_avg:
+                averaged.module.eval()
             meter.reset(device)
             loss_sum = torch.zeros((), device=device, dtype=torch.float64)
             seen = 0
-            learn = phase == 'train' or (phase == 'dev' and status == 'eval')
             loader = dataloaders[phase]
             split = _world() > 1 and not _is_sharded(loader)
             if _world() > 1 and _is_sharded(loader):
                 loader.sampler.set_epoch(epoch)          # a new shuffle per epoch, the same on every rank
             _set_weight(1.0)                             # (a shard weight belongs to ONE scattered batch: none carries over)
+            def averaged_step(in_replay=False):
+                """The EMA's update after a weight step — unless the replay that took the step held it."""
+                if ema is not None:
+                    if not in_replay:
+                        ema.update_parameters(model)
+                    stats['averaged_updates'] += 1
+
             def one_batch(inputs, labels):
                 nonlocal w_graph, w_attempts, loss_sum
                 # nothing of the previous batch's autograd graph may stay referenced while a step is
@@ -291,6 +326,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                             scheduler.step()
                             scheduler.update_optimizer(optimizer)
                         _idle_step(optimizer)
+                        averaged_step()
                     stats['idle_steps'] = stats.get('idle_steps', 0) + 1
                     return
                 if status == 'search' and phase in ('dev', 'test') and architect is not None:
@@ -309,12 +345,13 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     if w_graph is None and w_attempts < 3:
                         w_attempts += 1
                         w_graph = GraphedTrainStep.try_build(model, criterion, optimizer, inputs, labels,
-                                                             logger) or None
+                                                             logger, averaged=ema) or None
                     if w_graph and w_graph.matches(inputs, labels):
                         if cosine:
                             scheduler.step()
                             scheduler.update_optimizer(optimizer)
                         loss, output = w_graph(inputs, labels)
+                        averaged_step(in_replay=w_graph.averaged is not None)
                         loss_sum += loss.detach().double() * labels.size(0)
                         meter.update(output.detach(), labels)
                         stats['graph_replays'] += 1
@@ -325,7 +362,9 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     # the metric pass: no gradients, one replay (the step above — architect.step in the dev phase —
                     # has already happened: this forward sees the updated alphas, like the reference's)
                     if got is None:
-                        got = f_graphs(model, criterion, inputs, labels)
+                        got = net_graphs(net, criterion, inputs, labels)
+                        if use_avg:
+                            stats['averaged_forwards'] += 1
                     else:
                         stats['merged_metric_replays'] = stats.get('merged_metric_replays', 0) + 1
                     if got is not None:
@@ -339,7 +378,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 stats['eager_steps'] += 1
                 optimizer.zero_grad()
                 with torch.set_grad_enabled(learn):
-                    output = model(inputs)
+                    output = net(inputs)
                     if isinstance(output, tuple):
                         output = output[-1]
                     loss = criterion(output, labels)
@@ -349,6 +388,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                             scheduler.update_optimizer(optimizer)
                         loss.backward()
                         optimizer.step()
+                        averaged_step()
                 loss_sum += loss.detach().double() * labels.size(0)
                 meter.update(output.detach(), labels)
                 _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
@@ -361,7 +401,8 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 x0, y0 = batches[0]
                 if wk_graph is None and wk_attempts < 3:
                     wk_attempts += 1
-                    wk_graph = GraphedTrainStep.try_build(model, criterion, optimizer, x0, y0, logger, k=k_steps) or None
+                    wk_graph = GraphedTrainStep.try_build(model, criterion, optimizer, x0, y0, logger, k=k_steps,
+                                                          averaged=ema) or None
                 if not (wk_graph and all(wk_graph.matches(x_, y_) for x_, y_ in batches)):
                     for x_, y_ in batches:
                         one_batch(x_, y_)
@@ -374,6 +415,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     lrs.append(wk_graph.stage(j, x_, y_))
                 stats['k_step_replays'] += 1
                 for (loss, output), (x_, y_), lr in zip(wk_graph.replay_staged(), batches, lrs):
+                    averaged_step(in_replay=wk_graph.averaged is not None)
                     loss_sum += loss.detach().double() * y_.size(0)
                     meter.update(output.detach(), y_)
                     stats['graph_replays'] += 1
@@ -435,6 +477,9 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 one_batch(inputs, labels)
             flush()
             _set_weight(1.0)
+            if averaged is not None and ema is None and phase == swa_phase and epoch >= avg_opts['swa_start']:
+                averaged.update_parameters(model)        # the SWA snapshot of this epoch: eager
+                stats['averaged_updates'] += 1
             n = dataset_sizes[phase]
             if _world() > 1:
                 # what the ranks processed together (a DistributedSampler pads; a split covers every sample)
@@ -463,6 +508,9 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     best[key + '_epoch'] = epoch
                     if _rank() == 0:
                         save(model, os.path.join(args.save, 'best', fname))
+                        if averaged is not None and which == 'test':
+                            # (torch.optim.swa_utils.AveragedModel's keys: `module.*` and `n_averaged`)
+                            save(averaged, os.path.join(args.save, 'best', 'best_test_averaged.pt'))
                         save_pickle(best[key + '_genotype'],
                                     os.path.join(args.save, 'best', fname.replace('model.pt', 'genotype.pkl')))
         plotter.plot(best['last_genotype'], os.path.join(args.save, 'architectures', 'epoch_{}'.format(epoch)),

@@ -962,6 +962,38 @@ int bmnas_sgd_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, i
                     const float* hyp, int flags, const float* partials, int n_parts, const float* clip,
                     float* norm_out, void* stream);
 
+/* ---- weight averaging: EMA / SWA of a model's tensors in one launch (csrc/average.hip) ------------------------
+ * torch.optim.swa_utils.AveragedModel.update_parameters as ONE launch, with no host synchronisation, over the
+ * descriptor table and the (tensor, chunk) list of bmnas_adam_multi (one workgroup per chunk, the same alignment rule).
+ * A descriptor's columns mean here: `param` = the AVERAGED tensor (read and written), `grad` = the LIVE tensor (read
+ * only); `exp_avg` / `exp_avg_sq` are not read.  `hyp_row` selects a 32-byte row of `rows`:
+ *     w      the weight of the live tensor: 1 - decay (EMA), float(1 / (n + 1)) (SWA), 1 (the first update)
+ *     omw    1 - w, formed by the host in double and rounded once
+ *     flags  BMNAS_AVG_RAW or 0
+ *     count  the number of updates this one completes
+ * Per element at::lerp(a, p, w), every operation rounded on its own (no fused multiply-add):
+ *     d = p - a;   |w| < 0.5:  a = a + w * d;   otherwise:  a = p - d * omw
+ *   The branch is on the row (uniform per workgroup).  w = 1, omw = 0 gives a = p for finite values — torch's first
+ *   update, a copy, is such a row and no kernel variant: one captured graph serves every replay.
+ * BMNAS_AVG_RAW: the row's tensors are copied bitwise as 32-bit words, `numel` counting WORDS (an int64 tensor of n
+ *   elements has numel 2 n); pointers need 4-byte alignment.  Integer buffers (num_batches_tracked) and buffers that
+ *   are kept in sync by copy.
+ * n_averaged: DEVICE int64; lane 0 of workgroup 0 stores the `count` of ITS tensor's row there — a value the host
+ *   passed: no read-modify-write, no atomic.
+ * Reads both tensors, writes the averaged one with plain stores: 12 B per element (RAW: 8 B per word).
+ * BMNAS_E_ARG (nothing launched): a NULL pointer; n_chunks <= 0. */
+#define BMNAS_AVG_RAW 1
+typedef struct {
+  float w;
+  float omw;
+  uint32_t flags;
+  uint32_t reserved0;
+  int64_t count;
+  int64_t reserved1;
+} bmnas_avg_row_t;
+int bmnas_avg_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                    const bmnas_avg_row_t* rows, int64_t* n_averaged, void* stream);
+
 /* ---- unrolled (second-order) architecture step of DARTS (csrc/unroll.hip) -----------------------------------
  * The reference still passes `unrolled=args.unrolled` to its Architect (models/search/darts/train_search.py:151,
  * the flag at :42 and main_darts_found_ntu.py:48) and keeps `network_weight_decay` for it
