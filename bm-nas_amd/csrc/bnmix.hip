@@ -1211,11 +1211,24 @@ __device__ __forceinline__ void cell_prologue_body(const ArchPack& P, const Fold
       const int cols = P.cols[t];
       const float* a = P.a[t] + r * cols;
       float* o = P.o[t] + r * cols;
-      float mx = a[0];
-      for (int p = 1; p < cols; ++p) mx = fmaxf(mx, a[p]);
-      float den = 0.f;
-      for (int p = 0; p < cols; ++p) den += expf(a[p] - mx);
-      for (int p = 0; p < cols; ++p) o[p] = expf(a[p] - mx) / den;
+      // the row's (at most four) logits in ONE batch, from clamped addresses: the three loops over `cols` below each
+      // loaded a[p] again, one s_waitcnt vmcnt(0) per trip — up to eleven dependent round trips in the one workgroup
+      // of the launch that every other one finishes ahead of
+      float av[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) av[p] = a[p < cols ? p : cols - 1];
+      float mx = av[0];
+#pragma unroll
+      for (int p = 1; p < 4; ++p) mx = p < cols ? fmaxf(mx, av[p]) : mx;
+      float ev[4], den = 0.f;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        ev[p] = expf(av[p] - mx);
+        den = p < cols ? den + ev[p] : den;
+      }
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (p < cols) o[p] = ev[p] / den;
       return;
     }
     r -= P.rows[t];
@@ -1260,15 +1273,21 @@ __global__ __launch_bounds__(256) void cell_prologue_pair_k(ArchPack P, FoldPack
     cell_prologue_body(P, F, step_counter, step_span, scrub, scrub4, (int)blockIdx.x, n_pro);
     return;
   }
+  const int64_t stride = (int64_t)(gridDim.x - n_pro) * 256;
+  int64_t i = (int64_t)(blockIdx.x - n_pro) * 256 + threadIdx.x;
+  if (i >= A.n4) return;
+  // the first trip's operands are requested BEFORE the edge weights: the logits sit behind pointers of the argument
+  // block (a second scalar round trip) and their softmaxes are ~350 instructions — in front of the operand loads both
+  // were part of the launch's one dependent chain, behind them they run while the operands travel
+  float4 v[NIN];
+#pragma unroll
+  for (int j = 0; j < NIN; ++j) v[j] = reinterpret_cast<const float4*>(A.xs.p[j])[i];
+  __builtin_amdgcn_sched_barrier(0);
   float wj[NIN];
 #pragma unroll
   for (int j = 0; j < NIN; ++j) wj[j] = softmax2_col1(A.alpha + 2 * j);
   const float s2 = softmax2_col1(A.beta) + softmax2_col1(A.beta + 2);
-  const int64_t stride = (int64_t)(gridDim.x - n_pro) * 256;
-  for (int64_t i = (int64_t)(blockIdx.x - n_pro) * 256 + threadIdx.x; i < A.n4; i += stride) {
-    float4 v[NIN];
-#pragma unroll
-    for (int j = 0; j < NIN; ++j) v[j] = reinterpret_cast<const float4*>(A.xs.p[j])[i];
+  for (;;) {
     float4 acc = f4_scale(v[0], wj[0]);
 #pragma unroll
     for (int j = 1; j < NIN; ++j) {
@@ -1279,6 +1298,10 @@ __global__ __launch_bounds__(256) void cell_prologue_pair_k(ArchPack P, FoldPack
     }
     st4_w0<0>(A.out + 4 * i, acc);
     st4_w0<0>(A.out2 + 4 * i, f4_scale(acc, s2));
+    i += stride;
+    if (i >= A.n4) break;
+#pragma unroll
+    for (int j = 0; j < NIN; ++j) v[j] = reinterpret_cast<const float4*>(A.xs.p[j])[i];
   }
 }
 

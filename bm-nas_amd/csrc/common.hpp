@@ -309,6 +309,14 @@ __device__ __forceinline__ T* pick_ptr(T* const (&arr)[N], int q) {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// A batch of loads that must ALL be requested before the first of them is waited for: hipcc sinks a load whose
+// value is used under a condition only (a clamped, later-masked load of an unrolled trip) into that condition, where
+// it becomes load -> s_waitcnt vmcnt(0) -> use again, one dependent round trip per trip.  An empty asm that takes the
+// value in and hands it out again, placed behind the whole batch, is a use the compiler cannot move under a branch:
+// the loads stay in front of it, together.  (The asm waits for its operands: pin in the order of the loads.)
+__device__ __forceinline__ void pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
+__device__ __forceinline__ void pin1(float& v) { asm volatile("" : "+v"(v)); }
+
 // Write-through (sc1) 16-byte store: the bytes go to memory when the store is issued instead of staying dirty in the
 // XCD's L2 until the kernel's end-of-launch write-back (MI355X_MICROARCH.md, "boundary": + B / 6 TB/s for B dirty
 // bytes) — for tensors the NEXT launch reads, mostly from other XCDs anyway.  hipcc does not count an asm store in its

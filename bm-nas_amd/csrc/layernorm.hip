@@ -239,38 +239,89 @@ struct LnAffineBatch {
   int n, b, chunk;
 };
 
+// The loads of FOUR sample trips (x, gy, resid, stats) go out together, before the first FMA, from clamped addresses
+// and without a branch around any of them: an absent operand (resid, stats under prenorm, ln_w / ln_b without ReLU,
+// gscale) reads g instead and is dropped by a select.  A sample chunk of 16 (b <= 256) is one such group = one memory
+// round trip per workgroup; the loop form — load under `if`, s_waitcnt vmcnt(0) at the join, per trip — was 8 to 12.
+// Longer chunks run in groups of four trips.  aw / ab still accumulate in sample order.
+// P's fields are copied into registers first: P is B.p[blockIdx.z], a run-time index into the argument block, and
+// inside the loop every use was a scalar load of its own.
 __device__ __forceinline__ void ln_affine_body(const LnAffineProb& P, int b, int chunk, float4 (*red)[3][64]) {
   const int col = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + col;
-  const bool active = i < P.d4;
-  const float gs = (P.gscale != nullptr) ? P.gscale[0] : 1.f;
+  const int d4 = P.d4, cl4 = P.cl4;
+  const bool relu = P.relu != 0, prenorm = P.prenorm != 0;
+  const float* __restrict__ g = P.g;
+  const float* gscale = P.gscale;
+  const float* resid = P.resid;
+  const float* stats = P.stats;
+  const float* ln_w = P.ln_w;
+  const float* ln_b = P.ln_b;
+  float* dln_w = P.dln_w;
+  float* dln_b = P.dln_b;
+  const float* src[4] = {sgpr_ptr(P.srcs.p[0]), sgpr_ptr(P.srcs.p[1]), sgpr_ptr(P.srcs.p[2]), sgpr_ptr(P.srcs.p[3])};
+  const int i0 = blockIdx.x * 64 + col;
+  const bool active = i0 < d4;
+  const int i = active ? i0 : d4 - 1;                                // clamped: an idle lane repeats the last column
+  const int q = i / cl4;
+  const int off = i - q * cl4;
+  const float* xsrc = src[0];                                        // (selects over SGPR pointers, pick_ptr)
+#pragma unroll
+  for (int qq = 1; qq < 4; ++qq) xsrc = (q == qq) ? src[qq] : xsrc;
+  const bool has_r = !prenorm && resid != nullptr, has_st = !prenorm;
+  const float* rp = has_r ? resid : g;
+  const float* sp = has_st ? stats : g;                              // (g holds >= 4 b floats)
+  const float4 w = ld4((relu ? ln_w : g) + (int64_t)i * 4);
+  const float4 bb = ld4((relu ? ln_b : g) + (int64_t)i * 4);
+  const float gsv = (gscale != nullptr ? gscale : g)[0];           // (selected behind the first batch, below)
   float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), ab = aw;
-  if (active) {
-    float4 w = make_float4(0.f, 0.f, 0.f, 0.f), bb = w;
-    if (P.relu) {
-      w = ld4(P.ln_w + (int64_t)i * 4);
-      bb = ld4(P.ln_b + (int64_t)i * 4);
+  const int s_beg = blockIdx.y * chunk;
+  int s_end = s_beg + chunk;
+  if (s_end > b) s_end = b;
+  for (int sg = s_beg; sg < s_end; sg += 16) {
+    float4 xv[4], gv[4], rv[4];
+    float mean[4], rstd[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int s_raw = sg + 4 * k + sl;
+      const int s = s_raw < s_end ? s_raw : s_end - 1;
+      xv[k] = ld4(xsrc + ((int64_t)s * cl4 + off) * 4);
+      gv[k] = ld4(g + ((int64_t)s * d4 + i) * 4);
+      rv[k] = ld4(rp + ((int64_t)s * d4 + i) * 4);
+      mean[k] = sp[2 * s];
+      rstd[k] = sp[2 * s + 1];
     }
-    const int s_beg = blockIdx.y * chunk;
-    int s_end = s_beg + chunk;
-    if (s_end > b) s_end = b;
-    for (int s = s_beg + sl; s < s_end; s += 4) {
-      float4 x = ld4(src_ptr(P.srcs, i, P.cl4, s));
-      float4 gy = f4_scale(ld4(P.g + ((int64_t)s * P.d4 + i) * 4), gs);
-      float4 h = x;
-      if (!P.prenorm) {
-        if (P.resid != nullptr) x = f4_add(x, ld4(P.resid + ((int64_t)s * P.d4 + i) * 4));
-        const float mean = P.stats[2 * s], rstd = P.stats[2 * s + 1];
-        h = make_float4((x.x - mean) * rstd, (x.y - mean) * rstd, (x.z - mean) * rstd, (x.w - mean) * rstd);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                    // (pin4, common.hpp: the batch stays a batch)
+      pin4(xv[k]);
+      pin4(gv[k]);
+      pin4(rv[k]);
+      pin1(mean[k]);
+      pin1(rstd[k]);
+    }
+    float gs = gsv;
+    pin1(gs);                                                        // (not hoisted in front of the loop: a wait there)
+    gs = gscale != nullptr ? gs : 1.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (sg + 4 * k + sl < s_end) {
+        float4 x = xv[k];
+        float4 gy = f4_scale(gv[k], gs);
+        float4 h = x;
+        if (!prenorm) {
+          if (has_r) x = f4_add(x, rv[k]);
+          h = make_float4((x.x - mean[k]) * rstd[k], (x.y - mean[k]) * rstd[k], (x.z - mean[k]) * rstd[k],
+                          (x.w - mean[k]) * rstd[k]);
+        }
+        if (relu) {
+          if (h.x * w.x + bb.x <= 0.f) gy.x = 0.f;
+          if (h.y * w.y + bb.y <= 0.f) gy.y = 0.f;
+          if (h.z * w.z + bb.z <= 0.f) gy.z = 0.f;
+          if (h.w * w.w + bb.w <= 0.f) gy.w = 0.f;
+        }
+        aw = f4_add(aw, f4_mul(gy, h));
+        ab = f4_add(ab, gy);
       }
-      if (P.relu) {
-        if (h.x * w.x + bb.x <= 0.f) gy.x = 0.f;
-        if (h.y * w.y + bb.y <= 0.f) gy.y = 0.f;
-        if (h.z * w.z + bb.z <= 0.f) gy.z = 0.f;
-        if (h.w * w.w + bb.w <= 0.f) gy.w = 0.f;
-      }
-      aw = f4_add(aw, f4_mul(gy, h));
-      ab = f4_add(ab, gy);
     }
   }
   if (sl > 0) {
@@ -284,8 +335,8 @@ __device__ __forceinline__ void ln_affine_body(const LnAffineProb& P, int b, int
       aw = f4_add(aw, red[0][k][col]);
       ab = f4_add(ab, red[1][k][col]);
     }
-    float* pw = P.dln_w + (int64_t)i * 4;
-    float* pb = P.dln_b + (int64_t)i * 4;
+    float* pw = dln_w + (int64_t)i * 4;
+    float* pb = dln_b + (int64_t)i * 4;
     atomicAdd(pw + 0, aw.x); atomicAdd(pw + 1, aw.y); atomicAdd(pw + 2, aw.z); atomicAdd(pw + 3, aw.w);
     atomicAdd(pb + 0, ab.x); atomicAdd(pb + 1, ab.y); atomicAdd(pb + 2, ab.z); atomicAdd(pb + 3, ab.w);
   }
@@ -322,15 +373,32 @@ __global__ __launch_bounds__(256) void backward_epilogue_k(LnAffineBatch B, Arch
     const long long per = (long long)gridDim.x * gridDim.y;
     const long long n4 = S.n4[i], wg = rep * per + (long long)blockIdx.y * gridDim.x + blockIdx.x;
     const float* __restrict__ part = S.part[i];
-    for (long long e = wg * 256 + threadIdx.x; e < n4; e += (long long)S.reps * per * 256) {
-      float4 t = ld4(part + 4 * e);
-      for (int c = 1; c < S.n_chunk[i]; ++c) t = f4_add(t, ld4(part + 4 * (e + (long long)c * n4)));
-      st4_wtg<3>(S.out[i] + 4 * e, t);
+    float* __restrict__ out = S.out[i];
+    const int nc = S.n_chunk[i];
+    const long long step = (long long)S.reps * per * 256;
+    // an element's chunks are requested four at a time (clamped, masked) and added in chunk order: one round trip per
+    // element at n_chunk <= 4 instead of one per chunk
+    for (long long e = wg * 256 + threadIdx.x; e < n4; e += step) {
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int c0 = 0; c0 < nc; c0 += 4) {
+        float4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = ld4(part + 4 * (e + (long long)(c0 + k < nc ? c0 + k : nc - 1) * n4));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pin4(v[k]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (c0 + k < nc) t = (c0 + k == 0) ? v[k] : f4_add(t, v[k]);
+      }
+      st4_wtg<3>(out + 4 * e, t);
     }
     return;
   }
   if ((int)blockIdx.z == B.n) {
-    const int r = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * 4 + (int)(threadIdx.x >> 6);
+    // (the wave index through readfirstlane: the row is wave-uniform, arch_body.hpp)
+    const int r = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * 4 +
+                  __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (r < arch_rows) arch_softmax_bwd_row(A, r, threadIdx.x & 63);
     return;
   }

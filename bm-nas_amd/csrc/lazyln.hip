@@ -320,6 +320,77 @@ __global__ __launch_bounds__(256) void mixsum_pair_bwd_lazy_k(
 //   g = rstd (gy w - m1 - xhat m2)          LayerNorm input gradient (= gradient of the mix output and of the residual)
 // and the mix backward (mix_bwd4).  BatchNorm reductions: registers over the chunk, LDS over the 4 sample
 // lanes, one atomic pair per channel per workgroup.
+//
+// Everything one trip of the sample loop reads from memory, REQUESTED TOGETHER (lnp_issue) before the first wait: the
+// launch costs the dependent round trips between its first load and its last store, and it has one — behind the
+// scalar fetch of the argument block.  NPL = ceil((n0 + n1) / 64) in 1 .. 4: the sample's partial pairs are NPL
+// unconditional loads per lane from clamped addresses, masked when they are added (in the order t = col, col + 64, ...
+// of the loop they replace).  NPL = 0 (more than 256 pairs): the loop itself, whose sums take pp[0]'s place.
+template <int NPL>
+struct LnpTrip {
+  float2 pp[NPL > 0 ? NPL : 1];
+  float2 st;                                                  // mean | rstd
+  float4 gy, pre, ua, ug, uf, x, y, p1, oldr, oldx, oldy;
+  int64_t e, ub;
+  bool on;
+};
+
+template <int NPL>
+__device__ __forceinline__ LnpTrip<NPL> lnp_issue(
+    int s0, int s_end, int sl, int col, bool active, int r, int cl4, int M, int C, int L,
+    const float* __restrict__ gy, const float* __restrict__ pre, const float* __restrict__ stats,
+    const float* __restrict__ lnp0, int n0, const float* __restrict__ lnp1, int n1, const float* oldr_p,
+    const float* oldx_p, const float* oldy_p, const float* __restrict__ x, const float* __restrict__ y,
+    const float* __restrict__ p1, const float* __restrict__ U) {
+  LnpTrip<NPL> t;
+  const int s_raw = s0 + sl;
+  t.on = active && s_raw < s_end;
+  const int s = s_raw < s_end ? s_raw : s_end - 1;            // clamped (wave-uniform)
+  const int np = n0 + n1;
+  if constexpr (NPL > 0) {
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+      const int t0 = col + 64 * k;
+      const int tc = t0 < np ? t0 : np - 1;                   // (np >= 1, host-checked)
+      const float2* src = tc < n0 ? reinterpret_cast<const float2*>(lnp0) + ((int64_t)s * n0 + tc)
+                                  : reinterpret_cast<const float2*>(lnp1) + ((int64_t)s * n1 + (tc - n0));
+      t.pp[k] = *src;
+    }
+  } else {
+    float q1 = 0.f, q2 = 0.f;
+#pragma unroll 1
+    for (int u0 = 0; u0 < np; u0 += 64) {                     // (uniform trip count; the last trip is ragged)
+      const int u = u0 + col;
+      const int uc = u < np ? u : np - 1;
+      const float2 pp = uc < n0 ? reinterpret_cast<const float2*>(lnp0)[(int64_t)s * n0 + uc]
+                                : reinterpret_cast<const float2*>(lnp1)[(int64_t)s * n1 + (uc - n0)];
+      if (u < np) {
+        q1 += pp.x;
+        q2 += pp.y;
+      }
+    }
+    t.pp[0] = make_float2(q1, q2);
+  }
+  t.st = make_float2(stats[2 * s], stats[2 * s + 1]);
+  t.e = ((int64_t)s * cl4 + r) * 4;
+  t.ub = ((int64_t)s * M) * L + (int64_t)r * 4;
+  t.gy = ld4(gy + t.e);
+  t.pre = ld4(pre + t.e);
+  t.ua = ld4(U + t.ub);
+  t.ug = ld4(U + t.ub + (int64_t)C * L);
+  t.uf = ld4(U + t.ub + (int64_t)2 * C * L);
+  t.x = ld4(x + t.e);
+  t.y = ld4(y + t.e);
+  t.p1 = ld4(p1 + t.e);
+  // the destinations' old values, unconditionally: an absent one reads gy again and is masked out where it is used (a
+  // load under `if` is a branch whose join waits for vmcnt(0), mixsum_pair_bwd_lazy_k)
+  t.oldr = ld4(oldr_p + t.e);
+  t.oldx = ld4(oldx_p + t.e);
+  t.oldy = ld4(oldy_p + t.e);
+  return t;
+}
+
+template <int NPL>
 __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
     const float* __restrict__ gy, const float* __restrict__ pre, const float* __restrict__ ln_w,
     const float* __restrict__ stats, const float* __restrict__ lnp0, int n0, const float* __restrict__ lnp1, int n1,
@@ -337,10 +408,6 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
   const bool active = r0 < cl4;
   const int r = active ? r0 : cl4 - 1;
   const int c = r / l4n;
-  const float g0 = gamma[0], g2 = gamma[2], g3 = gamma[3];
-  const DropRt rglu = drop_begin(dglu), rfc = drop_begin(dfc);
-  const ChanBn<3> bn = chan_load<3>(chan, M, C, c);
-  const float4 lw = ld4(ln_w + (int64_t)r * 4);
   const float inv_d = 1.f / (float)(cl4 * 4);
   float dgam[4] = {0.f, 0.f, 0.f, 0.f};
   float sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
@@ -348,48 +415,69 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
   int s_end = s_beg + chunk;
   if (s_end > b) s_end = b;
   const int np = n0 + n1;
-  for (int s0 = s_beg; s0 < s_end; s0 += 4) {
-    const int s_raw = s0 + sl;
-    const bool on = active && s_raw < s_end;
-    const int s = s_raw < s_end ? s_raw : s_end - 1;          // clamped (wave-uniform)
-    // the sample's partial sums first, then every operand: one round trip
+  const bool use_r = acc_resid != 0, use_x = dx != nullptr && (acc_mask & 1u), use_y = dy != nullptr && (acc_mask & 2u);
+  const float* oldr_p = use_r ? dresid : gy;
+  const float* oldx_p = use_x ? dx : gy;
+  const float* oldy_p = use_y ? dy : gy;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  // the first trip's loads and the per-lane constants: one batch, nothing waited for yet
+  // (the loop form, NPL = 0, has a round trip of its own for the pairs anyway: it requests each trip at the trip's top)
+  LnpTrip<NPL> t;
+  if constexpr (NPL > 0)
+    t = lnp_issue<NPL>(s_beg, s_end, sl, col, active, r, cl4, M, C, L, gy, pre, stats, lnp0, n0, lnp1, n1, oldr_p,
+                       oldx_p, oldy_p, x, y, p1, U);
+  const float4 lw = ld4(ln_w + (int64_t)r * 4);
+  const ChanBn<3> bn = chan_load<3>(chan, M, C, c);
+  // only now what hangs off a SECOND scalar round trip (gamma and the dropout step counters sit behind pointers of the
+  // argument block, node_mix_pre_fwd_k): it runs beside the vector loads instead of in front of them
+  __builtin_amdgcn_sched_barrier(0);
+  const float g0 = gamma[0], g2 = gamma[2], g3 = gamma[3];
+  const DropRt rglu = drop_begin(dglu), rfc = drop_begin(dfc);
+  for (int s0 = s_beg;;) {
+    if constexpr (NPL == 0)
+      t = lnp_issue<NPL>(s0, s_end, sl, col, active, r, cl4, M, C, L, gy, pre, stats, lnp0, n0, lnp1, n1, oldr_p,
+                         oldx_p, oldy_p, x, y, p1, U);
     float q1 = 0.f, q2 = 0.f;
-    for (int t = col; t < np; t += 64) {
-      const float2 pp = t < n0 ? reinterpret_cast<const float2*>(lnp0)[(int64_t)s * n0 + t]
-                               : reinterpret_cast<const float2*>(lnp1)[(int64_t)s * n1 + (t - n0)];
-      q1 += pp.x;
-      q2 += pp.y;
+    if constexpr (NPL > 0) {
+#pragma unroll
+      for (int k = 0; k < NPL; ++k) {
+        if (col + 64 * k < np) {
+          q1 += t.pp[k].x;
+          q2 += t.pp[k].y;
+        }
+      }
+    } else {
+      q1 = t.pp[0].x;
+      q2 = t.pp[0].y;
     }
-    const float mean = stats[2 * s], rstd = stats[2 * s + 1];
-    const int64_t e = ((int64_t)s * cl4 + r) * 4;
-    const int64_t ub = ((int64_t)s * M) * L + (int64_t)r * 4;
-    const float4 gyv = ld4(gy + e), prv = ld4(pre + e);
-    const float4 ua = ld4(U + ub), ug = ld4(U + ub + (int64_t)C * L), uf = ld4(U + ub + (int64_t)2 * C * L);
-    const float4 xv = ld4(x + e), yv = ld4(y + e), pv = ld4(p1 + e);
-    float4 oldr = make_float4(0.f, 0.f, 0.f, 0.f), oldx = oldr, oldy = oldr;
-    if (acc_resid) oldr = ld4(dresid + e);
-    if (dx != nullptr && (acc_mask & 1u)) oldx = ld4(dx + e);
-    if (dy != nullptr && (acc_mask & 2u)) oldy = ld4(dy + e);
+    const float mean = t.st.x, rstd = t.st.y;
     const float m1 = wave_sum(q1) * inv_d, m2 = wave_sum(q2) * inv_d;
     STAMP(3, blockIdx.y * gridDim.x + blockIdx.x, 1);
-    if (on) {
-      const float4 xh = make_float4((prv.x - mean) * rstd, (prv.y - mean) * rstd, (prv.z - mean) * rstd,
-                                    (prv.w - mean) * rstd);
+    if (t.on) {
+      const int64_t e = t.e, ub = t.ub;
+      const float4 xh = make_float4((t.pre.x - mean) * rstd, (t.pre.y - mean) * rstd, (t.pre.z - mean) * rstd,
+                                    (t.pre.w - mean) * rstd);
       float4 gv;
-      gv.x = rstd * (gyv.x * lw.x - m1 - xh.x * m2);
-      gv.y = rstd * (gyv.y * lw.y - m1 - xh.y * m2);
-      gv.z = rstd * (gyv.z * lw.z - m1 - xh.z * m2);
-      gv.w = rstd * (gyv.w * lw.w - m1 - xh.w * m2);
+      gv.x = rstd * (t.gy.x * lw.x - m1 - xh.x * m2);
+      gv.y = rstd * (t.gy.y * lw.y - m1 - xh.y * m2);
+      gv.z = rstd * (t.gy.z * lw.z - m1 - xh.z * m2);
+      gv.w = rstd * (t.gy.w * lw.w - m1 - xh.w * m2);
       if (gbuf != nullptr) st4_w0<6>(gbuf + e, gv);
-      if (dresid != nullptr) st4_w0<6>(dresid + e, f4_add(gv, oldr));
+      if (dresid != nullptr) st4_w0<6>(dresid + e, f4_add(gv, use_r ? t.oldr : zero4));
       const float4 m2d = drop_mult4(rglu, (uint64_t)e), m3d = drop_mult4(rfc, (uint64_t)e);
       float4 da, dg, df;
-      mix_bwd4<kMixAll>(g2, g3, gv, f4_add(xv, yv), pv, ua, ug, uf, m2d, m3d, bn, dgam, da, dg, df, sw, sb);
+      mix_bwd4<kMixAll>(g2, g3, gv, f4_add(t.x, t.y), t.p1, t.ua, t.ug, t.uf, m2d, m3d, bn, dgam, da, dg, df, sw, sb);
       st4_w0<6>(dV + ub, da);
       st4_w0<6>(dV + ub + (int64_t)C * L, dg);
       st4_w0<6>(dV + ub + (int64_t)2 * C * L, df);
-      mix_dxy_store([](float* p, float4 v) { st4_w0<6>(p, v); }, dx, dy, e, gv, g0, oldx, oldy);
+      mix_dxy_store([](float* p, float4 v) { st4_w0<6>(p, v); }, dx, dy, e, gv, g0, use_x ? t.oldx : zero4,
+                    use_y ? t.oldy : zero4);
     }
+    s0 += 4;
+    if (s0 >= s_end) break;                                   // (b <= 256: chunk = 4, one trip)
+    if constexpr (NPL > 0)
+      t = lnp_issue<NPL>(s0, s_end, sl, col, active, r, cl4, M, C, L, gy, pre, stats, lnp0, n0, lnp1, n1, oldr_p,
+                         oldx_p, oldy_p, x, y, p1, U);
   }
   STAMP(3, blockIdx.y * gridDim.x + blockIdx.x, 2);
   float cs[6];
@@ -597,10 +685,21 @@ extern "C" int bmnas_node_mix_lnp_bwd(const float* g, const float* pre, const fl
   int chunk = 4;
   while ((b + chunk - 1) / chunk > 64) chunk += 4;
   dim3 grid((cl4 + 63) / 64, (b + chunk - 1) / chunk);
-  hipLaunchKernelGGL(node_mix_lnp_bwd_k, grid, dim3(256), 0, (hipStream_t)stream, g, pre, ln_w, stats, lnp0, n0,
-                     lnp1, n1, g_in, dresid, accumulate_resid, x, y, p1, U, chan, gamma, dgamma, dgamma_shards,
-                     dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, bn_part, b, C, L, chunk,
-                     to_cfg(drop_glu), to_cfg(drop_fc));
+  // partial pairs per lane, a compile-time count up to 4 (256 pairs); 0 = the loop form above that
+  const int npl = (n0 + n1 + 63) / 64;
+#define CALL(N)                                                                                                     \
+  hipLaunchKernelGGL(node_mix_lnp_bwd_k<N>, grid, dim3(256), 0, (hipStream_t)stream, g, pre, ln_w, stats, lnp0, n0, \
+                     lnp1, n1, g_in, dresid, accumulate_resid, x, y, p1, U, chan, gamma, dgamma, dgamma_shards,     \
+                     dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, bn_part, b, C, L, chunk,            \
+                     to_cfg(drop_glu), to_cfg(drop_fc))
+  switch (npl) {
+    case 1: CALL(1); break;
+    case 2: CALL(2); break;
+    case 3: CALL(3); break;
+    case 4: CALL(4); break;
+    default: CALL(0); break;
+  }
+#undef CALL
   BMNAS_CHECK_LAUNCH();
   if (bn_part != nullptr)      // rows in order -> bn_grad (6 C floats per row; C % 16 == 0)
     return bmnas_sum_chunks(bn_part, bn_grad, (int)grid.y, (int64_t)6 * C, stream);

@@ -215,55 +215,91 @@ __global__ __launch_bounds__(256) void mixsum_pair_bwd_x_k(PtrsIn xs, PtrsOut dx
                                                            MoreG X, int64_t n4) {
   __shared__ float red[4 * (NIN + 1)];
   float wj[NIN], wx[NX][NIN], part[NIN + 1];
+  // one trip's operands.  Every load unconditional (an absent optional operand reads gz again and is masked out): a
+  // load under `if` is a branch whose join waits for vmcnt(0) — gz, gz2 and gh were three dependent round trips
+  // before the operands
+  struct Trip {
+    float4 z4, z2v, h4, ghv, gx[NX], v[NIN];
+  };
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto issue = [&](int64_t i) {
+    Trip t;
+    t.z4 = reinterpret_cast<const float4*>(gz)[i];
+    t.z2v = reinterpret_cast<const float4*>(gz2 != nullptr ? gz2 : gz)[i];
+    t.h4 = zero4;
+    if constexpr (DOTS) t.h4 = reinterpret_cast<const float4*>(h)[i];
+    t.ghv = reinterpret_cast<const float4*>(gh != nullptr ? gh : gz)[i];
 #pragma unroll
-  for (int j = 0; j < NIN; ++j) {
-    wj[j] = w[j * w_stride];
-    part[j] = 0.f;
-#pragma unroll
-    for (int t = 0; t < NX; ++t) wx[t][j] = X.w[t][j * w_stride];
-  }
-  part[NIN] = 0.f;
-  const float s2 = w2[0] + w2[w2_stride];
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-    // every load unconditional (an absent optional operand reads gz again and is masked out): a load under `if` is
-    // a branch whose join waits for vmcnt(0) — gz, gz2 and gh were three dependent round trips before the operands
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 z4 = reinterpret_cast<const float4*>(gz)[i];
-    const float4 z2v = reinterpret_cast<const float4*>(gz2 != nullptr ? gz2 : gz)[i];
-    float4 h4 = zero4;
-    if constexpr (DOTS) h4 = reinterpret_cast<const float4*>(h)[i];
-    const float4 ghv = reinterpret_cast<const float4*>(gh != nullptr ? gh : gz)[i];
-    float4 gx[NX];
-#pragma unroll
-    for (int t = 0; t < NX; ++t) gx[t] = reinterpret_cast<const float4*>(X.g[t])[i];
-    float4 v[NIN];
+    for (int k = 0; k < NX; ++k) t.gx[k] = reinterpret_cast<const float4*>(X.g[k])[i];
 #pragma unroll
     for (int j = 0; j < NIN; ++j) {
-      if constexpr (DOTS) v[j] = reinterpret_cast<const float4*>(xs.p[j])[i];
-      else v[j] = zero4;
+      if constexpr (DOTS) t.v[j] = reinterpret_cast<const float4*>(xs.p[j])[i];
+      else t.v[j] = zero4;
     }
-    z4 = f4_add(z4, gz2 != nullptr ? z2v : zero4);
-    const float4 g4 = f4_add(f4_scale(z4, s2), gh != nullptr ? ghv : zero4);
+    return t;
+  };
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool live = i < n4;
+  auto weights = [&]() {
 #pragma unroll
-    for (int j = 0; j < NIN; ++j) part[j] += f4_dot(g4, v[j]);
-    part[NIN] += f4_dot(z4, h4);
+    for (int j = 0; j < NIN; ++j) {
+      wj[j] = w[j * w_stride];
+#pragma unroll
+      for (int k = 0; k < NX; ++k) wx[k][j] = X.w[k][j * w_stride];
+    }
+    return w2[0] + w2[w2_stride];
+  };
+#pragma unroll
+  for (int j = 0; j <= NIN; ++j) part[j] = 0.f;
+  // on: false for a lane without a first trip — it adds nothing and stores nothing, but its arithmetic is not put
+  // under a branch (the compiler sinks a load into the branch that holds its only use)
+  auto finish = [&](const Trip& t, int64_t i, float s2, bool on) {
+    const float4 z4 = f4_add(t.z4, gz2 != nullptr ? t.z2v : zero4);
+    const float4 g4 = f4_add(f4_scale(z4, s2), gh != nullptr ? t.ghv : zero4);
+#pragma unroll
+    for (int j = 0; j < NIN; ++j) {
+      const float dj = f4_dot(g4, t.v[j]);
+      part[j] += on ? dj : 0.f;
+    }
+    const float dh = f4_dot(z4, t.h4);
+    part[NIN] += on ? dh : 0.f;
 #pragma unroll
     for (int j = 0; j < NIN; ++j) {
       float* d = dxs.p[j];
-      if (d == nullptr) continue;
+      if (d == nullptr || !on) continue;
       float4 r = f4_scale(g4, wj[j]);
 #pragma unroll
-      for (int t = 0; t < NX; ++t) {
-        r.x = fmaf(wx[t][j], gx[t].x, r.x);
-        r.y = fmaf(wx[t][j], gx[t].y, r.y);
-        r.z = fmaf(wx[t][j], gx[t].z, r.z);
-        r.w = fmaf(wx[t][j], gx[t].w, r.w);
+      for (int k = 0; k < NX; ++k) {
+        r.x = fmaf(wx[k][j], t.gx[k].x, r.x);
+        r.y = fmaf(wx[k][j], t.gx[k].y, r.y);
+        r.z = fmaf(wx[k][j], t.gx[k].z, r.z);
+        r.w = fmaf(wx[k][j], t.gx[k].w, r.w);
       }
       if (acc_mask & (1u << j)) r = f4_add(r, reinterpret_cast<float4*>(d)[i]);
       st4_w0<10>(d + 4 * i, r);
     }
+  };
+  // The edge weights sit behind pointers of the argument block.  Read in front of the loop they were a second scalar
+  // round trip that every vector load waited for: the first trip's operands are requested BEFORE them (a lane without
+  // a first trip repeats the last element, n4 >= 1: every lane reaches the barrier below).  pin4 (common.hpp) keeps
+  // the first trip's arithmetic — and with it the waits for the operands — behind the weights' loads.
+  Trip t = issue(live ? i : n4 - 1);
+  __builtin_amdgcn_sched_barrier(0);
+  const float s2 = weights();
+  __builtin_amdgcn_sched_barrier(0);
+  pin4(t.z4);
+  pin4(t.z2v);
+  pin4(t.ghv);
+  if constexpr (DOTS) pin4(t.h4);
+#pragma unroll
+  for (int k = 0; k < NX; ++k) pin4(t.gx[k]);
+  if constexpr (DOTS) {
+#pragma unroll
+    for (int j = 0; j < NIN; ++j) pin4(t.v[j]);
   }
+  finish(t, i, s2, live);
+  for (i += stride; i < n4; i += stride) finish(issue(i), i, s2, true);   // (grids above 2048 workgroups' worth only)
   if constexpr (!DOTS) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
