@@ -269,7 +269,9 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf
 // reductions over a row = shuffles inside a 16-lane group), then the tile:  per group of 16 samples
 // dfeat^T = W^T dl^T on the matrix cores with k on the accumulator rows (float4 along k per sample:
 // LayerNorm backward and the state-gradient store are coalesced), and dW = dl^T feat accumulated
-// over the SG groups, with feat recomputed in B-operand layout straight from the states.
+// over the SG groups, with feat handed from the first product's lanes to the second's through a per-wave LDS image
+// (never stored to memory, the states fetched once).  Each product requests all its LDS operands, then runs its MFMAs
+// without a wait or a branch between them (profiles/r22_head_bwd_batches.txt).
 // OT = class tiles of 16 the kernel is built for (O <= 16 OT).
 // CR = 0: modes 0 - 2 as above.  CR = 1: BCEWithLogits with per-class weight / pos_weight, CR = 2: CrossEntropy with
 // class weights, label smoothing and ignore_index, both with reduction mean or sum (the formulas: bmnas_hip.h,
@@ -283,8 +285,20 @@ __device__ __forceinline__ float group16_max(float v) { return row16_max(v); }
 template <int OT, int SG, bool LZ, int CR = 0>
 __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
   constexpr int kSteps = 4 * OT, kRows = 16 * SG;
-  __shared__ float dl_s[kRows][16 * OT + 4];
-  __shared__ float ms[LZ ? 6 : 4][kRows];         // m1, m2, mean, rstd (, node mean, node rstd)
+  // dl in the two layouts its products read it in, so that one lane's operands of a product are contiguous and leave as
+  // ds_read_b128, every one of them requested before the product's first MFMA (one wait per product instead of one per MFMA):
+  //   dl_a[row][(o & 3) kSteps + (o >> 2)]   GEMM 1: lane (lo, h) takes dl[row = lo][o = 4 t + h], t = 0 .. kSteps - 1;
+  //                                          row stride = 4 (mod 32) floats: the 16 rows of a k-slot h cover all 64 banks
+  //   dl_b[row >> 2][o][row & 3]             GEMM 2: lane (lo, h) takes dl[row = 4 h + r][o = 16 t + lo], r = 0 .. 3;
+  //                                          lanes lo are 16 bytes apart
+  // Both hold zeros past O and in rows past b: the products run all OT class tiles without a range test.
+  constexpr int kDlA = 4 * kSteps + 4, kMs = LZ ? 8 : 4;
+  __shared__ __attribute__((aligned(16))) float dl_a[kRows][kDlA];
+  __shared__ __attribute__((aligned(16))) float dl_b[kRows / 4][16 * OT][4];
+  __shared__ __attribute__((aligned(16))) float ms[kRows][kMs];  // per row: m1, m2, mean, rstd (, node mean, node rstd, -, -)
+  // feat of a wave's (16 samples x 16 k) block per sample group: written as GEMM 1's lanes hold it (sample lo, k 4h + r:
+  // one float4), read as GEMM 2 takes it (sample 4h + r, k lo).  Row stride 20: a read's four k-slots are 16 banks apart.
+  __shared__ __attribute__((aligned(16))) float ft_s[4][SG][16][20];
   __shared__ float lnp_s[LZ ? 4 : 1][LZ ? kRows : 1][2];
   __shared__ float loss_s[4];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -300,7 +314,6 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
   const int k0 = (vt ? kt : nkt - 1) * 16;
   const int q = k0 / a.CL;                                      // a tile never straddles two states
   const int kin = k0 - q * a.CL;
-  const int osteps = (a.O + 3) / 4, otiles = (a.O + 15) / 16;
   float wv[kSteps];
 #pragma unroll
   for (int t = 0; t < kSteps; ++t) {
@@ -308,12 +321,10 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
     wv[t] = a.W[(int64_t)(o < a.O ? o : a.O - 1) * a.D + k0 + lo];     // clamped address, selected below
   }
   const float4 lw = ld4(a.ln_w + k0 + 4 * h), lb = ld4(a.ln_b + k0 + 4 * h);
-  const float lwk = a.ln_w[k0 + lo], lbk = a.ln_b[k0 + lo];
   // the workgroup's source q through select chains (common.hpp pick_ptr), never a.src.p[q]: a run-time index into the
   // argument block is a memory load of the POINTER and a wait in front of every operand load it feeds
   const float* const srcq = pick_ptr(a.src.p, q);
   float4 nw4 = make_float4(1.f, 1.f, 1.f, 1.f), nb4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float nwk = 1.f, nbk = 0.f;
   const float* nstq = nullptr;
   if (LZ) {                                                     // (q: uniform over the workgroup, CL % 64 == 0)
     const float* const nwq_p = pick_ptr(z.nw, q);
@@ -321,20 +332,13 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
     nstq = pick_ptr(z.nstats, q);
     nw4 = ld4(nwq_p + kin + 4 * h);
     nb4 = ld4(nbq_p + kin + 4 * h);
-    nwk = nwq_p[kin + lo];
-    nbk = nbq_p[kin + lo];
   }
+  // (the states are fetched ONCE, in GEMM 1's layout; GEMM 2 takes the same block through ft_s)
   float4 x[SG];
-  float xr[SG][4];
 #pragma unroll
   for (int g = 0; g < SG; ++g) {
     const int s = s0 + 16 * g + lo;
     x[g] = ld4(srcq + (int64_t)(s < a.b ? s : a.b - 1) * a.CL + kin + 4 * h);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int sr = s0 + 16 * g + 4 * h + r;
-      xr[g][r] = srcq[(int64_t)(sr < a.b ? sr : a.b - 1) * a.CL + kin + lo];
-    }
   }
   // ---- prologue: thread = (row tid / 16 of sample group g, class stripe lo + 16 u)
   {
@@ -500,22 +504,17 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
 #pragma unroll
       for (int u = 0; u < OT; ++u) {
         if (!vsp) dl[u] = 0.f;
-        const int o = lo + 16 * u;
-        if (o < a.O) dl_s[rr][o] = dl[u];
+        const int o = lo + 16 * u;                              // (dl[u] is zero past O in every mode)
+        dl_a[rr][(o & 3) * kSteps + (o >> 2)] = dl[u];
+        dl_b[rr >> 2][o][rr & 3] = dl[u];
         p1 += dl[u] * aa[g][u];
         p2 += dl[u] * bb[g][u];
       }
       p1 = group16_sum(p1);
       p2 = group16_sum(p2);
       if (lo == 0) {
-        ms[0][rr] = p1 * invD;
-        ms[1][rr] = p2 * invD;
-        ms[2][rr] = st_mean[g];
-        ms[3][rr] = st_rstd[g];
-        if (LZ) {
-          ms[4][rr] = nd_mean[g];
-          ms[5][rr] = nd_rstd[g];
-        }
+        *reinterpret_cast<float4*>(&ms[rr][0]) = make_float4(p1 * invD, p2 * invD, st_mean[g], st_rstd[g]);
+        if (LZ) *reinterpret_cast<float4*>(&ms[rr][kMs - 4]) = make_float4(nd_mean[g], nd_rstd[g], 0.f, 0.f);
       }
       loss_acc += vsp ? row_loss : 0.f;
     }
@@ -540,7 +539,7 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
   if (a.part != nullptr && blockIdx.x == 0 && (int)threadIdx.x < a.O) {   // dbias partial of this chunk
     float t = 0.f;
 #pragma unroll
-    for (int rr = 0; rr < kRows; ++rr) t += dl_s[rr][threadIdx.x];
+    for (int rr = 0; rr < kRows; ++rr) t += dl_a[rr][(threadIdx.x & 3) * kSteps + (threadIdx.x >> 2)];
     a.part[((int64_t)chunk * (a.O + 3) + a.O + 2) * a.D + threadIdx.x] = t;
   }
   STAMP(5, blockIdx.y * gridDim.x + blockIdx.x, 1);
@@ -550,43 +549,77 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
   const float wq[4] = {lw.x, lw.y, lw.z, lw.w}, bq[4] = {lb.x, lb.y, lb.z, lb.w};
   const float nwq[4] = {nw4.x, nw4.y, nw4.z, nw4.w}, nbq[4] = {nb4.x, nb4.y, nb4.z, nb4.w};
   float gw[4] = {0.f, 0.f, 0.f, 0.f}, gb[4] = {0.f, 0.f, 0.f, 0.f};
-  float fr[SG][4];
+  // GEMM 1: D[k = 4h + r][s = lo] = sum_o W[o][k0 + 4h + r] dl[s][o].  Every LDS operand of the product — dl of all class
+  // steps and the per-sample values, of all sample groups — is requested first (float4 reads, one wait); the steps then run
+  // without a range test (W is selected to zero past O, dl IS zero there: the steps past O add zeros) with the sample
+  // groups' accumulators taking turns, each in its own order t = 0, 1, ...
+  float wz[kSteps];
+#pragma unroll
+  for (int t = 0; t < kSteps; ++t) wz[t] = (4 * t + h < a.O) ? wv[t] : 0.f;
+  float4 mv[SG], nv[SG], da[SG][OT];
 #pragma unroll
   for (int g = 0; g < SG; ++g) {
     const int rl = 16 * g + lo;
-    const int s = s0 + rl;
-    const bool vs = s < a.b;
-    const float m1 = ms[0][rl], m2 = ms[1][rl], mean = ms[2][rl], rstd = ms[3][rl];
-    // GEMM 1: D[k = 4h + r][s = lo] = sum_o W[o][k0 + 4h + r] dl[s][o]
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    mv[g] = *reinterpret_cast<const float4*>(&ms[rl][0]);
+    nv[g] = *reinterpret_cast<const float4*>(&ms[rl][kMs - 4]);
 #pragma unroll
-    for (int t = 0; t < kSteps; ++t) {
-      if (t < osteps) {                                         // uniform
-        const int o = 4 * t + h;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(o < a.O ? wv[t] : 0.f, dl_s[rl][o < a.O ? o : a.O - 1], acc,
-                                                   0, 0, 0);
-      }
-    }
+    for (int j = 0; j < OT; ++j) da[g][j] = *reinterpret_cast<const float4*>(&dl_a[rl][h * kSteps + 4 * j]);
+  }
+#pragma unroll
+  for (int g = 0; g < SG; ++g) {                                  // (common.hpp pin4: the batch stays in front of the MFMAs)
+#pragma unroll
+    for (int j = 0; j < OT; ++j) pin4(da[g][j]);
+    pin4(mv[g]);
+    if (LZ) pin4(nv[g]);
+  }
+  f32x4 acc1[SG];
+#pragma unroll
+  for (int g = 0; g < SG; ++g) acc1[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < OT; ++j) {
+#pragma unroll
+    for (int g = 0; g < SG; ++g) acc1[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[4 * j], da[g][j].x, acc1[g], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < SG; ++g) acc1[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[4 * j + 1], da[g][j].y, acc1[g], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < SG; ++g) acc1[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[4 * j + 2], da[g][j].z, acc1[g], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < SG; ++g) acc1[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[4 * j + 3], da[g][j].w, acc1[g], 0, 0, 0);
+  }
+  float* const d = pick_ptr(a.dsrc, q);
+  const bool dst = d != nullptr && !(a.probe & 2), dacc = (a.acc_mask & (1u << q)) != 0;      // uniform
+  float4 dx4[SG];
+#pragma unroll
+  for (int g = 0; g < SG; ++g) {
+    const int rl = 16 * g + lo;
+    const bool vs = s0 + rl < a.b;
+    const f32x4 acc = acc1[g];
+    const float m1 = mv[g].x, m2 = mv[g].y, mean = mv[g].z, rstd = mv[g].w;
     float xq[4] = {x[g].x, x[g].y, x[g].z, x[g].w};
     float xhn[4] = {0.f, 0.f, 0.f, 0.f};
     if (LZ) {                                                   // the state itself: LayerNorm_node(pre)
-      const float nmean = ms[4][rl], nrstd = ms[5][rl];
+      const float nmean = nv[g].x, nrstd = nv[g].y;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         xhn[r] = (xq[r] - nmean) * nrstd;
         xq[r] = xhn[r] * nwq[r] + nbq[r];
       }
     }
-    float dx[4];
+    float dx[4], ff[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float xh = (xq[r] - mean) * rstd;
-      const bool on = (xh * wq[r] + bq[r]) > 0.f;
+      const float pre = xh * wq[r] + bq[r];
+      const bool on = pre > 0.f;
       const float gy = (on && vs) ? acc[r] : 0.f;               // gradient at the LayerNorm output
       dx[r] = rstd * (gy * wq[r] - m1 - xh * m2);
       gw[r] += gy * xh;
       gb[r] += gy;
+      ff[r] = vs ? fmaxf(pre, 0.f) : 0.f;                       // feat = relu(LayerNorm(.)), zero in rows past b
     }
+    // feat for GEMM 2, from what this lane holds: (sample lo, k 4h + r) here, (sample 4h + r, k lo) there
+    *reinterpret_cast<float4*>(&ft_s[wave][g][lo][4 * h]) = make_float4(ff[0], ff[1], ff[2], ff[3]);
+    dx4[g] = make_float4(dx[0], dx[1], dx[2], dx[3]);
     if (LZ) {
       // this wave's 16 k of the node LayerNorm backward's two sums, per sample: S(gy w), S(gy w xhat)
       float q1 = 0.f, q2 = 0.f;
@@ -603,21 +636,18 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
         lnp_s[wave][rl][1] = q2;
       }
     }
-    float* d = pick_ptr(a.dsrc, q);
-    if (d != nullptr && vs && !(a.probe & 2)) {
-      float* pp = d + (int64_t)s * a.CL + kin + 4 * h;
-      float4 o4 = make_float4(dx[0], dx[1], dx[2], dx[3]);
-      if (a.acc_mask & (1u << q)) o4 = f4_add(o4, ld4(pp));
-      st4_w0<5>(pp, o4);
-    }
-    // feat in (s = 4h + r, k = lo) layout for GEMM 2, recomputed from the state (never stored)
+  }
+  // the state gradients, behind both groups' arithmetic.  (The old value of an accumulating call is loaded INSIDE the
+  // store's condition: a load that some path leaves unwaited makes the compiler wait for every outstanding memory
+  // operation at the next barrier — these write-through stores included.)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rl2 = 16 * g + 4 * h + r;
-      float xv2 = xr[g][r];
-      if (LZ) xv2 = (xv2 - ms[4][rl2]) * ms[5][rl2] * nwk + nbk;
-      const float pre = (xv2 - ms[2][rl2]) * ms[3][rl2] * lwk + lbk;
-      fr[g][r] = (s0 + rl2 < a.b) ? fmaxf(pre, 0.f) : 0.f;
+  for (int g = 0; g < SG; ++g) {
+    const int s = s0 + 16 * g + lo;
+    if (dst && s < a.b) {
+      float* pp = d + (int64_t)s * a.CL + kin + 4 * h;
+      float4 o4 = dx4[g];
+      if (dacc) o4 = f4_add(o4, ld4(pp));
+      st4_w0<5>(pp, o4);
     }
   }
   STAMP(5, blockIdx.y * gridDim.x + blockIdx.x, 2);
@@ -647,25 +677,49 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
     st4_wt(part + (int64_t)a.O * a.D + k0 + 4 * h, make_float4(gw[0], gw[1], gw[2], gw[3]));
     st4_wt(part + (int64_t)(a.O + 1) * a.D + k0 + 4 * h, make_float4(gb[0], gb[1], gb[2], gb[3]));
   }
-  // GEMM 2: dW[o = 16 t + 4h + r][k0 + lo] = sum_s dl[s][o] feat[s][k0 + lo]
+  // GEMM 2: dW[o = 16 t + lo][k0 + 4h + r] = sum_s feat[s][k0 + 4h + r] dl[s][o] — feat on the row operand, dl on the
+  // column operand: an accumulator holds four consecutive k of one class and leaves as one 16-byte store (a plain one:
+  // written through, the epilogue and the launch after this one each ran 0.3 us longer and the step did not move).
+  // Both operands of all class tiles are requested first (feat back from this wave's ft_s, dl as float4 over r); the class
+  // tiles' accumulators then take turns, each summing its samples in the order g, r.
+  if (!(a.probe & 1)) {                                           // uniform (timing builds)
+    __builtin_amdgcn_wave_barrier();                              // ft_s: this wave's own writes, in program order
+    float fr[SG][4];
+    float4 db[SG][OT];
 #pragma unroll
-  for (int t = 0; t < OT; ++t) {
-    if (t < otiles && !(a.probe & 1)) {                                           // uniform
-      const int oa = 16 * t + lo;
-      const int oac = oa < a.O ? oa : a.O - 1;
-      f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+    for (int g = 0; g < SG; ++g) {
 #pragma unroll
-      for (int g = 0; g < SG; ++g)
+      for (int r = 0; r < 4; ++r) fr[g][r] = ft_s[wave][g][4 * h + r][lo];
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(oa < a.O ? dl_s[16 * g + 4 * h + r][oac] : 0.f, fr[g][r],
-                                                      acc2, 0, 0, 0);
+      for (int t = 0; t < OT; ++t) db[g][t] = *reinterpret_cast<const float4*>(&dl_b[4 * g + h][16 * t + lo][0]);
+    }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int o = 16 * t + 4 * h + r;
-        // (probe bit 4, timing builds: one store per address — the volume of a design without per-chunk partials)
-        if (o < a.O && (!(a.probe & 4) || chunk == 0)) part[(int64_t)o * a.D + k0 + lo] = acc2[r];
-      }
+    for (int g = 0; g < SG; ++g) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pin1(fr[g][r]);
+#pragma unroll
+      for (int t = 0; t < OT; ++t) pin4(db[g][t]);
+    }
+    f32x4 acc2[OT];
+#pragma unroll
+    for (int t = 0; t < OT; ++t) acc2[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < SG; ++g) {
+#pragma unroll
+      for (int t = 0; t < OT; ++t) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(fr[g][0], db[g][t].x, acc2[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < OT; ++t) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(fr[g][1], db[g][t].y, acc2[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < OT; ++t) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(fr[g][2], db[g][t].z, acc2[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < OT; ++t) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(fr[g][3], db[g][t].w, acc2[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < OT; ++t) {
+      const int o = 16 * t + lo;
+      // (probe bit 4, timing builds: one store per address — the volume of a design without per-chunk partials)
+      if (o < a.O && (!(a.probe & 4) || chunk == 0))
+        st4(part + (int64_t)o * a.D + k0 + 4 * h, make_float4(acc2[t][0], acc2[t][1], acc2[t][2], acc2[t][3]));
     }
   }
   STAMP(5, blockIdx.y * gridDim.x + blockIdx.x, 4);
