@@ -12,6 +12,8 @@
 #pragma once
 #include "common.hpp"
 
+constexpr float kEpsBn = 1e-5f;      // nn.BatchNorm1d's default
+
 struct BnFin {
   const float* stat;       // (shards, M, 2); unused in eval mode
   const float* conv_bias;  // shift of the sums (nullable: 0)
@@ -31,7 +33,7 @@ struct BnFin {
 template <int BS>
 __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ chan, const int M, const int N,
                                             float* sc, float* sh, const bool writer) {
-  constexpr float kEpsBn = 1e-5f, kMom = 0.1f;
+  constexpr float kMom = 0.1f;
   constexpr int kMaxShards = 4;
   if (!f.on) {
     for (int m0 = 4 * (int)threadIdx.x; m0 < M; m0 += 4 * BS) {   // one trip for M <= 4 * BS

@@ -8,6 +8,7 @@
 #include "../../include/bmnas_hip.h"
 #include "arch_body.hpp"
 #include "bn_fin.hpp"
+#include "ln_sample.hpp"
 #include "mix_common.hpp"
 #include "mish.hpp"
 #include <algorithm>
@@ -15,7 +16,6 @@
 
 namespace {
 
-constexpr float kEps = 1e-5f;
 constexpr float kMomentum = 0.1f;
 
 __global__ __launch_bounds__(256) void bn_finalize_k(const float* __restrict__ part, int n_part,
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void bn_finalize_k(const float* __restrict__ p
     }
     m2 = wave_sum(m2);
     const float var = m2 / (float)N;
-    rstd = 1.f / sqrtf(var + kEps);
+    rstd = 1.f / sqrtf(var + kEpsBn);
     if (lane == 0) {
       if (running_mean != nullptr) {
         running_mean[m] = (1.f - kMomentum) * running_mean[m] + kMomentum * mean;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void bn_finalize_k(const float* __restrict__ p
     }
   } else {
     mean = running_mean[m];
-    rstd = 1.f / sqrtf(running_var[m] + kEps);
+    rstd = 1.f / sqrtf(running_var[m] + kEpsBn);
   }
   if (lane == 0) {
     const float scale = bn_w[m] * rstd;
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(BS) void node_mix_ln_fwd_k(
     acc[0] = block_sum_fresh<BS / 64>(acc[0], red6);        // (red6, not red: threads may still be reading the mean)
   }
   const float var = acc[0] * inv_d;
-  const float rstd = 1.f / sqrtf(var + kEps);
+  const float rstd = 1.f / sqrtf(var + kLnEps);
   if (threadIdx.x == 0) {
     stats[2 * smp] = mean;
     stats[2 * smp + 1] = rstd;
@@ -261,10 +261,7 @@ __global__ __launch_bounds__(BS) void node_mix_ln_fwd_k(
   for (int k = 0; k < VPT; ++k) {
     const int r = threadIdx.x + k * BS;
     if (r < cl4) {
-      const float4 w = lw[k], bb = lb[k];
-      st4_wtg<2>(out + ((int64_t)smp * cl4 + r) * 4,
-          make_float4((v[k].x - mean) * rstd * w.x + bb.x, (v[k].y - mean) * rstd * w.y + bb.y,
-                      (v[k].z - mean) * rstd * w.z + bb.z, (v[k].w - mean) * rstd * w.w + bb.w));
+      st4_wtg<2>(out + ((int64_t)smp * cl4 + r) * 4, ln_apply4(v[k], mean, rstd, lw[k], lb[k]));
     }
   }
 }
@@ -456,8 +453,7 @@ __global__ __launch_bounds__(BS) void node_mix_ln_bwd_k(
   for (int k = 0; k < VPT1; ++k) {
     const int idx = threadIdx.x + k * BS;
     const bool on = idx < cl4 && !((probe & 2) && idx >= h4);
-    const float4 pr = xh[k];
-    xh[k] = make_float4((pr.x - mean) * rstd, (pr.y - mean) * rstd, (pr.z - mean) * rstd, (pr.w - mean) * rstd);
+    xh[k] = ln_xhat4(xh[k], mean, rstd);
     s12[0] += on ? f4_hsum(dxh[k]) : 0.f;
     s12[1] += on ? f4_dot(dxh[k], xh[k]) : 0.f;
   }
@@ -476,11 +472,7 @@ __global__ __launch_bounds__(BS) void node_mix_ln_bwd_k(
     if (act) {
       const int64_t e = ((int64_t)smp * cl4 + r) * 4;
       const int64_t ub = ((int64_t)smp * M) * L + (int64_t)r * 4;
-      float4 gv;
-      gv.x = rstd * (dxh[k].x - m1 - xh[k].x * m2);
-      gv.y = rstd * (dxh[k].y - m1 - xh[k].y * m2);
-      gv.z = rstd * (dxh[k].z - m1 - xh[k].z * m2);
-      gv.w = rstd * (dxh[k].w - m1 - xh[k].w * m2);
+      const float4 gv = ln_dx4(dxh[k], xh[k], m1, m2, rstd);
       if (gbuf != nullptr) st4_wtg<2>(gbuf + e, gv);
       if (dresid != nullptr) st4_wtg<2>(dresid + e, f4_add(gv, oldr[k]));
       const float4 m2d = drop_mult4(rglu, (uint64_t)e), m3d = drop_mult4(rfc, (uint64_t)e);
@@ -876,7 +868,7 @@ __global__ __launch_bounds__(BS) void bn_relu_ln_fwd_k(
     acc[0] = block_sum_fresh<BS / 64>(acc[0], red6);        // (red6, not red: threads may still be reading the mean)
   }
   const float var = acc[0] * inv_d;
-  const float rstd = 1.f / sqrtf(var + kEps);
+  const float rstd = 1.f / sqrtf(var + kLnEps);
   if (threadIdx.x == 0) {
     stats[2 * smp] = mean;
     stats[2 * smp + 1] = rstd;
@@ -889,9 +881,7 @@ __global__ __launch_bounds__(BS) void bn_relu_ln_fwd_k(
   for (int k = 0; k < VPT; ++k) {
     const int r = threadIdx.x + k * BS;
     if (r < cl4) {
-      const float4 w = lw[k], bb = lb[k];
-      const float4 y = make_float4((v[k].x - mean) * rstd * w.x + bb.x, (v[k].y - mean) * rstd * w.y + bb.y,
-                                   (v[k].z - mean) * rstd * w.z + bb.z, (v[k].w - mean) * rstd * w.w + bb.w);
+      const float4 y = ln_apply4(v[k], mean, rstd, lw[k], lb[k]);
       const int64_t e = ((int64_t)smp * cl4 + r) * 4;
       st4_wtg<2>(out + e, y);
       if (NP > 0) {
@@ -998,7 +988,7 @@ __global__ __launch_bounds__(BS) void bn_relu_ln_bwd_k(
         gy = f4_add(gy, f4_scale(G, P.w[NP * P.ws]));
         st4_wtg<2>(P.g_full + e, gy);
       }
-      xh[k] = make_float4((x.x - mean) * rstd, (x.y - mean) * rstd, (x.z - mean) * rstd, (x.w - mean) * rstd);
+      xh[k] = ln_xhat4(x, mean, rstd);
       dxh[k] = f4_mul(gy, w);
       s1 += f4_hsum(dxh[k]);
       s2 += f4_dot(dxh[k], xh[k]);
@@ -1007,19 +997,13 @@ __global__ __launch_bounds__(BS) void bn_relu_ln_bwd_k(
   // the LayerNorm backward's two sums and (NP > 0) the mixed-sum weight gradients behind ONE barrier (three
   // reductions with two barriers each before); `red` / `redp` are written once per launch
   constexpr int NWV = BS / 64;
-  const int wv = threadIdx.x >> 6;
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
+  ln_bwd_sums_put<NWV>(s1, s2, red);
   if (NP > 0) {
 #pragma unroll
     for (int j = 0; j < NP + 2; ++j) part[j] = wave_sum(part[j]);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[wv] = s1;
-    red[NWV + wv] = s2;
-    if (NP > 0) {
+    if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-      for (int j = 0; j < NP + 2; ++j) redp[j * NWV + wv] = part[j];
+      for (int j = 0; j < NP + 2; ++j) redp[j * NWV + (threadIdx.x >> 6)] = part[j];
     }
   }
   __syncthreads();
@@ -1035,15 +1019,8 @@ __global__ __launch_bounds__(BS) void bn_relu_ln_bwd_k(
     if (t <= NP) atomicAdd(P.dw + sh + t * P.ws, val);
     else atomicAdd(P.dw2 + sh + (t - NP - 1) * P.w2s, val);
   }
-  const float inv_d = 1.f / (float)(cl4 * 4);
-  float m1 = red[0], m2 = red[NWV];
-#pragma unroll
-  for (int w = 1; w < NWV; ++w) {
-    m1 += red[w];
-    m2 += red[NWV + w];
-  }
-  m1 *= inv_d;
-  m2 *= inv_d;
+  float m1, m2;
+  ln_bwd_sums_get<NWV>(red, 1.f / (float)(cl4 * 4), m1, m2);
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int r = threadIdx.x + k * BS;
@@ -1052,11 +1029,7 @@ __global__ __launch_bounds__(BS) void bn_relu_ln_bwd_k(
     float sw = 0.f, sb = 0.f;
     if (act) {
       const int64_t e = ((int64_t)smp * cl4 + r) * 4;
-      float4 dx;
-      dx.x = rstd * (dxh[k].x - m1 - xh[k].x * m2);
-      dx.y = rstd * (dxh[k].y - m1 - xh[k].y * m2);
-      dx.z = rstd * (dxh[k].z - m1 - xh[k].z * m2);
-      dx.w = rstd * (dxh[k].w - m1 - xh[k].w * m2);
+      const float4 dx = ln_dx4(dxh[k], xh[k], m1, m2, rstd);
       if (dresid != nullptr) st4_wtg<2>(dresid + e, f4_add(dx, old[k]));
       const float mu = chan[c], rs = chan[C + c], scv = chan[2 * C + c], shv = chan[3 * C + c];
       const float4 m = drop_mult4(dr, (uint64_t)e);

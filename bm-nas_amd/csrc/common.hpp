@@ -259,31 +259,11 @@ __device__ __forceinline__ void block_sum_n(float (&v)[N], float* red) {
 }
 
 // As block_sum_n, but only v[0] is handed to every thread; v[1..N-1] are complete on thread 0 only
-// (the other threads skip their LDS reads).
+// (the other threads skip their LDS reads).  block_sum_lead_fresh behind the barrier that lets `red` be reused.
 template <int NW, int N>
 __device__ __forceinline__ void block_sum_lead(float (&v)[N], float* red) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
-  const int w = threadIdx.x >> 6;
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) red[i * NW + w] = v[i];
-  }
-  __syncthreads();
-  float t = red[0];
-#pragma unroll
-  for (int k = 1; k < NW; ++k) t += red[k];
-  v[0] = t;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 1; i < N; ++i) {
-      float u = red[i * NW];
-#pragma unroll
-      for (int k = 1; k < NW; ++k) u += red[i * NW + k];
-      v[i] = u;
-    }
-  }
+  block_sum_lead_fresh<NW, N>(v, red);
 }
 
 // Picking one of a few kernel-argument pointers by a run-time (per-lane) index:  never `args.p[q]` — that

@@ -27,12 +27,12 @@
 #include "common.hpp"
 #include "../../include/bmnas_hip.h"
 #include "lazy_ln.hpp"
+#include "ln_sample.hpp"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
-constexpr float kEpsLn = 1e-5f;
 constexpr int kHeadSrc = 4;
 constexpr int kMaxO = 128;
 
@@ -71,7 +71,7 @@ __device__ __forceinline__ void sample_stats(const HeadSrc& src, int n_src, int 
   const float m = S * inv;
   const float var = fmaxf(Q * inv - m * m, 0.f);
   *mean = m;
-  *rstd = 1.f / sqrtf(var + kEpsLn);
+  *rstd = 1.f / sqrtf(var + kLnEps);
 }
 
 // ------------------------------------------------------------------------------ forward
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void head_fwd_k(HeadFwdArgs a, HeadLazy z) {
     }
     const float inv = 1.f / (float)a.D;
     mean = S * inv;
-    rstd = 1.f / sqrtf(fmaxf(Q * inv - mean * mean, 0.f) + kEpsLn);
+    rstd = 1.f / sqrtf(fmaxf(Q * inv - mean * mean, 0.f) + kLnEps);
     nmean = ls.mean;
     nrstd = ls.rstd;
   } else {
@@ -185,11 +185,11 @@ __global__ __launch_bounds__(256) void head_fwd_k(HeadFwdArgs a, HeadLazy z) {
       const float n4[4] = {nwv[j].x, nwv[j].y, nwv[j].z, nwv[j].w};
       const float c4[4] = {nbv[j].x, nbv[j].y, nbv[j].z, nbv[j].w};
 #pragma unroll
-      for (int r = 0; r < 4; ++r) x4[r] = (x4[r] - nmean) * nrstd * n4[r] + c4[r];
+      for (int r = 0; r < 4; ++r) x4[r] = ln_apply(x4[r], nmean, nrstd, n4[r], c4[r]);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float xh = (x4[r] - mean) * rstd;
+      const float xh = ln_xhat(x4[r], mean, rstd);
       const float pre = xh * w4[r] + b4[r];
       const bool on = pre > 0.f;
       const float f = on ? pre : 0.f;                         // relu(LayerNorm(.))
@@ -601,18 +601,18 @@ __global__ __launch_bounds__(256) void head_bwd_k(HeadBwdArgs a, HeadLazy z) {
       const float nmean = nv[g].x, nrstd = nv[g].y;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        xhn[r] = (xq[r] - nmean) * nrstd;
+        xhn[r] = ln_xhat(xq[r], nmean, nrstd);
         xq[r] = xhn[r] * nwq[r] + nbq[r];
       }
     }
     float dx[4], ff[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float xh = (xq[r] - mean) * rstd;
+      const float xh = ln_xhat(xq[r], mean, rstd);
       const float pre = xh * wq[r] + bq[r];
       const bool on = pre > 0.f;
       const float gy = (on && vs) ? acc[r] : 0.f;               // gradient at the LayerNorm output
-      dx[r] = rstd * (gy * wq[r] - m1 - xh * m2);
+      dx[r] = ln_dx(gy * wq[r], xh, m1, m2, rstd);
       gw[r] += gy * xh;
       gb[r] += gy;
       ff[r] = vs ? fmaxf(pre, 0.f) : 0.f;                       // feat = relu(LayerNorm(.)), zero in rows past b

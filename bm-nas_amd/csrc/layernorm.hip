@@ -6,10 +6,9 @@
 #include <cstdlib>
 #include "../../include/bmnas_hip.h"
 #include "arch_body.hpp"
+#include "ln_sample.hpp"
 
 namespace {
-
-constexpr float kEps = 1e-5f;
 
 struct LnSrc {
   const float* p[4];
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(BS) void cat_ln_fwd_k(LnSrc srcs, const float* __re
     acc[0] = block_sum_fresh<BS / 64>(acc[0], red6);         // (red6, not red: threads may still be reading the mean)
   }
   const float var = acc[0] * inv_d;
-  const float rstd = 1.f / sqrtf(var + kEps);
+  const float rstd = 1.f / sqrtf(var + kLnEps);
   if (threadIdx.x == 0) {
     stats[2 * s] = mean;
     stats[2 * s + 1] = rstd;
@@ -94,12 +93,7 @@ __global__ __launch_bounds__(BS) void cat_ln_fwd_k(LnSrc srcs, const float* __re
   for (int k = 0; k < VPT; ++k) {
     const int i = threadIdx.x + k * BS;
     if (i < d4) {
-      const float4 w = lw[k], bb = lb[k];
-      float4 o;
-      o.x = (v[k].x - mean) * rstd * w.x + bb.x;
-      o.y = (v[k].y - mean) * rstd * w.y + bb.y;
-      o.z = (v[k].z - mean) * rstd * w.z + bb.z;
-      o.w = (v[k].w - mean) * rstd * w.w + bb.w;
+      float4 o = ln_apply4(v[k], mean, rstd, lw[k], lb[k]);
       if (relu) {
         o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
       }
@@ -144,9 +138,7 @@ __global__ __launch_bounds__(BS) void cat_ln_bwd_k(const float* __restrict__ g, 
       if (resid != nullptr) x = f4_add(x, ld4(resid + ((int64_t)s * d4 + i) * 4));
       const float4 w = ld4(ln_w + (int64_t)i * 4);
       float4 gy = ld4(g + ((int64_t)s * d4 + i) * 4);
-      float4 h;
-      h.x = (x.x - mean) * rstd; h.y = (x.y - mean) * rstd;
-      h.z = (x.z - mean) * rstd; h.w = (x.w - mean) * rstd;
+      const float4 h = ln_xhat4(x, mean, rstd);
       if (relu) {
         const float4 bb = ld4(ln_b + (int64_t)i * 4);
         if (h.x * w.x + bb.x <= 0.f) gy.x = 0.f;
@@ -174,31 +166,15 @@ __global__ __launch_bounds__(BS) void cat_ln_bwd_k(const float* __restrict__ g, 
   }
   const float inv_d = 1.f / (float)(d4 * 4);
   // both sums behind ONE barrier (two block_sum calls were four; `red` is written once per launch)
-  constexpr int NWV = BS / 64;
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = s1;
-    red[NWV + (threadIdx.x >> 6)] = s2;
-  }
+  ln_bwd_sums_put<BS / 64>(s1, s2, red);
   __syncthreads();
-  float m1 = red[0], m2 = red[NWV];
-#pragma unroll
-  for (int w = 1; w < NWV; ++w) {
-    m1 += red[w];
-    m2 += red[NWV + w];
-  }
-  m1 *= inv_d;
-  m2 *= inv_d;
+  float m1, m2;
+  ln_bwd_sums_get<BS / 64>(red, inv_d, m1, m2);
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int i = threadIdx.x + k * BS;
     if (i < d4) {
-      float4 dx;
-      dx.x = rstd * (dxh[k].x - m1 - xh[k].x * m2);
-      dx.y = rstd * (dxh[k].y - m1 - xh[k].y * m2);
-      dx.z = rstd * (dxh[k].z - m1 - xh[k].z * m2);
-      dx.w = rstd * (dxh[k].w - m1 - xh[k].w * m2);
+      const float4 dx = ln_dx4(dxh[k], xh[k], m1, m2, rstd);
       const int q = i / cl4;
       const int off = i - q * cl4;
       float* d = pick_ptr(dsrcs.p, q);

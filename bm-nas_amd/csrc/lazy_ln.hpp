@@ -14,11 +14,11 @@
 // the two-pass form node_mix_ln_fwd_k uses.
 #pragma once
 #include "common.hpp"
+#include "ln_sample.hpp"
 
 constexpr int kLazyPart = 256;      // float4 per part (= threads of the producer's workgroup)
 constexpr int kLazyMaxParts = 4;    // C * L <= 4096 (MM-IMDB: 3 parts; NTU / Ego: 1)
 constexpr int kLazyRec = 8;         // floats per record
-constexpr float kEpsLazy = 1e-5f;
 
 struct LazyStats {
   float mean, rstd, osum, osq;
@@ -62,7 +62,7 @@ __device__ __forceinline__ LazyStats lazy_combine(const float* __restrict__ rec,
   }
   LazyStats o;
   o.mean = mu;
-  o.rstd = 1.f / sqrtf(M2 / D + kEpsLazy);
+  o.rstd = 1.f / sqrtf(M2 / D + kLnEps);
   o.osum = o.rstd * S1 + H;
   o.osq = o.rstd * o.rstd * S2 + 2.f * o.rstd * S3 + I;
   return o;

@@ -163,8 +163,7 @@ __global__ __launch_bounds__(256) void mixsum_pair_fwd_lazy_k(
   const float4 pv = reinterpret_cast<const float4*>(pre)[i];
   const float4 lw = ld4(ln_w + (int64_t)r * 4), lb = ld4(ln_b + (int64_t)r * 4);
   const LazyStats st = lazy_combine(rec, prm, P, smp);
-  const float4 n = make_float4((pv.x - st.mean) * st.rstd * lw.x + lb.x, (pv.y - st.mean) * st.rstd * lw.y + lb.y,
-                               (pv.z - st.mean) * st.rstd * lw.z + lb.z, (pv.w - st.mean) * st.rstd * lw.w + lb.w);
+  const float4 n = ln_apply4(pv, st.mean, st.rstd, lw, lb);
   float4 acc = f4_scale(v[0], wj[0]);
 #pragma unroll
   for (int j = 1; j < NIN; ++j) {
@@ -455,13 +454,7 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
     STAMP(3, blockIdx.y * gridDim.x + blockIdx.x, 1);
     if (t.on) {
       const int64_t e = t.e, ub = t.ub;
-      const float4 xh = make_float4((t.pre.x - mean) * rstd, (t.pre.y - mean) * rstd, (t.pre.z - mean) * rstd,
-                                    (t.pre.w - mean) * rstd);
-      float4 gv;
-      gv.x = rstd * (t.gy.x * lw.x - m1 - xh.x * m2);
-      gv.y = rstd * (t.gy.y * lw.y - m1 - xh.y * m2);
-      gv.z = rstd * (t.gy.z * lw.z - m1 - xh.z * m2);
-      gv.w = rstd * (t.gy.w * lw.w - m1 - xh.w * m2);
+      const float4 gv = ln_dx4(f4_mul(t.gy, lw), ln_xhat4(t.pre, mean, rstd), m1, m2, rstd);
       if (gbuf != nullptr) st4_w0<6>(gbuf + e, gv);
       if (dresid != nullptr) st4_w0<6>(dresid + e, f4_add(gv, use_r ? t.oldr : zero4));
       const float4 m2d = drop_mult4(rglu, (uint64_t)e), m3d = drop_mult4(rfc, (uint64_t)e);

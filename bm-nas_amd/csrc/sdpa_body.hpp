@@ -5,10 +5,10 @@
 #pragma once
 #include "attn_tile.hpp"
 #include "drop_cfg.hpp"
+#include "ln_sample.hpp"
 
 namespace {
 
-constexpr float kEps = 1e-5f;
 constexpr int kSdpaFwdLds = 4096 + 64;                 // bytes of LDS sdpa_fwd_body needs
 constexpr int kSdpaBwdFixedLds = 4096 + 2 * 4352 + 64;  // ... sdpa_bwd_body, before its [C][17] transpose buffer
 constexpr int kMaxCh = 8;          // 16-channel chunks per wave: C <= 4 * 8 * 16 = 512
@@ -124,7 +124,7 @@ __device__ __forceinline__ void sdpa_fwd_body(const int g, const float* __restri
     }
   }
   const float var = wg_sample_sum(sq, G.L, G.Lb, red, wave, lo, h) * inv_d;
-  const float rstd = 1.f / sqrtf(var + kEps);
+  const float rstd = 1.f / sqrtf(var + kLnEps);
   if (!v_h) return;
   if (wave == 0 && lo == 0 && l0 == 0) {
     stats[2 * sh] = mean;
@@ -137,8 +137,7 @@ __device__ __forceinline__ void sdpa_fwd_body(const int g, const float* __restri
       const int64_t pe = (int64_t)(ch * 16 + lo) * G.L + l0;
       const int64_t e = (int64_t)sh * G.C * G.L + pe;
       const float4 w = lw[k], bb = lb[k];
-      const float4 hh = make_float4((od[k].x - mean) * rstd, (od[k].y - mean) * rstd,
-                                    (od[k].z - mean) * rstd, (od[k].w - mean) * rstd);
+      const float4 hh = ln_xhat4(od[k], mean, rstd);
       st4_w0<2>(xhat + e, hh);
       st4_w0<2>(out + e, make_float4(hh.x * w.x + bb.x, hh.y * w.y + bb.y, hh.z * w.z + bb.z, hh.w * w.w + bb.w));
     }
@@ -217,10 +216,7 @@ __device__ __forceinline__ void sdpa_bwd_body(
     if (ch < nch) {
       const int64_t e = ((int64_t)sh * G.C + ch * 16 + lo) * G.L + l0;
       const float4 m = v_h ? drop_mult4(drop_rt, (uint64_t)e) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 d = make_float4(rstd * (dv[k].x - m1 - xh[k].x * m2) * m.x,
-                                   rstd * (dv[k].y - m1 - xh[k].y * m2) * m.y,
-                                   rstd * (dv[k].z - m1 - xh[k].z * m2) * m.z,
-                                   rstd * (dv[k].w - m1 - xh[k].w * m2) * m.w);
+      const float4 d = f4_mul(ln_dx4(dv[k], xh[k], m1, m2, rstd), m);
       dv[k] = d;
       float* t = dOt + (ch * 16 + lo) * 17 + 4 * h;
       t[0] = d.x; t[1] = d.y; t[2] = d.z; t[3] = d.w;
