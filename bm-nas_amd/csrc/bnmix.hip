@@ -1302,31 +1302,25 @@ extern "C" int bmnas_node_mix_fwd_next(const float* x, const float* y, const flo
                                        bmnas_dropout_t drop_fc, const float* const* prev, int n_prev,
                                        const float* w, int w_stride, float* z_next, void* stream) {
   if (!x || !y || !p1 || !U || !chan || !gamma || !out || b < 0 || C < 1 || n_prev < 0) return BMNAS_E_ARG;
-  if (L % 4 || L > 16) return BMNAS_E_SHAPE;
+  if (!len_fwd_ok(L)) return BMNAS_E_SHAPE;
   if (n_prev > kMixPrev) return BMNAS_E_LIMIT;
   MixNextF N{};
   if (n_prev > 0) {
     if (!prev || !w || !z_next || w_stride < 1) return BMNAS_E_ARG;
-    for (int j = 0; j < n_prev; ++j) {
-      if (!prev[j]) return BMNAS_E_ARG;
-      N.prev[j] = prev[j];
-    }
+    if (int e = fill_ptrs(N.prev, prev, n_prev)) return e;
     N.w = w; N.ws = w_stride; N.z = z_next; N.n = n_prev;
   }
   BnFin f;
-  if (int e = to_fin(fin, &f)) return e;
-  if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
-  if (C > 4096 / 3 || (3 * C) % 4) return BMNAS_E_LIMIT;   // bn_fin_fill: four channels per thread, scale | shift in LDS
+  if (int e = fin_for(fin, b, L, &f)) return e;
+  if (!fin_lds_ok(3, C)) return BMNAS_E_LIMIT;
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * C * L / 4;
-#define NMF(NPv)                                                                                          \
-  case NPv:                                                                                               \
-    hipLaunchKernelGGL(node_mix_fwd_k<NPv>, dim3(stream_grid(total)), dim3(256), (size_t)6 * C * sizeof(float), \
-                       (hipStream_t)stream, x, y, p1, U, chan, f, gamma, out, b, C, L, to_cfg(drop_glu),   \
-                       to_cfg(drop_fc), N);                                                               \
-    break;
-  switch (n_prev) { NMF(0) NMF(1) NMF(2) NMF(3) NMF(4) NMF(5) default: return BMNAS_E_LIMIT; }
-#undef NMF
+  if (int e = dispatch_range<0, kMixPrev>(n_prev, [&](auto NP) {
+        hipLaunchKernelGGL(node_mix_fwd_k<decltype(NP)::value>, dim3(stream_grid(total)), dim3(256),
+                           (size_t)6 * C * sizeof(float), (hipStream_t)stream, x, y, p1, U, chan, f, gamma, out, b, C,
+                           L, to_cfg(drop_glu), to_cfg(drop_fc), N);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -1349,35 +1343,19 @@ extern "C" int bmnas_node_mix_ln_fwd(const float* x, const float* y, const float
   if (!x || !y || !p1 || !U || !chan || !gamma || !resid || !ln_w || !ln_b || !pre || !out || !stats ||
       b < 0 || C < 1)
     return BMNAS_E_ARG;
-  if (L % 4 || L > 16) return BMNAS_E_SHAPE;
+  if (!len_fwd_ok(L)) return BMNAS_E_SHAPE;
   BnFin f;
-  if (int e = to_fin(fin, &f)) return e;
-  if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
-  if (C > 4096 / 3 || (3 * C) % 4) return BMNAS_E_LIMIT;   // bn_fin_fill, as bmnas_node_mix_fwd_next
+  if (int e = fin_for(fin, b, L, &f)) return e;
+  if (!fin_lds_ok(3, C)) return BMNAS_E_LIMIT;
   if (b == 0) return 0;
   const size_t fin_lds = (size_t)6 * C * sizeof(float);
-  const bool wide = b <= 256 && C * L / 4 >= 512;   // fewer samples than CUs: 8 waves per sample
-  const int bs = wide ? 512 : 256;
-  const int need = (C * L / 4 + bs - 1) / bs;
   hipStream_t st = (hipStream_t)stream;
-#define NML(V)                                                                                         \
-  do {                                                                                                 \
-    if (wide)                                                                                          \
-      hipLaunchKernelGGL((node_mix_ln_fwd_k<V, 512>), dim3(b), dim3(512), fin_lds, st, x, y, p1, U,    \
-                         chan, f, gamma, resid, ln_w, ln_b, pre, out, stats, b, C, L,                  \
-                         to_cfg(drop_glu), to_cfg(drop_fc), out_sums);                                 \
-    else                                                                                               \
-      hipLaunchKernelGGL((node_mix_ln_fwd_k<V, 256>), dim3(b), dim3(256), fin_lds, st, x, y, p1, U,    \
-                         chan, f, gamma, resid, ln_w, ln_b, pre, out, stats, b, C, L,                  \
-                         to_cfg(drop_glu), to_cfg(drop_fc), out_sums);                                 \
-  } while (0)
-  if (need <= 1) NML(1);
-  else if (need <= 2) NML(2);
-  else if (need <= 3) NML(3);
-  else if (need <= 4) NML(4);
-  else if (need <= 8) NML(8);
-  else return BMNAS_E_LIMIT;
-#undef NML
+  if (int e = dispatch_ln<1, 2, 3, 4, 8>(ln_launch_shape(b, C * L / 4), [&](auto V, auto BS) {
+        hipLaunchKernelGGL((node_mix_ln_fwd_k<decltype(V)::value, decltype(BS)::value>), dim3(b),
+                           dim3(decltype(BS)::value), fin_lds, st, x, y, p1, U, chan, f, gamma, resid, ln_w, ln_b, pre,
+                           out, stats, b, C, L, to_cfg(drop_glu), to_cfg(drop_fc), out_sums);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -1395,17 +1373,14 @@ extern "C" int bmnas_node_mix_bwd_next(const float* g, const float* x, const flo
   if (!x || !y || !p1 || !U || !chan || !gamma || !dV || !bn_grad || b < 0 || C < 1 || dgamma_shards < 1 ||
       n_prev < 0)
     return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (n_prev > kMixPrev) return BMNAS_E_LIMIT;
   MixNextB N{};
   if (n_prev > 0) {
     // g (nullable here) is what other consumers of s accumulated; g_out receives the complete gradient
     if (!prev || !dprev || !w || !dw || !s || !gz || !g_out || w_stride < 1 || dw_shards < 1) return BMNAS_E_ARG;
-    for (int j = 0; j < n_prev; ++j) {
-      if (!prev[j]) return BMNAS_E_ARG;
-      N.prev[j] = prev[j];
-      N.dprev[j] = dprev[j];
-    }
+    if (int e = fill_ptrs(N.prev, prev, n_prev)) return e;
+    fill_ptrs_out(N.dprev, dprev, n_prev);
     N.w = w; N.ws = w_stride; N.dw = dw; N.dw_shards = dw_shards; N.dw_stride = dw_shard_stride;
     N.s = s; N.gz = gz; N.gz2 = gz2; N.g_in = g; N.g_out = g_out; N.n = n_prev; N.acc = prev_accumulate_mask;
   } else if (!g) {
@@ -1415,14 +1390,12 @@ extern "C" int bmnas_node_mix_bwd_next(const float* g, const float* x, const flo
   const int cl4 = C * L / 4;
   const int chunk = pick_chunk(b, cl4);
   dim3 grid((cl4 + 63) / 64, (b + chunk - 1) / chunk);
-#define NMB(NPv)                                                                                          \
-  case NPv:                                                                                               \
-    hipLaunchKernelGGL(node_mix_bwd_k<NPv>, grid, dim3(256), 0, (hipStream_t)stream, g, x, y, p1, U, chan, \
-                       gamma, dgamma, dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV,     \
-                       bn_grad, b, C, L, chunk, to_cfg(drop_glu), to_cfg(drop_fc), N);                     \
-    break;
-  switch (n_prev) { NMB(0) NMB(1) NMB(2) NMB(3) NMB(4) NMB(5) default: return BMNAS_E_LIMIT; }
-#undef NMB
+  if (int e = dispatch_range<0, kMixPrev>(n_prev, [&](auto NP) {
+        hipLaunchKernelGGL(node_mix_bwd_k<decltype(NP)::value>, grid, dim3(256), 0, (hipStream_t)stream, g, x, y, p1, U,
+                           chan, gamma, dgamma, dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV,
+                           bn_grad, b, C, L, chunk, to_cfg(drop_glu), to_cfg(drop_fc), N);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -1454,7 +1427,7 @@ extern "C" int bmnas_node_mix_ln_bwd(const float* g, const float* pre, const flo
       C < 1 || dgamma_shards < 1)
     return BMNAS_E_ARG;
   if (accumulate_resid && !dresid) return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (b == 0) return 0;
   if (!bmnas_node_mix_ln_bwd_ok(b, C, L)) return BMNAS_E_LIMIT;
   const int cl4 = C * L / 4;
@@ -1466,15 +1439,15 @@ extern "C" int bmnas_node_mix_ln_bwd(const float* g, const float* pre, const flo
 #else
   const int probe = 0;
 #endif
-#define NMLB(V1, V2)                                                                                         \
-  hipLaunchKernelGGL((node_mix_ln_bwd_k<V1, V2, 512>), dim3(2 * b), dim3(512), 0, st, g, pre, ln_w, stats,   \
-                     g_in, dresid, accumulate_resid, x, y, p1, U, chan, gamma, dgamma, dgamma_shards,        \
-                     dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, b, C, L, to_cfg(drop_glu),   \
-                     to_cfg(drop_fc), probe)
-  if (cl4 <= 512) NMLB(1, 1);
-  else if (cl4 <= 1024) NMLB(2, 1);
-  else NMLB(4, 2);
-#undef NMLB
+  auto launch = [&](auto V1, auto V2) {
+    hipLaunchKernelGGL((node_mix_ln_bwd_k<decltype(V1)::value, decltype(V2)::value, 512>), dim3(2 * b), dim3(512), 0,
+                       st, g, pre, ln_w, stats, g_in, dresid, accumulate_resid, x, y, p1, U, chan, gamma, dgamma,
+                       dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, b, C, L,
+                       to_cfg(drop_glu), to_cfg(drop_fc), probe);
+  };
+  if (cl4 <= 512) launch(int_c<1>{}, int_c<1>{});
+  else if (cl4 <= 1024) launch(int_c<2>{}, int_c<1>{});
+  else launch(int_c<4>{}, int_c<2>{});
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -1482,12 +1455,10 @@ extern "C" int bmnas_node_mix_ln_bwd(const float* g, const float* pre, const flo
 extern "C" int bmnas_bn_glu_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b, int C, int L,
                                 bmnas_dropout_t drop, void* stream) {
   if (!U || !chan || !out || b < 0 || C < 1) return BMNAS_E_ARG;
-  if (L % 4 || L > 16) return BMNAS_E_SHAPE;
-  // scale | shift of every channel sit in LDS, written four adjacent channels per thread (bn_fin_fill)
-  if (2 * C > 4096 || (2 * C) % 4) return BMNAS_E_LIMIT;
+  if (!len_fwd_ok(L)) return BMNAS_E_SHAPE;
+  if (!fin_lds_ok(2, C)) return BMNAS_E_LIMIT;
   BnFin f;
-  if (int e = to_fin(fin, &f)) return e;
-  if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+  if (int e = fin_for(fin, b, L, &f)) return e;
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * C * L / 4;
   hipLaunchKernelGGL(bn_glu_fwd_k, dim3(stream_grid(total)), dim3(256), (size_t)4 * C * sizeof(float),
@@ -1500,7 +1471,7 @@ extern "C" int bmnas_bn_glu_bwd(const float* g, const float* U, const float* cha
                                 float* bn_grad, int b, int C, int L, bmnas_dropout_t drop,
                                 void* stream) {
   if (!g || !U || !chan || !dV || !bn_grad || b < 0 || C < 1) return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (b == 0) return 0;
   const int cl4 = C * L / 4;
   const int chunk = pick_chunk(b, cl4);
@@ -1515,12 +1486,10 @@ template <typename Kern>
 static int bn_act_fwd(Kern kern, const float* U, float* chan, bmnas_bn_fin_t fin, float* out, int b, int M, int L,
                       bmnas_dropout_t drop, void* stream) {
   if (!U || !chan || !out || b < 0 || M < 1) return BMNAS_E_ARG;
-  if (L % 4 || L > 16) return BMNAS_E_SHAPE;
-  // scale | shift of every channel sit in LDS, written four adjacent channels per thread (bn_fin_fill)
-  if (M > 4096 || M % 4) return BMNAS_E_LIMIT;
+  if (!len_fwd_ok(L)) return BMNAS_E_SHAPE;
+  if (!fin_lds_ok(1, M)) return BMNAS_E_LIMIT;
   BnFin f;
-  if (int e = to_fin(fin, &f)) return e;
-  if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+  if (int e = fin_for(fin, b, L, &f)) return e;
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * M * L / 4;
   hipLaunchKernelGGL(kern, dim3(stream_grid(total)), dim3(256), (size_t)2 * M * sizeof(float),
@@ -1543,7 +1512,7 @@ template <typename Kern>
 static int bn_act_bwd(Kern kern, const float* g, const float* U, const float* chan, float* dV, float* bn_grad, int b,
                       int M, int L, bmnas_dropout_t drop, void* stream) {
   if (!g || !U || !chan || !dV || !bn_grad || b < 0 || M < 1) return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (b == 0) return 0;
   const int ml4 = M * L / 4;
   const int chunk = pick_chunk(b, ml4);
@@ -1570,13 +1539,12 @@ extern "C" int bmnas_bn_relu_fwd_group(const bmnas_bn_relu_fwd_prob_t* probs, in
                                        void* stream) {
   if (!probs || n < 1 || b < 0 || M < 1) return BMNAS_E_ARG;
   if (n > kBnGroup) return BMNAS_E_LIMIT;
-  if (L % 4 || L > 16) return BMNAS_E_SHAPE;
-  if (M > 4096 || M % 4) return BMNAS_E_LIMIT;
+  if (!len_fwd_ok(L)) return BMNAS_E_SHAPE;
+  if (!fin_lds_ok(1, M)) return BMNAS_E_LIMIT;
   BnReluFwdGroup G{};
   for (int p = 0; p < n; ++p) {
     if (!probs[p].U || !probs[p].chan || !probs[p].out) return BMNAS_E_ARG;
-    if (int e = to_fin(probs[p].fin, &G.fin[p])) return e;
-    if (G.fin[p].on && G.fin[p].training && b * L < 2) return BMNAS_E_ARG;
+    if (int e = fin_for(probs[p].fin, b, L, &G.fin[p])) return e;
     G.U[p] = probs[p].U; G.chan[p] = probs[p].chan; G.out[p] = probs[p].out; G.drop[p] = to_cfg(probs[p].drop);
   }
   if (b == 0) return 0;
@@ -1596,7 +1564,7 @@ extern "C" int bmnas_bn_relu_bwd_group(const bmnas_bn_relu_bwd_prob_t* probs, in
                                        void* stream) {
   if (!probs || n < 1 || b < 0 || M < 1) return BMNAS_E_ARG;
   if (n > kBnGroup) return BMNAS_E_LIMIT;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   BnReluBwdGroup G{};
   for (int p = 0; p < n; ++p) {
     if (!probs[p].g || !probs[p].U || !probs[p].chan || !probs[p].dV || !probs[p].bn_grad) return BMNAS_E_ARG;
@@ -1610,21 +1578,6 @@ extern "C" int bmnas_bn_relu_bwd_group(const bmnas_bn_relu_bwd_prob_t* probs, in
   hipLaunchKernelGGL(bn_relu_bwd_group_k, grid, dim3(256), 0, (hipStream_t)stream, G, b, M, L, chunk);
   BMNAS_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int bmnas_bn_relu_ln_fwd_pair(const float* U, float* chan, bmnas_bn_fin_t fin, const float* resid,
-                                         const float* ln_w, const float* ln_b, float* o, float* out,
-                                         float* stats, int b, int C, int L, bmnas_dropout_t drop,
-                                         float* out_sums, const float* const* xs, int n_prev, const float* w,
-                                         int w_stride, const float* w2, int w2_stride, float* h, float* z,
-                                         void* stream);
-
-extern "C" int bmnas_bn_relu_ln_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, const float* resid,
-                                    const float* ln_w, const float* ln_b, float* o, float* out, float* stats,
-                                    int b, int C, int L, bmnas_dropout_t drop, float* out_sums,
-                                    void* stream) {
-  return bmnas_bn_relu_ln_fwd_pair(U, chan, fin, resid, ln_w, ln_b, o, out, stats, b, C, L, drop, out_sums,
-                                   nullptr, 0, nullptr, 1, nullptr, 1, nullptr, nullptr, stream);
 }
 
 extern "C" int bmnas_bn_relu_ln_fwd_pair_ok(int b, int C, int L, int n_prev) {
@@ -1642,74 +1595,40 @@ extern "C" int bmnas_bn_relu_ln_fwd_pair(const float* U, float* chan, bmnas_bn_f
   if (n_prev > 0) {
     if (!xs || !w || !w2 || !h || !z || w_stride < 1 || w2_stride < 1) return BMNAS_E_ARG;
     if (!bmnas_bn_relu_ln_fwd_pair_ok(b > 0 ? b : 1, C, L, n_prev)) return BMNAS_E_LIMIT;
-    for (int j = 0; j < n_prev; ++j) {
-      if (!xs[j]) return BMNAS_E_ARG;
-      P.xs.p[j] = xs[j];
-    }
+    if (int e = fill_ptrs(P.xs.p, xs, n_prev)) return e;
     P.w = w; P.w2 = w2; P.h = h; P.z = z; P.ws = w_stride; P.w2s = w2_stride;
   } else if (n_prev < 0) {
     return BMNAS_E_ARG;
   }
-  if (L % 4 || L > 16 || C % 4) return BMNAS_E_SHAPE;
+  if (!len_fwd_ok(L) || C % 4) return BMNAS_E_SHAPE;
   BnFin f;
-  if (int e = to_fin(fin, &f)) return e;
-  if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+  if (int e = fin_for(fin, b, L, &f)) return e;
   if (b == 0) return 0;
   const size_t fin_lds = (size_t)2 * C * sizeof(float);
-  const bool wide = b <= 256 && C * L / 4 >= 512;
-  const int bs = wide ? 512 : 256;
-  const int need = (C * L / 4 + bs - 1) / bs;
-  if (C > 4 * bs) return BMNAS_E_LIMIT;                 // bn_fin_fill: one trip
+  const LnShape sh = ln_launch_shape(b, C * L / 4);
+  if (C > 4 * sh.bs) return BMNAS_E_LIMIT;                 // bn_fin_fill: one trip
   hipStream_t st = (hipStream_t)stream;
-  if (n_prev > 0) {                                      // (host-checked: one float4 per lane, 256 lanes)
-#define BRP(N)                                                                                          \
-  case N:                                                                                               \
-    hipLaunchKernelGGL((bn_relu_ln_fwd_k<1, 256, N>), dim3(b), dim3(256), fin_lds, st, U, chan, f, resid, \
-                       ln_w, ln_b, o, out, stats, b, C, L, to_cfg(drop), out_sums, P);                  \
-    break;
-    switch (n_prev) {
-      BRP(1) BRP(2) BRP(3) BRP(4) BRP(5) BRP(6) BRP(7) BRP(8) BRP(9) BRP(10) BRP(11) BRP(12) BRP(13) BRP(14) BRP(15)
-      default: return BMNAS_E_LIMIT;
-    }
-#undef BRP
-    BMNAS_CHECK_LAUNCH();
-    return 0;
-  }
-#define BRL(V)                                                                                          \
-  do {                                                                                                  \
-    if (wide)                                                                                           \
-      hipLaunchKernelGGL((bn_relu_ln_fwd_k<V, 512>), dim3(b), dim3(512), fin_lds, st, U, chan, f, resid, \
-                         ln_w, ln_b, o, out, stats, b, C, L, to_cfg(drop), out_sums, P);                \
-    else                                                                                                \
-      hipLaunchKernelGGL((bn_relu_ln_fwd_k<V, 256>), dim3(b), dim3(256), fin_lds, st, U, chan, f, resid, \
-                         ln_w, ln_b, o, out, stats, b, C, L, to_cfg(drop), out_sums, P);                \
-  } while (0)
-  if (need <= 1) BRL(1);
-  else if (need <= 2) BRL(2);
-  else if (need <= 3) BRL(3);
-  else if (need <= 4) BRL(4);
-  else if (need <= 8) BRL(8);
-  else return BMNAS_E_LIMIT;
-#undef BRL
+  const int e = n_prev > 0                                 // (host-checked: one float4 per lane, 256 lanes)
+      ? dispatch_range<1, BMNAS_MAX_PTRS - 1>(n_prev, [&](auto NP) {
+          hipLaunchKernelGGL((bn_relu_ln_fwd_k<1, 256, decltype(NP)::value>), dim3(b), dim3(256), fin_lds, st, U, chan,
+                             f, resid, ln_w, ln_b, o, out, stats, b, C, L, to_cfg(drop), out_sums, P);
+        })
+      : dispatch_ln<1, 2, 3, 4, 8>(sh, [&](auto V, auto BS) {
+          hipLaunchKernelGGL((bn_relu_ln_fwd_k<decltype(V)::value, decltype(BS)::value>), dim3(b),
+                             dim3(decltype(BS)::value), fin_lds, st, U, chan, f, resid, ln_w, ln_b, o, out, stats, b,
+                             C, L, to_cfg(drop), out_sums, P);
+        });
+  if (e) return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int bmnas_bn_relu_ln_bwd_pair(
-    const float* g, const float* o, const float* resid, const float* ln_w, const float* stats, const float* U,
-    const float* chan, float* dV, float* bn_grad, float* dresid, int accumulate_resid, int b, int C, int L,
-    bmnas_dropout_t drop, const float* const* xs, float* const* dxs, int n_prev, uint32_t accumulate_mask,
-    const float* out, const float* w, int w_stride, const float* w2, int w2_stride, const float* h,
-    const float* gh, const float* gz, const float* gz2, float* dw, float* dw2, int dw_shards,
-    int64_t dw_shard_stride, float* g_full, void* stream);
-
-extern "C" int bmnas_bn_relu_ln_bwd(const float* g, const float* o, const float* resid, const float* ln_w,
-                                    const float* stats, const float* U, const float* chan, float* dV,
-                                    float* bn_grad, float* dresid, int accumulate_resid, int b, int C,
-                                    int L, bmnas_dropout_t drop, void* stream) {
-  return bmnas_bn_relu_ln_bwd_pair(g, o, resid, ln_w, stats, U, chan, dV, bn_grad, dresid, accumulate_resid, b, C,
-                                   L, drop, nullptr, nullptr, 0, 0, nullptr, nullptr, 1, nullptr, 1, nullptr,
-                                   nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, nullptr, stream);
+extern "C" int bmnas_bn_relu_ln_fwd(const float* U, float* chan, bmnas_bn_fin_t fin, const float* resid,
+                                    const float* ln_w, const float* ln_b, float* o, float* out, float* stats,
+                                    int b, int C, int L, bmnas_dropout_t drop, float* out_sums,
+                                    void* stream) {
+  return bmnas_bn_relu_ln_fwd_pair(U, chan, fin, resid, ln_w, ln_b, o, out, stats, b, C, L, drop, out_sums,
+                                   nullptr, 0, nullptr, 1, nullptr, 1, nullptr, nullptr, stream);
 }
 
 extern "C" int bmnas_bn_relu_ln_bwd_pair(
@@ -1727,65 +1646,50 @@ extern "C" int bmnas_bn_relu_ln_bwd_pair(
         dw_shards < 1)
       return BMNAS_E_ARG;
     if (!bmnas_bn_relu_ln_fwd_pair_ok(b > 0 ? b : 1, C, L, n_prev)) return BMNAS_E_LIMIT;
-    for (int j = 0; j < n_prev; ++j) {
-      if (!xs[j]) return BMNAS_E_ARG;
-      P.xs.p[j] = xs[j];
-      P.dxs.p[j] = dxs[j];
+    if (int e = fill_ptrs(P.xs.p, xs, n_prev)) return e;
+    fill_ptrs_out(P.dxs.p, dxs, n_prev);
+    for (int j = 0; j < n_prev; ++j)
       for (int k = 0; k < j; ++k)
         if (dxs[j] != nullptr && dxs[j] == dxs[k]) return BMNAS_E_ARG;     // old values are fetched up front
-    }
     P.out = out; P.w = w; P.w2 = w2; P.h = h; P.gh = gh; P.gz = gz; P.gz2 = gz2; P.dw = dw; P.dw2 = dw2;
     P.g_full = g_full; P.dw_stride = dw_shard_stride; P.ws = w_stride; P.w2s = w2_stride;
     P.dw_shards = dw_shards; P.acc = accumulate_mask;
   } else if (n_prev < 0) {
     return BMNAS_E_ARG;
   }
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (accumulate_resid && !dresid) return BMNAS_E_ARG;
   if (b == 0) return 0;
-  const bool wide = b <= 256 && C * L / 4 >= 512;
-  const int bs = wide ? 512 : 256;
-  const int need = (C * L / 4 + bs - 1) / bs;
   hipStream_t st = (hipStream_t)stream;
-  if (n_prev > 0) {                                      // (host-checked: one float4 per lane, 256 lanes)
-#define BRP(N)                                                                                          \
-  case N:                                                                                               \
-    hipLaunchKernelGGL((bn_relu_ln_bwd_k<1, 256, N>), dim3(b), dim3(256), 0, st, g, o, resid, ln_w, stats, \
-                       U, chan, dV, bn_grad, dresid, accumulate_resid, b, C, L, to_cfg(drop), P);       \
-    break;
-    switch (n_prev) {
-      BRP(1) BRP(2) BRP(3) BRP(4) BRP(5) BRP(6) BRP(7) BRP(8) BRP(9) BRP(10) BRP(11) BRP(12) BRP(13) BRP(14) BRP(15)
-      default: return BMNAS_E_LIMIT;
-    }
-#undef BRP
-    BMNAS_CHECK_LAUNCH();
-    return 0;
-  }
-#define BRL(V)                                                                                          \
-  do {                                                                                                  \
-    if (wide)                                                                                           \
-      hipLaunchKernelGGL((bn_relu_ln_bwd_k<V, 512>), dim3(b), dim3(512), 0, st, g, o, resid, ln_w, stats, \
-                         U, chan, dV, bn_grad, dresid, accumulate_resid, b, C, L, to_cfg(drop), P);     \
-    else                                                                                                \
-      hipLaunchKernelGGL((bn_relu_ln_bwd_k<V, 256>), dim3(b), dim3(256), 0, st, g, o, resid, ln_w, stats, \
-                         U, chan, dV, bn_grad, dresid, accumulate_resid, b, C, L, to_cfg(drop), P);     \
-  } while (0)
-  if (need <= 1) BRL(1);
-  else if (need <= 2) BRL(2);
-  else if (need <= 3) BRL(3);
-  else if (need <= 4) BRL(4);
-  else if (need <= 8) BRL(8);
-  else return BMNAS_E_LIMIT;
-#undef BRL
+  const int e = n_prev > 0                                 // (host-checked: one float4 per lane, 256 lanes)
+      ? dispatch_range<1, BMNAS_MAX_PTRS - 1>(n_prev, [&](auto NP) {
+          hipLaunchKernelGGL((bn_relu_ln_bwd_k<1, 256, decltype(NP)::value>), dim3(b), dim3(256), 0, st, g, o, resid,
+                             ln_w, stats, U, chan, dV, bn_grad, dresid, accumulate_resid, b, C, L, to_cfg(drop), P);
+        })
+      : dispatch_ln<1, 2, 3, 4, 8>(ln_launch_shape(b, C * L / 4), [&](auto V, auto BS) {
+          hipLaunchKernelGGL((bn_relu_ln_bwd_k<decltype(V)::value, decltype(BS)::value>), dim3(b),
+                             dim3(decltype(BS)::value), 0, st, g, o, resid, ln_w, stats, U, chan, dV, bn_grad, dresid,
+                             accumulate_resid, b, C, L, to_cfg(drop), P);
+        });
+  if (e) return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int bmnas_bn_relu_ln_bwd(const float* g, const float* o, const float* resid, const float* ln_w,
+                                    const float* stats, const float* U, const float* chan, float* dV,
+                                    float* bn_grad, float* dresid, int accumulate_resid, int b, int C,
+                                    int L, bmnas_dropout_t drop, void* stream) {
+  return bmnas_bn_relu_ln_bwd_pair(g, o, resid, ln_w, stats, U, chan, dV, bn_grad, dresid, accumulate_resid, b, C,
+                                   L, drop, nullptr, nullptr, 0, 0, nullptr, nullptr, 1, nullptr, 1, nullptr,
+                                   nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, nullptr, stream);
 }
 
 extern "C" int bmnas_bn_bwd_apply(float* dV, const float* U, const float* chan,
                                   const float* bn_grad, int b, int M, int L, int training,
                                   void* stream) {
   if (!dV || !U || !chan || !bn_grad || b < 0 || M < 1) return BMNAS_E_ARG;
-  if (L % 4 || L > 16) return BMNAS_E_SHAPE;
+  if (!len_fwd_ok(L)) return BMNAS_E_SHAPE;
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * M * L / 4;
   hipLaunchKernelGGL(bn_bwd_apply_k, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, dV,
@@ -1910,28 +1814,20 @@ extern "C" int bmnas_cell_prologue_pair(const float* const* a, float* const* out
   if (n_in > BMNAS_MAX_PTRS - 1) return BMNAS_E_LIMIT;
   if (n_elem % 4) return BMNAS_E_SHAPE;
   PairArgs A{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    A.xs.p[j] = xs[j];
-  }
+  if (int e = fill_ptrs(A.xs.p, xs, n_in)) return e;
   A.alpha = alpha_logits; A.beta = beta_logits; A.out = h; A.out2 = z; A.n4 = n_elem / 4;
   // one float4 per lane and input: the pair sum is a latency-floor kernel at the reference batches
-  int64_t pair_blocks = (A.n4 + 255) / 256;
+  int64_t pair_blocks = (A.n4 + 255) / 256;                   // (0 at n_elem == 0: the prologue alone)
   if (pair_blocks > 2048) pair_blocks = 2048;                 // as bmnas_mixsum_pair_fwd
   if (L.blocks + pair_blocks == 0) return 0;
   dim3 grid((unsigned)(L.blocks + pair_blocks));
   hipStream_t st = (hipStream_t)stream;
-#define PP(N)                                                                                          \
-  case N:                                                                                              \
-    hipLaunchKernelGGL(cell_prologue_pair_k<N>, grid, dim3(256), 0, st, L.P, L.F,                      \
-                       (unsigned long long*)step_counter, (const unsigned long long*)step_span, scrub, \
-                       scrub_n / 4, L.blocks, A);                                                      \
-    break;
-  switch (n_in) {
-    PP(1) PP(2) PP(3) PP(4) PP(5) PP(6) PP(7) PP(8) PP(9) PP(10) PP(11) PP(12) PP(13) PP(14) PP(15)
-    default: return BMNAS_E_LIMIT;
-  }
-#undef PP
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS - 1>(n_in, [&](auto N) {
+        hipLaunchKernelGGL(cell_prologue_pair_k<decltype(N)::value>, grid, dim3(256), 0, st, L.P, L.F,
+                           (unsigned long long*)step_counter, (const unsigned long long*)step_span, scrub,
+                           scrub_n / 4, L.blocks, A);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

@@ -7,6 +7,7 @@
 #include "../../include/bmnas_hip.h"
 #include "arch_body.hpp"
 #include "ln_sample.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -383,29 +384,7 @@ __global__ __launch_bounds__(256) void backward_epilogue_k(LnAffineBatch B, Arch
   ln_affine_body(P, B.b, B.chunk, red);
 }
 
-inline int pick_vpt(int d4, int bs) {
-  const int need = (d4 + bs - 1) / bs;
-  if (need <= 1) return 1;
-  if (need <= 2) return 2;
-  if (need <= 3) return 3;
-  if (need <= 4) return 4;
-  if (need <= 8) return 8;
-  if (need <= 16) return 16;
-  return -1;
-}
-
 }  // namespace
-
-#define LN_DISPATCH(V, CALL)      \
-  switch (V) {                    \
-    case 1: CALL(1); break;       \
-    case 2: CALL(2); break;       \
-    case 3: CALL(3); break;       \
-    case 4: CALL(4); break;       \
-    case 8: CALL(8); break;       \
-    case 16: CALL(16); break;     \
-    default: return BMNAS_E_LIMIT; \
-  }
 
 extern "C" int bmnas_cat_ln_fwd(const float* const* srcs, int n_src, const float* resid,
                                 const float* ln_w, const float* ln_b, float* out, float* stats,
@@ -417,21 +396,14 @@ extern "C" int bmnas_cat_ln_fwd(const float* const* srcs, int n_src, const float
   if ((C * L) % 4 != 0) return BMNAS_E_SHAPE;
   if (b == 0) return 0;
   LnSrc s{};
-  for (int q = 0; q < n_src; ++q) {
-    if (!srcs[q]) return BMNAS_E_ARG;
-    s.p[q] = srcs[q];
-  }
+  if (int e = fill_ptrs(s.p, srcs, n_src)) return e;
   const int cl4 = C * L / 4, d4 = cl4 * n_src;
-  const bool wide = b <= 256 && d4 >= 512;          // fewer samples than CUs: 8 waves per sample
-  const int vpt = pick_vpt(d4, wide ? 512 : 256);
   hipStream_t st = (hipStream_t)stream;
-#define CALL(V)                                                                                         \
-  do {                                                                                                  \
-    if (wide) hipLaunchKernelGGL((cat_ln_fwd_k<V, 512>), dim3(b), dim3(512), 0, st, s, resid, ln_w, ln_b, out, stats, cl4, d4, relu, out_sums); \
-    else hipLaunchKernelGGL((cat_ln_fwd_k<V, 256>), dim3(b), dim3(256), 0, st, s, resid, ln_w, ln_b, out, stats, cl4, d4, relu, out_sums);      \
-  } while (0)
-  LN_DISPATCH(vpt, CALL)
-#undef CALL
+  if (int e = dispatch_ln<1, 2, 3, 4, 8, 16>(ln_launch_shape(b, d4), [&](auto V, auto BS) {
+        hipLaunchKernelGGL((cat_ln_fwd_k<decltype(V)::value, decltype(BS)::value>), dim3(b), dim3(decltype(BS)::value),
+                           0, st, s, resid, ln_w, ln_b, out, stats, cl4, d4, relu, out_sums);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -451,22 +423,16 @@ extern "C" int bmnas_cat_ln_bwd(const float* g, const float* const* srcs, int n_
   if (b == 0) return 0;
   LnSrc s{};
   LnDst d{};
-  for (int q = 0; q < n_src; ++q) {
-    if (!srcs[q]) return BMNAS_E_ARG;
-    s.p[q] = srcs[q];
-    d.p[q] = dsrcs[q];
-  }
+  if (int e = fill_ptrs(s.p, srcs, n_src)) return e;
+  fill_ptrs_out(d.p, dsrcs, n_src);
   const int cl4 = C * L / 4, d4 = cl4 * n_src;
-  const bool wide = b <= 256 && d4 >= 512;
-  const int vpt = pick_vpt(d4, wide ? 512 : 256);
   hipStream_t st = (hipStream_t)stream;
-#define CALL(V)                                                                                         \
-  do {                                                                                                  \
-    if (wide) hipLaunchKernelGGL((cat_ln_bwd_k<V, 512>), dim3(b), dim3(512), 0, st, g, s, resid, ln_w, ln_b, stats, d, dresid, accumulate_mask, dln_w, dln_b, cl4, d4, relu, scrub, scrub_n / 4); \
-    else hipLaunchKernelGGL((cat_ln_bwd_k<V, 256>), dim3(b), dim3(256), 0, st, g, s, resid, ln_w, ln_b, stats, d, dresid, accumulate_mask, dln_w, dln_b, cl4, d4, relu, scrub, scrub_n / 4);      \
-  } while (0)
-  LN_DISPATCH(vpt, CALL)
-#undef CALL
+  if (int e = dispatch_ln<1, 2, 3, 4, 8, 16>(ln_launch_shape(b, d4), [&](auto V, auto BS) {
+        hipLaunchKernelGGL((cat_ln_bwd_k<decltype(V)::value, decltype(BS)::value>), dim3(b), dim3(decltype(BS)::value),
+                           0, st, g, s, resid, ln_w, ln_b, stats, d, dresid, accumulate_mask, dln_w, dln_b, cl4, d4,
+                           relu, scrub, scrub_n / 4);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -482,13 +448,23 @@ int fill_prob(LnAffineProb& P, const float* g, const float* gscale, const float*
   if (resid && n_src != 1) return BMNAS_E_ARG;
   if ((C * L) % 4 != 0) return BMNAS_E_SHAPE;
   P = LnAffineProb{};
-  for (int q = 0; q < n_src; ++q) {
-    if (!srcs[q]) return BMNAS_E_ARG;
-    P.srcs.p[q] = srcs[q];
-  }
+  if (int e = fill_ptrs(P.srcs.p, srcs, n_src)) return e;
   P.g = g; P.gscale = gscale; P.resid = resid; P.ln_w = ln_w; P.ln_b = ln_b; P.stats = stats;
   P.dln_w = dln_w; P.dln_b = dln_b;
   P.cl4 = C * L / 4; P.d4 = P.cl4 * n_src; P.relu = relu; P.prenorm = prenorm;
+  return 0;
+}
+
+// the n problems of the multi-problem entries, element i of every list (a null list: absent for all)
+int fill_probs(LnAffineBatch& B, int n_prob, const float* const* g, const float* const* gscale,
+               const float* const* const* srcs, const int* n_src, const float* const* resid,
+               const float* const* ln_w, const float* const* ln_b, const float* const* stats, float* const* dln_w,
+               float* const* dln_b, const int* C, int L, const int* relu, const int* prenorm) {
+  for (int i = 0; i < n_prob; ++i)
+    if (int e = fill_prob(B.p[i], g[i], gscale ? gscale[i] : nullptr, srcs[i], n_src[i],
+                          resid ? resid[i] : nullptr, ln_w ? ln_w[i] : nullptr, ln_b ? ln_b[i] : nullptr,
+                          stats ? stats[i] : nullptr, dln_w[i], dln_b[i], C[i], L, relu[i], prenorm[i]))
+      return e;
   return 0;
 }
 
@@ -503,11 +479,16 @@ inline int ln_affine_chunk(int b) {
   return b <= 256 ? 16 : (b + 15) / 16;
 }
 
-int launch_ln_affine(LnAffineBatch& B, hipStream_t st) {
+// sets B.chunk; grid of the B.n affine problems: 64 float4 columns x one sample chunk per workgroup, z = problem
+dim3 ln_affine_grid(LnAffineBatch& B) {
   B.chunk = ln_affine_chunk(B.b);
   int maxd4 = 0;
   for (int i = 0; i < B.n; ++i) maxd4 = B.p[i].d4 > maxd4 ? B.p[i].d4 : maxd4;
-  dim3 grid((maxd4 + 63) / 64, (B.b + B.chunk - 1) / B.chunk, B.n);
+  return dim3((maxd4 + 63) / 64, (B.b + B.chunk - 1) / B.chunk, B.n);
+}
+
+int launch_ln_affine(LnAffineBatch& B, hipStream_t st) {
+  const dim3 grid = ln_affine_grid(B);
   hipLaunchKernelGGL(ln_affine_bwd_k, grid, dim3(256), 0, st, B);
   BMNAS_CHECK_LAUNCH();
   return 0;
@@ -539,11 +520,9 @@ extern "C" int bmnas_ln_affine_bwd_multi(int n_prob, const float* const* g, cons
     return BMNAS_E_ARG;
   if (n_prob > kMaxLnProbs) return BMNAS_E_LIMIT;
   LnAffineBatch B{};
-  for (int i = 0; i < n_prob; ++i)
-    if (int e = fill_prob(B.p[i], g[i], gscale ? gscale[i] : nullptr, srcs[i], n_src[i],
-                          resid ? resid[i] : nullptr, ln_w ? ln_w[i] : nullptr, ln_b ? ln_b[i] : nullptr,
-                          stats ? stats[i] : nullptr, dln_w[i], dln_b[i], C[i], L, relu[i], prenorm[i]))
-      return e;
+  if (int e = fill_probs(B, n_prob, g, gscale, srcs, n_src, resid, ln_w, ln_b, stats, dln_w, dln_b, C, L, relu,
+                         prenorm))
+    return e;
   if (b == 0) return 0;
   B.n = n_prob;
   B.b = b;
@@ -572,11 +551,9 @@ extern "C" int bmnas_backward_epilogue(int n_prob, const float* const* g, const 
   }
   S.n = n_sums;
   LnAffineBatch B{};
-  for (int i = 0; i < n_prob; ++i)
-    if (int e = fill_prob(B.p[i], g[i], gscale ? gscale[i] : nullptr, srcs[i], n_src[i],
-                          resid ? resid[i] : nullptr, ln_w ? ln_w[i] : nullptr, ln_b ? ln_b[i] : nullptr,
-                          stats ? stats[i] : nullptr, dln_w[i], dln_b[i], C[i], L, relu[i], prenorm[i]))
-      return e;
+  if (int e = fill_probs(B, n_prob, g, gscale, srcs, n_src, resid, ln_w, ln_b, stats, dln_w, dln_b, C, L, relu,
+                         prenorm))
+    return e;
   ArchPack A{};
   // (n_arch == 0: no architecture tensors — the per-op path's end-of-backward launch: affine reductions + chunk sums)
   const int total = n_arch > 0 ? fill_arch_pack(A, arch_w, arch_dw, arch_out, arch_rows, arch_cols, n_arch, 1, n_shards,
@@ -585,10 +562,7 @@ extern "C" int bmnas_backward_epilogue(int n_prob, const float* const* g, const 
   if (total < 0) return total;
   B.n = n_prob;
   B.b = b;
-  B.chunk = ln_affine_chunk(B.b);
-  int maxd4 = 0;
-  for (int i = 0; i < B.n; ++i) maxd4 = B.p[i].d4 > maxd4 ? B.p[i].d4 : maxd4;
-  dim3 grid((maxd4 + 63) / 64, (B.b + B.chunk - 1) / B.chunk, B.n + 1 + n_sums);
+  dim3 grid = ln_affine_grid(B);                      // (z: set below, once the partial sums' slices are counted)
   // the arch slice needs one wavefront per row, four per workgroup (LayerNorm workgroups past a
   // problem's width return at once, so widening the grid for tiny shapes costs nothing)
   const unsigned need_x = (unsigned)((total + 4 * (int)grid.y - 1) / (4 * (int)grid.y));

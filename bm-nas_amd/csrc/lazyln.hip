@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256) void node_mix_lnp_bwd_k(
 BMNAS_DEFINE_STAMP_SETTER(bmnas_debug_stamps)
 
 extern "C" int bmnas_lazy_ln_ok(int C, int L) {
-  return C >= 1 && (L == 4 || L == 8 || L == 16) && lazy_parts(C * L / 4) <= kLazyMaxParts;
+  return C >= 1 && len_bwd_ok(L) && lazy_parts(C * L / 4) <= kLazyMaxParts;
 }
 
 extern "C" int bmnas_lazy_ln_parts(int C, int L) {
@@ -540,12 +540,11 @@ extern "C" int bmnas_node_mix_pre_fwd(const float* x, const float* y, const floa
                                       bmnas_dropout_t drop_glu, bmnas_dropout_t drop_fc, void* stream) {
   if (!x || !y || !p1 || !U || !chan || !gamma || !resid || !ln_w || !ln_b || !pre || !rec || !prm || b < 0 || C < 1)
     return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;
   BnFin f;
-  if (int e = to_fin(fin, &f)) return e;
-  if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
-  if (C > 4096 / 3 || (3 * C) % 4) return BMNAS_E_LIMIT;   // bn_fin_fill, as bmnas_node_mix_fwd_next
+  if (int e = fin_for(fin, b, L, &f)) return e;
+  if (!fin_lds_ok(3, C)) return BMNAS_E_LIMIT;
   if (b == 0) return 0;
   const int P = lazy_parts(C * L / 4);
   hipLaunchKernelGGL(node_mix_pre_fwd_k, dim3(P, b), dim3(256), (size_t)6 * C * sizeof(float), (hipStream_t)stream,
@@ -566,26 +565,16 @@ extern "C" int bmnas_mixsum_pair_fwd_lazy(const float* const* xs, int n_in, cons
   if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;
   if (b == 0) return 0;
   PtrsIn p{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
   const int cl4 = C * L / 4;
   dim3 grid(lazy_parts(cl4), b);
   hipStream_t st = (hipStream_t)stream;
-#define CALL(N)                                                                                              \
-  hipLaunchKernelGGL(mixsum_pair_fwd_lazy_k<N>, grid, dim3(256), 0, st, p, w, w_stride, w2, w2_stride,       \
-                     last->pre, last->rec, last->prm, last->ln_w, last->ln_b, last_out, last->stats,         \
-                     last_sums, out, out2, cl4)
-  switch (n_in) {
-    case 1: CALL(1); break;   case 2: CALL(2); break;   case 3: CALL(3); break;
-    case 4: CALL(4); break;   case 5: CALL(5); break;   case 6: CALL(6); break;
-    case 7: CALL(7); break;   case 8: CALL(8); break;   case 9: CALL(9); break;
-    case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break;
-    case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break;
-    default: return BMNAS_E_LIMIT;
-  }
-#undef CALL
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS - 1>(n_in, [&](auto N) {
+        hipLaunchKernelGGL(mixsum_pair_fwd_lazy_k<decltype(N)::value>, grid, dim3(256), 0, st, p, w, w_stride, w2,
+                           w2_stride, last->pre, last->rec, last->prm, last->ln_w, last->ln_b, last_out, last->stats,
+                           last_sums, out, out2, cl4);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -608,11 +597,8 @@ extern "C" int bmnas_mixsum_pair_bwd_lazy(const float* const* xs, float* const* 
   if (b == 0) return 0;
   PtrsIn p{};
   PtrsOut d{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-    d.p[j] = dxs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
+  fill_ptrs_out(d.p, dxs, n_in);
   LazyIn Z{};
   for (int t = 0; t < n_lazy; ++t) {
     if (!lazy[t].pre || !lazy[t].ln_w || !lazy[t].stats || !lnpart[t]) return BMNAS_E_ARG;
@@ -628,32 +614,20 @@ extern "C" int bmnas_mixsum_pair_bwd_lazy(const float* const* xs, float* const* 
   const int cl4 = C * L / 4;
   dim3 grid(lazy_parts(cl4), b);
   hipStream_t st = (hipStream_t)stream;
-#define CALL2(N, Z_)                                                                                                 \
-  do {                                                                                                               \
-    if (dots)                                                                                                        \
-      hipLaunchKernelGGL((mixsum_pair_bwd_lazy_k<N, Z_, true>), grid, dim3(256), 0, st, p, d, w, w_stride, w2,       \
-                         w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards, dw_shard_stride, accumulate_mask, Z, g_full, \
-                         cl4);                                                                                       \
-    else                                                                                                             \
-      hipLaunchKernelGGL((mixsum_pair_bwd_lazy_k<N, Z_, false>), grid, dim3(256), 0, st, p, d, w, w_stride, w2,      \
-                         w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards, dw_shard_stride, accumulate_mask, Z, g_full, \
-                         cl4);                                                                                       \
-  } while (0)
-#define CALL(N)                            \
-  do {                                     \
-    if (n_lazy == 1) CALL2(N, 1);          \
-    else CALL2(N, 2);                      \
-  } while (0)
-  switch (n_in) {
-    case 2: CALL2(2, 1); break;
-    case 3: CALL(3); break;   case 4: CALL(4); break;   case 5: CALL(5); break;   case 6: CALL(6); break;
-    case 7: CALL(7); break;   case 8: CALL(8); break;   case 9: CALL(9); break;   case 10: CALL(10); break;
-    case 11: CALL(11); break; case 12: CALL(12); break; case 13: CALL(13); break; case 14: CALL(14); break;
-    case 15: CALL(15); break;
-    default: return BMNAS_E_LIMIT;
-  }
-#undef CALL
-#undef CALL2
+  // (n_lazy < n_in: two inputs leave room for one lazy input only)
+  if (int e = dispatch_range<2, BMNAS_MAX_PTRS - 1>(n_in, [&](auto N) {
+        auto launch = [&](auto NZ) {
+          dispatch_bool(dots, [&](auto DOTS) {
+            hipLaunchKernelGGL(
+                (mixsum_pair_bwd_lazy_k<decltype(N)::value, decltype(NZ)::value, decltype(DOTS)::value>), grid,
+                dim3(256), 0, st, p, d, w, w_stride, w2, w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards,
+                dw_shard_stride, accumulate_mask, Z, g_full, cl4);
+          });
+        };
+        if constexpr (decltype(N)::value == 2) launch(int_c<1>{});
+        else dispatch_range<1, kMaxLazyIn>(n_lazy, launch);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -670,7 +644,7 @@ extern "C" int bmnas_node_mix_lnp_bwd(const float* g, const float* pre, const fl
       C < 1 || dgamma_shards < 1 || n0 < 0 || n1 < 0 || (n0 > 0 && !lnp0) || (n1 > 0 && !lnp1) || n0 + n1 < 1)
     return BMNAS_E_ARG;
   if (accumulate_resid && !dresid) return BMNAS_E_ARG;
-  if (!(L == 4 || L == 8 || L == 16)) return BMNAS_E_SHAPE;
+  if (!len_bwd_ok(L)) return BMNAS_E_SHAPE;
   if (!bmnas_lazy_ln_ok(C, L)) return BMNAS_E_LIMIT;             // (pre / stats come from the producer's family)
   if (b == 0) return 0;
   const int cl4 = C * L / 4;
@@ -680,19 +654,13 @@ extern "C" int bmnas_node_mix_lnp_bwd(const float* g, const float* pre, const fl
   dim3 grid((cl4 + 63) / 64, (b + chunk - 1) / chunk);
   // partial pairs per lane, a compile-time count up to 4 (256 pairs); 0 = the loop form above that
   const int npl = (n0 + n1 + 63) / 64;
-#define CALL(N)                                                                                                     \
-  hipLaunchKernelGGL(node_mix_lnp_bwd_k<N>, grid, dim3(256), 0, (hipStream_t)stream, g, pre, ln_w, stats, lnp0, n0, \
-                     lnp1, n1, g_in, dresid, accumulate_resid, x, y, p1, U, chan, gamma, dgamma, dgamma_shards,     \
-                     dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, bn_part, b, C, L, chunk,            \
-                     to_cfg(drop_glu), to_cfg(drop_fc))
-  switch (npl) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 3: CALL(3); break;
-    case 4: CALL(4); break;
-    default: CALL(0); break;
-  }
-#undef CALL
+  auto launch = [&](auto N) {
+    hipLaunchKernelGGL(node_mix_lnp_bwd_k<decltype(N)::value>, grid, dim3(256), 0, (hipStream_t)stream, g, pre, ln_w,
+                       stats, lnp0, n0, lnp1, n1, g_in, dresid, accumulate_resid, x, y, p1, U, chan, gamma, dgamma,
+                       dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, bn_part, b, C, L,
+                       chunk, to_cfg(drop_glu), to_cfg(drop_fc));
+  };
+  if (dispatch_range<1, 4>(npl, launch)) launch(int_c<0>{});
   BMNAS_CHECK_LAUNCH();
   if (bn_part != nullptr)      // rows in order -> bn_grad (6 C floats per row; C % 16 == 0)
     return bmnas_sum_chunks(bn_part, bn_grad, (int)grid.y, (int64_t)6 * C, stream);

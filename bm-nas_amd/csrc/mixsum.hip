@@ -5,6 +5,7 @@
 // Algorithmic bytes: fwd (n_in + 1) * T, bwd (2 * n_in + 1) * T, T = n_elem * 4.
 #include "common.hpp"
 #include "../../include/bmnas_hip.h"
+#include "launch.hpp"
 
 namespace {
 
@@ -317,35 +318,7 @@ __global__ __launch_bounds__(256) void mixsum_pair_bwd_x_k(PtrsIn xs, PtrsOut dx
   }
 }
 
-inline int grid_for(int64_t n4) {
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 }  // namespace
-
-#define MIXSUM_DISPATCH(N, CALL) \
-  switch (N) {                   \
-    case 1: CALL(1); break;      \
-    case 2: CALL(2); break;      \
-    case 3: CALL(3); break;      \
-    case 4: CALL(4); break;      \
-    case 5: CALL(5); break;      \
-    case 6: CALL(6); break;      \
-    case 7: CALL(7); break;      \
-    case 8: CALL(8); break;      \
-    case 9: CALL(9); break;      \
-    case 10: CALL(10); break;    \
-    case 11: CALL(11); break;    \
-    case 12: CALL(12); break;    \
-    case 13: CALL(13); break;    \
-    case 14: CALL(14); break;    \
-    case 15: CALL(15); break;    \
-    case 16: CALL(16); break;    \
-    default: return BMNAS_E_LIMIT; \
-  }
 
 extern "C" int bmnas_mixsum_fwd(const float* const* xs, int n_in, const float* w, int w_stride,
                                 float* out, int64_t n_elem, void* stream) {
@@ -354,15 +327,14 @@ extern "C" int bmnas_mixsum_fwd(const float* const* xs, int n_in, const float* w
   if (n_elem % 4 != 0) return BMNAS_E_SHAPE;
   if (n_elem == 0) return 0;
   PtrsIn p{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
   const int64_t n4 = n_elem / 4;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(N) hipLaunchKernelGGL(mixsum_fwd_k<N>, dim3(grid_for(n4)), dim3(256), 0, st, p, w, w_stride, out, n4)
-  MIXSUM_DISPATCH(n_in, CALL)
-#undef CALL
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS>(n_in, [&](auto N) {
+        hipLaunchKernelGGL(mixsum_fwd_k<decltype(N)::value>, dim3(stream_grid(n4)), dim3(256), 0, st, p, w, w_stride,
+                           out, n4);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -378,16 +350,15 @@ extern "C" int bmnas_mixsum_bwd(const float* const* xs, float* const* dxs, int n
   if (n_elem == 0) return 0;
   PtrsIn p{};
   PtrsOut d{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-    d.p[j] = dxs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
+  fill_ptrs_out(d.p, dxs, n_in);
   const int64_t n4 = n_elem / 4;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(N) hipLaunchKernelGGL(mixsum_bwd_k<N>, dim3(grid_for(n4)), dim3(256), 0, st, p, d, w, w_stride, g, g2, dw, dw_shards, dw_shard_stride, accumulate_mask, n4)
-  MIXSUM_DISPATCH(n_in, CALL)
-#undef CALL
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS>(n_in, [&](auto N) {
+        hipLaunchKernelGGL(mixsum_bwd_k<decltype(N)::value>, dim3(stream_grid(n4)), dim3(256), 0, st, p, d, w,
+                           w_stride, g, g2, dw, dw_shards, dw_shard_stride, accumulate_mask, n4);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -401,15 +372,14 @@ extern "C" int bmnas_mixsum_pair_fwd(const float* const* xs, int n_in, const flo
   if (n_elem % 4 != 0) return BMNAS_E_SHAPE;
   if (n_elem == 0) return 0;
   PtrsIn p{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
   const int64_t n4 = n_elem / 4;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(N) hipLaunchKernelGGL(mixsum_pair_fwd_k<N>, dim3(grid_for(n4)), dim3(256), 0, st, p, w, w_stride, w2, w2_stride, out, out2, n4)
-  MIXSUM_DISPATCH(n_in, CALL)
-#undef CALL
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS>(n_in, [&](auto N) {
+        hipLaunchKernelGGL(mixsum_pair_fwd_k<decltype(N)::value>, dim3(stream_grid(n4)), dim3(256), 0, st, p, w,
+                           w_stride, w2, w2_stride, out, out2, n4);
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -430,31 +400,18 @@ extern "C" int bmnas_mixsum_pair_bwd(const float* const* xs, float* const* dxs, 
   if (n_elem == 0) return 0;
   PtrsIn p{};
   PtrsOut d{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-    d.p[j] = dxs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
+  fill_ptrs_out(d.p, dxs, n_in);
   const int64_t n4 = n_elem / 4;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(N)                                                                                                    \
-  do {                                                                                                             \
-    if (dots)                                                                                                      \
-      hipLaunchKernelGGL((mixsum_pair_bwd_k<N, true>), dim3(grid_for(n4)), dim3(256), 0, st, p, d, w, w_stride,    \
-                         w2, w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards, dw_shard_stride, accumulate_mask, n4); \
-    else                                                                                                           \
-      hipLaunchKernelGGL((mixsum_pair_bwd_k<N, false>), dim3(grid_for(n4)), dim3(256), 0, st, p, d, w, w_stride,   \
-                         w2, w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards, dw_shard_stride, accumulate_mask, n4); \
-  } while (0)
-  switch (n_in) {
-    case 1: CALL(1); break;   case 2: CALL(2); break;   case 3: CALL(3); break;
-    case 4: CALL(4); break;   case 5: CALL(5); break;   case 6: CALL(6); break;
-    case 7: CALL(7); break;   case 8: CALL(8); break;   case 9: CALL(9); break;
-    case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break;
-    case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break;
-    default: return BMNAS_E_LIMIT;
-  }
-#undef CALL
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS - 1>(n_in, [&](auto N) {
+        dispatch_bool(dots, [&](auto DOTS) {
+          hipLaunchKernelGGL((mixsum_pair_bwd_k<decltype(N)::value, decltype(DOTS)::value>), dim3(stream_grid(n4)),
+                             dim3(256), 0, st, p, d, w, w_stride, w2, w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards,
+                             dw_shard_stride, accumulate_mask, n4);
+        });
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -479,11 +436,8 @@ extern "C" int bmnas_mixsum_pair_bwd_x(const float* const* xs, float* const* dxs
   if (n_elem == 0) return 0;
   PtrsIn p{};
   PtrsOut d{};
-  for (int j = 0; j < n_in; ++j) {
-    if (!xs[j]) return BMNAS_E_ARG;
-    p.p[j] = xs[j];
-    d.p[j] = dxs[j];
-  }
+  if (int e = fill_ptrs(p.p, xs, n_in)) return e;
+  fill_ptrs_out(d.p, dxs, n_in);
   MoreG X{};
   for (int t = 0; t < n_more; ++t) {
     if (!g_more[t] || !w_more[t]) return BMNAS_E_ARG;
@@ -492,32 +446,16 @@ extern "C" int bmnas_mixsum_pair_bwd_x(const float* const* xs, float* const* dxs
   }
   const int64_t n4 = n_elem / 4;
   hipStream_t st = (hipStream_t)stream;
-#define CALL2(N, X_)                                                                                                \
-  do {                                                                                                              \
-    if (dots)                                                                                                       \
-      hipLaunchKernelGGL((mixsum_pair_bwd_x_k<N, X_, true>), dim3(grid_for(n4)), dim3(256), 0, st, p, d, w,         \
-                         w_stride, w2, w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards, dw_shard_stride,              \
-                         accumulate_mask, X, n4);                                                                   \
-    else                                                                                                            \
-      hipLaunchKernelGGL((mixsum_pair_bwd_x_k<N, X_, false>), dim3(grid_for(n4)), dim3(256), 0, st, p, d, w,        \
-                         w_stride, w2, w2_stride, h, gh, gz, gz2, dw, dw2, dw_shards, dw_shard_stride,              \
-                         accumulate_mask, X, n4);                                                                   \
-  } while (0)
-#define CALL(N)                   \
-  do {                            \
-    if (n_more == 1) CALL2(N, 1); \
-    else CALL2(N, 2);             \
-  } while (0)
-  switch (n_in) {
-    case 1: CALL(1); break;   case 2: CALL(2); break;   case 3: CALL(3); break;
-    case 4: CALL(4); break;   case 5: CALL(5); break;   case 6: CALL(6); break;
-    case 7: CALL(7); break;   case 8: CALL(8); break;   case 9: CALL(9); break;
-    case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break;
-    case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break;
-    default: return BMNAS_E_LIMIT;
-  }
-#undef CALL
-#undef CALL2
+  if (int e = dispatch_range<1, BMNAS_MAX_PTRS - 1>(n_in, [&](auto N) {
+        dispatch_range<1, kMaxMoreG>(n_more, [&](auto NX) {
+          dispatch_bool(dots, [&](auto DOTS) {
+            hipLaunchKernelGGL((mixsum_pair_bwd_x_k<decltype(N)::value, decltype(NX)::value, decltype(DOTS)::value>),
+                               dim3(stream_grid(n4)), dim3(256), 0, st, p, d, w, w_stride, w2, w2_stride, h, gh, gz,
+                               gz2, dw, dw2, dw_shards, dw_shard_stride, accumulate_mask, X, n4);
+          });
+        });
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

@@ -207,23 +207,20 @@ extern "C" int bmnas_node_mix_sel_ok(int mask, int b, int C, int L) {
   const bool attn = mask & kAttn, conv = mask & (kGlu | kFc);
   // the attention kernels and the conv GEMMs tile 16 (sample, l) columns and 16 channels; the BatchNorm row
   // reductions of the backward walk L / 4 in {1, 2, 4} adjacent lanes
-  if ((attn || conv) && !(L == 4 || L == 8 || L == 16)) return 0;
+  if ((attn || conv) && !len_bwd_ok(L)) return 0;
   if ((attn || conv) && C % 16) return 0;
   if (attn && C > 512) return 0;
   if (conv && sel_rows(mask) * C > 4096) return 0;        // scale | shift of every conv row sit in LDS
   return 1;
 }
 
-// ReLU: all 15 masks; Mish: the 8 masks with the FC slot (mask | 16 in the switch)
-#define SEL_SWITCH(CASE)                                                                                    \
-  switch (fc_act == kActMish ? (mask | 16) : mask) {                                                        \
-    CASE(1, kActRelu) CASE(2, kActRelu) CASE(3, kActRelu) CASE(4, kActRelu) CASE(5, kActRelu)               \
-    CASE(6, kActRelu) CASE(7, kActRelu) CASE(8, kActRelu) CASE(9, kActRelu) CASE(10, kActRelu)              \
-    CASE(11, kActRelu) CASE(12, kActRelu) CASE(13, kActRelu) CASE(14, kActRelu) CASE(15, kActRelu)          \
-    CASE(8, kActMish) CASE(9, kActMish) CASE(10, kActMish) CASE(11, kActMish) CASE(12, kActMish)            \
-    CASE(13, kActMish) CASE(14, kActMish) CASE(15, kActMish)                                                \
-    default: return BMNAS_E_ARG;                                                                            \
-  }
+// f(int_c<mask>, int_c<fc_act>) for the 23 instantiated pairs — ReLU: all 15 masks; Mish: the 8 masks with the FC slot
+template <class F>
+static int dispatch_sel(int mask, int fc_act, F&& f) {
+  const int e = fc_act != kActMish ? dispatch_range<1, 15>(mask, [&](auto M) { f(M, int_c<kActRelu>{}); })
+                                   : dispatch_range<8, 15>(mask, [&](auto M) { f(M, int_c<kActMish>{}); });
+  return e ? BMNAS_E_ARG : 0;
+}
 
 extern "C" int bmnas_node_mix_sel_act_fwd(const float* x, const float* y, const float* p1, const float* U,
                                           float* chan, bmnas_bn_fin_t fin, const float* gamma, bmnas_node_sel_t sel,
@@ -242,19 +239,16 @@ extern "C" int bmnas_node_mix_sel_act_fwd(const float* x, const float* y, const 
   if (M > 0 && (!U || !chan)) return BMNAS_E_ARG;
   BnFin f{};
   if (M > 0) {
-    if (int e = to_fin(fin, &f)) return e;
-    if (f.on && f.training && b * L < 2) return BMNAS_E_ARG;
+    if (int e = fin_for(fin, b, L, &f)) return e;
   }
   if (b == 0) return 0;
   const int64_t total = (int64_t)b * C * L / 4;
-#define CASE(Mv, Av)                                                                                        \
-  case Mv | (Av << 4):                                                                                      \
-    hipLaunchKernelGGL((node_mix_sel_fwd_k<Mv, Av>), dim3(stream_grid(total)), dim3(256),                   \
-                       (size_t)2 * M * sizeof(float), (hipStream_t)stream, x, y, p1, U, chan, f, gamma, s, out, b, \
-                       C, L, to_cfg(drop_glu), to_cfg(drop_fc));                                            \
-    break;
-  SEL_SWITCH(CASE)
-#undef CASE
+  if (int e = dispatch_sel(mask, fc_act, [&](auto Mk, auto Act) {
+        hipLaunchKernelGGL((node_mix_sel_fwd_k<decltype(Mk)::value, decltype(Act)::value>), dim3(stream_grid(total)),
+                           dim3(256), (size_t)2 * M * sizeof(float), (hipStream_t)stream, x, y, p1, U, chan, f, gamma,
+                           s, out, b, C, L, to_cfg(drop_glu), to_cfg(drop_fc));
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }
@@ -289,14 +283,13 @@ extern "C" int bmnas_node_mix_sel_act_bwd(const float* g, const float* x, const 
   const int cl4 = C * L / 4;
   const int chunk = pick_chunk(b, cl4);
   dim3 grid((cl4 + 63) / 64, (b + chunk - 1) / chunk);
-#define CASE(Mv, Av)                                                                                        \
-  case Mv | (Av << 4):                                                                                      \
-    hipLaunchKernelGGL((node_mix_sel_bwd_k<Mv, Av>), grid, dim3(256), 0, (hipStream_t)stream, g, x, y, p1, U, chan, \
-                       gamma, s, dgamma, dgamma_shards, dgamma_shard_stride, dx, dy, accumulate_mask, dV,    \
-                       bn_grad, b, C, L, chunk, to_cfg(drop_glu), to_cfg(drop_fc));                         \
-    break;
-  SEL_SWITCH(CASE)
-#undef CASE
+  if (int e = dispatch_sel(mask, fc_act, [&](auto Mk, auto Act) {
+        hipLaunchKernelGGL((node_mix_sel_bwd_k<decltype(Mk)::value, decltype(Act)::value>), grid, dim3(256), 0,
+                           (hipStream_t)stream, g, x, y, p1, U, chan, gamma, s, dgamma, dgamma_shards,
+                           dgamma_shard_stride, dx, dy, accumulate_mask, dV, bn_grad, b, C, L, chunk, to_cfg(drop_glu),
+                           to_cfg(drop_fc));
+      }))
+    return e;
   BMNAS_CHECK_LAUNCH();
   return 0;
 }

@@ -1,6 +1,6 @@
 """CPU: the host contract of the BatchNorm entry points of csrc/bnmix.hip — which return code bmnas_bn_finalize, the
 three forward tails (bmnas_bn_relu_fwd, _mish_fwd, _glu_fwd), the three backward tails, the two grouped entries and
-bmnas_bn_bwd_apply give for a refused argument, and what the descriptor conversion (to_fin, csrc/mix_common.hpp)
+bmnas_bn_bwd_apply give for a refused argument, and what the descriptor conversion (to_fin, csrc/launch.hpp)
 refuses through each forward entry.
 
 Every call here returns before any HIP call: b = 0 with valid arguments, or exactly one refused argument.  Only

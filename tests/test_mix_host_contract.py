@@ -2,7 +2,7 @@
 bmnas_node_mix_ln_fwd, bmnas_node_mix_pre_fwd, bmnas_node_mix_bwd_next, bmnas_node_mix_ln_bwd,
 bmnas_node_mix_sel_act_fwd / _bwd and bmnas_node_mix_conv_fwd: which return code each gives for a refused argument, in
 which order (BMNAS_E_ARG -1, then BMNAS_E_SHAPE -2, then BMNAS_E_LIMIT -3), and what the descriptor conversion (to_fin,
-csrc/mix_common.hpp) refuses through each forward entry.
+csrc/launch.hpp) refuses through each forward entry.
 
 Every call here returns before any HIP call: b = 0 with valid arguments, or an argument that the entry refuses (the
 order rows carry two, and show which one wins).  The only rows with b > 0 are refusals that the entry makes AFTER its
