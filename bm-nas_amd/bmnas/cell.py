@@ -179,6 +179,13 @@ class Pack:
         self.__dict__.update(kw)
 
 
+def pack_momentum(P, name):
+    """The BatchNorm momentum a parameter pack carries under `name` (stack_mom: the stacked LinearGLU + FC-slot
+    BatchNorms of a NodeMixedOp, bn_mom: the out_conv BatchNorm of a NodeCell); a pack built without one means
+    nn.BatchNorm1d's default."""
+    return getattr(P, name, 0.1)
+
+
 class HeadState(Pack):
     """What the fused head (csrc/head.hip) shares between the cell's forward, the criterion and the
     backward: classifier weights, the zero-filled hb = logits | A | B buffer, the loss scalar, and —
@@ -299,11 +306,13 @@ class StatArena:
 
 
 def conv_bn_fwd(srcs, C_src, W, ldw, bias, bn_w, bn_b, rm, rv, nbt, training, dup=0, fold=0, attn=None,
-                stats=None):
+                stats=None, momentum=0.1):
     """U = conv1x1(cat(srcs)) (+ batch statistics) and the fused BN affine `chan`.
     W is (M, ldw) row-major with the first len(srcs)*C_src columns used.
     stats: a StatArena -> the statistics are finalised by the CONSUMER kernel (sv.fin is the
-    descriptor to hand to it; `chan` is written by that kernel); None -> bmnas_bn_finalize here."""
+    descriptor to hand to it; `chan` is written by that kernel); None -> bmnas_bn_finalize here.
+    momentum: the owning nn.BatchNorm1d's (a float, or None: cumulative average) — it reaches the running
+    statistics only."""
     x0 = srcs[0]
     b, L = x0.shape[0], x0.shape[2]
     M = bn_w.numel()
@@ -325,10 +334,10 @@ def conv_bn_fwd(srcs, C_src, W, ldw, bias, bn_w, bn_b, rm, rv, nbt, training, du
     chan = _empty(x0, 4 * M)
     sv = ConvBnSaved()
     if stats is not None:
-        sv.fin = lib.make_bn_fin(part, shards, bias, bn_w, bn_b, rm, rv, nbt, training)
+        sv.fin = lib.make_bn_fin(part, shards, bias, bn_w, bn_b, rm, rv, nbt, training, momentum)
     else:
         sv.fin = lib.NO_FIN
-        lib.bn_finalize(part, n_part, b, L, M, bn_w, bn_b, rm, rv, nbt, training, chan)
+        lib.bn_finalize(part, n_part, b, L, M, bn_w, bn_b, rm, rv, nbt, training, chan, momentum)
     sv.srcs, sv.C_src, sv.W, sv.ldw, sv.U, sv.chan, sv.M = list(srcs), C_src, W, ldw, U, chan, M
     sv.training, sv.dup, sv.fold = training, dup, fold
     bn_ratio_note(chan, bias, M, f'conv {len(srcs)}x{C_src}->{M}', training)
@@ -549,11 +558,11 @@ def _mixed_conv_fwd(sv, x, y, same, P, training, C, attn=None, Weff=None, stats=
             lib.fold_weight(P.stack_W, Weff, M, C)
         U, chan, sv.conv = conv_bn_fwd([x], C, Weff, C, P.stack_bias, P.stack_bn_w, P.stack_bn_b,
                                        P.stack_rm, P.stack_rv, P.stack_nbt, training, dup=C, attn=attn,
-                                       stats=stats)
+                                       stats=stats, momentum=pack_momentum(P, 'stack_mom'))
     else:
         U, chan, sv.conv = conv_bn_fwd([x, y], C, P.stack_W, 2 * C, P.stack_bias, P.stack_bn_w,
                                        P.stack_bn_b, P.stack_rm, P.stack_rv, P.stack_nbt, training,
-                                       stats=stats)
+                                       stats=stats, momentum=pack_momentum(P, 'stack_mom'))
     return U, chan
 
 
@@ -787,7 +796,8 @@ def _mix_conv_fwd(pending, tail, C, Wo, ldw, NP, training, stats):
     lib.node_mix_conv_fwd(x, y, p1, U, chan_mix, gamma_row, out, d_glu, d_fc, fin, tail[:-1], Wo, ldw,
                           NP.out_conv_b, V, part, shards, b, C, L)
     sv = ConvBnSaved()
-    sv.fin = lib.make_bn_fin(part, shards, NP.out_conv_b, NP.bn_w, NP.bn_b, NP.bn_rm, NP.bn_rv, NP.bn_nbt, training)
+    sv.fin = lib.make_bn_fin(part, shards, NP.out_conv_b, NP.bn_w, NP.bn_b, NP.bn_rm, NP.bn_rv, NP.bn_nbt, training,
+                             pack_momentum(NP, 'bn_mom'))
     sv.srcs, sv.C_src, sv.W, sv.ldw, sv.U, sv.chan, sv.M = list(tail), C, Wo, ldw, V, _empty(x, 4 * C), C
     sv.training, sv.dup, sv.fold = training, 0, 0
     bn_ratio_note(sv.chan, NP.out_conv_b, C, f'out_conv {len(tail)}x{C}->{C}', training)
@@ -849,7 +859,8 @@ def node_cell_fwd(x, y, beta_w, gamma_w, NP, training, ns, nm, z0=None, weffs=No
             V, chan, sv.oconv = _mix_conv_fwd(pending, tail, C, Wo, nm * C, NP, training, stats)
         else:
             V, chan, sv.oconv = conv_bn_fwd(tail, C, Wo, nm * C, NP.out_conv_b, NP.bn_w, NP.bn_b,
-                                            NP.bn_rm, NP.bn_rv, NP.bn_nbt, training, stats=stats)
+                                            NP.bn_rm, NP.bn_rv, NP.bn_nbt, training, stats=stats,
+                                            momentum=pack_momentum(NP, 'bn_mom'))
         sv.d_out = DROP.make(NP.out_p, x.numel(), training)
         o = torch.empty_like(x)
         sv.fused_bn_tail = FUSE_BN_TAIL and b <= BN_TAIL_MAX_B and C <= 1024

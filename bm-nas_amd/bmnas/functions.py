@@ -618,7 +618,7 @@ class ConvBnActFn(Function):
     (node_search.py:59-64).  bn buffers are updated in place in training mode."""
 
     @staticmethod
-    def forward(ctx, act, p, training, rm, rv, nbt, conv_w, conv_b, bn_w, bn_b, *srcs):
+    def forward(ctx, act, p, training, rm, rv, nbt, momentum, conv_w, conv_b, bn_w, bn_b, *srcs):
         _require_gpu(srcs[0], 'conv1x1 + BatchNorm')
         if act not in ('glu', 'relu', 'mish'):               # before anything is launched or a buffer is updated
             raise ValueError(f'conv1x1 + BatchNorm: no kernel for the activation {act!r}')
@@ -632,7 +632,7 @@ class ConvBnActFn(Function):
             pool = FWD_STAT_POOL             # statistics finalised inside bn_relu_fwd / bn_glu_fwd (no bn_finalize launch)
             pool.device = srcs[0].device
         U, chan, sv = K.conv_bn_fwd(srcs, C_src, W, K_in, _c(conv_b), _c(bn_w), _c(bn_b), rm, rv, nbt,
-                                    training, stats=pool)
+                                    training, stats=pool, momentum=momentum)
         if act == 'glu':
             Cout = M // 2
             out = torch.empty((b, Cout, L), device=U.device, dtype=torch.float32)
@@ -666,10 +666,10 @@ class ConvBnActFn(Function):
             lib.bn_mish_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
         else:
             lib.bn_relu_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
-        slots = [K.GradSlot(s) if ctx.needs_input_grad[10 + q] else None for q, s in enumerate(sv.srcs)]
+        slots = [K.GradSlot(s) if ctx.needs_input_grad[11 + q] else None for q, s in enumerate(sv.srcs)]
         K.conv_bn_bwd(sv, dV, bn_grad, slots, dW, dbias)
         dsrcs = [s.get() if s is not None else None for s in slots]
-        return (None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:],
+        return (None, None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:],
                 *dsrcs)
 
 
@@ -683,8 +683,8 @@ class ConvBnActThruFn(Function):
     reader's backward, which nothing else holds — no retain_grad / hooks on these inner tensors.)"""
 
     @staticmethod
-    def forward(ctx, act, p, training, rm, rv, nbt, conv_w, conv_b, bn_w, bn_b, *srcs):
-        out = ConvBnActFn.forward(ctx, act, p, training, rm, rv, nbt, conv_w, conv_b, bn_w, bn_b, *srcs)
+    def forward(ctx, act, p, training, rm, rv, nbt, momentum, conv_w, conv_b, bn_w, bn_b, *srcs):
+        out = ConvBnActFn.forward(ctx, act, p, training, rm, rv, nbt, momentum, conv_w, conv_b, bn_w, bn_b, *srcs)
         ctx.set_materialize_grads(False)
         return (out, *[s.view_as(s) for s in srcs])
 
@@ -693,7 +693,7 @@ class ConvBnActThruFn(Function):
         sv, act = ctx.sv, ctx.act
         n = len(sv.srcs)
         if g is None:                       # only the handed-back sources were differentiated: identity
-            return (None,) * 10 + tuple(g_thru)
+            return (None,) * 11 + tuple(g_thru)
         U = sv.U
         b, M, L = U.shape
         g = _c(g)
@@ -711,7 +711,7 @@ class ConvBnActThruFn(Function):
         slots = []
         for q, s in enumerate(sv.srcs):
             gt = g_thru[q] if q < len(g_thru) else None
-            if not ctx.needs_input_grad[10 + q]:
+            if not ctx.needs_input_grad[11 + q]:
                 slots.append(None)
                 continue
             slot = K.GradSlot(s)
@@ -726,7 +726,8 @@ class ConvBnActThruFn(Function):
             if slot is not None and gt is not None and d is not gt:
                 d = gt if d is None else d + gt          # (a non-contiguous arrival: the engine's way)
             dsrcs.append(d)
-        return (None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:], *dsrcs)
+        return (None, None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:],
+                *dsrcs)
 
 
 class ConvBnReluLnFn(Function):
@@ -742,7 +743,7 @@ class ConvBnReluLnFn(Function):
         return K.FUSE_BN_TAIL and b <= K.BN_TAIL_MAX_B and C <= 1024
 
     @staticmethod
-    def forward(ctx, p, training, want_sums, rm, rv, nbt, conv_w, conv_b, bn_w, bn_b, ln_w, ln_b, x, *srcs):
+    def forward(ctx, p, training, want_sums, rm, rv, nbt, momentum, conv_w, conv_b, bn_w, bn_b, ln_w, ln_b, x, *srcs):
         _require_gpu(srcs[0], 'conv1x1 + BatchNorm + LayerNorm tail')
         srcs = [_c(_f32(s)) for s in srcs]
         x = _c(_f32(x))
@@ -755,7 +756,7 @@ class ConvBnReluLnFn(Function):
             pool = FWD_STAT_POOL
             pool.device = srcs[0].device
         U, chan, sv = K.conv_bn_fwd(srcs, C_src, W, K_in, _c(conv_b), _c(bn_w), _c(bn_b), rm, rv, nbt,
-                                    training, stats=pool)
+                                    training, stats=pool, momentum=momentum)
         o = torch.empty_like(x)                  # dropout(relu(bn(U))), saved for the backward
         out = torch.empty_like(x)
         stats = torch.empty(b * 2, device=x.device, dtype=torch.float32)
@@ -775,7 +776,7 @@ class ConvBnReluLnFn(Function):
     @staticmethod
     def backward(ctx, g, _g_sums):
         sv = ctx.sv
-        n_in = 13 + len(sv.srcs)
+        n_in = 14 + len(sv.srcs)
         if g is None:
             return (None,) * n_in
         U, x = sv.U, ctx.x
@@ -786,16 +787,17 @@ class ConvBnReluLnFn(Function):
         bn_grad = zero[:2 * M]
         dW = zero[2 * M:2 * M + M * sv.ldw].view(M, sv.ldw)
         dbias = zero[2 * M + M * sv.ldw:]
-        dx = torch.empty_like(x) if ctx.needs_input_grad[12] else None
+        dx = torch.empty_like(x) if ctx.needs_input_grad[13] else None
         dlw, dlb = _zero_pair(ctx.lw)
         # LayerNorm input gradient, ReLU / dropout mask, BatchNorm reductions and the residual's gradient: one launch
         lib.bn_relu_ln_bwd(g, ctx.o, x, ctx.lw, ctx.stats, U, sv.chan, dV, bn_grad, dx, 0, b, M, L, ctx.drop)
-        slots = [K.GradSlot(s) if ctx.needs_input_grad[13 + q] else None for q, s in enumerate(sv.srcs)]
+        slots = [K.GradSlot(s) if ctx.needs_input_grad[14 + q] else None for q, s in enumerate(sv.srcs)]
         K.conv_bn_bwd(sv, dV, bn_grad, slots, dW, dbias)
         _ln_affine(g, [ctx.o], x, ctx.lw, ctx.lb, ctx.stats, dlw, dlb, b, M, L, False, False,
                    key=ctx.lw.data_ptr(), leaf=ctx.leaf)
         dsrcs = [s.get() if s is not None else None for s in slots]
-        return (None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:], dlw, dlb, dx,
+        return (None, None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:], dlw, dlb,
+                dx,
                 *dsrcs)
 
 
@@ -875,7 +877,8 @@ class ReshapeGroupFn(Function):
         outs = [torch.empty((b, M, L), device=dev, dtype=torch.float32) for _ in range(n)]
         drops = [K.DROP.make(p, outs[i].numel(), training) for i in range(n)]
         fins = [lib.make_bn_fin(None if stats is None else stats[i], shards, cbs[i], _c(prm[i][2]), _c(prm[i][3]),
-                                buffers[i][0], buffers[i][1], buffers[i][2], training) for i in range(n)]
+                                buffers[i][0], buffers[i][1], buffers[i][2], training,
+                                momentum=buffers[i][3] if len(buffers[i]) > 3 else 0.1) for i in range(n)]
         lib.bn_relu_fwd_group(Us, chans, outs, fins, drops, b, M, L)
         ctx.n, ctx.xs, ctx.Ws, ctx.Us, ctx.chans, ctx.drops, ctx.training = n, xs, Ws, Us, chans, drops, training
         for i in range(n):

@@ -57,10 +57,25 @@ class BnFin(C.Structure):
     """bmnas_bn_fin_t"""
     _fields_ = [('stat', C.c_void_p), ('conv_bias', C.c_void_p), ('bn_w', C.c_void_p), ('bn_b', C.c_void_p),
                 ('running_mean', C.c_void_p), ('running_var', C.c_void_p), ('num_batches_tracked', C.c_void_p),
-                ('shards', C.c_int), ('n_nbt', C.c_int), ('training', C.c_int), ('on', C.c_int)]
+                ('shards', C.c_int), ('n_nbt', C.c_int), ('training', C.c_int), ('on', C.c_int),
+                ('momentum', C.c_float), ('momentum_mode', C.c_int)]
 
 
 NO_FIN = BnFin()
+
+BN_MOM_DEFAULT, BN_MOM_VALUE, BN_MOM_CUMULATIVE = 0, 1, 2
+
+
+def bn_momentum(momentum):
+    """nn.BatchNorm1d.momentum -> (momentum, momentum_mode) of bmnas_bn_fin_t / bmnas_bn_finalize_ex: 0.1 is the
+    kernels' default mode (the descriptor is then byte for byte what it was before momentum existed), another float
+    is passed by value, None is torch's cumulative moving average (factor 1 / num_batches_tracked)."""
+    if momentum is None:
+        return 0.0, BN_MOM_CUMULATIVE
+    m = float(momentum)
+    if m != m:
+        raise BmnasError('BatchNorm momentum is NaN')
+    return (0.0, BN_MOM_DEFAULT) if m == 0.1 else (m, BN_MOM_VALUE)
 
 
 class NodeSel(C.Structure):
@@ -152,13 +167,14 @@ class FcEdge(C.Structure):
 FC_MAX_EDGES = 15
 
 
-def make_bn_fin(stat, shards, conv_bias, bn_w, bn_b, rm, rv, nbt, training):
+def make_bn_fin(stat, shards, conv_bias, bn_w, bn_b, rm, rv, nbt, training, momentum=0.1):
     """Descriptor for in-kernel BatchNorm finalisation (bmnas_bn_fin_t): the consumer of a conv output
     derives scale / shift from the atomically accumulated batch sums `stat` (training) or from the
-    running statistics (eval) and writes `chan` for the backward kernels."""
+    running statistics (eval) and writes `chan` for the backward kernels.  momentum: the owning
+    nn.BatchNorm1d's (a float, or None for the cumulative average)."""
     p = lambda t: None if t is None else t.data_ptr()
     return BnFin(p(stat), p(conv_bias), p(bn_w), p(bn_b), p(rm), p(rv), p(nbt), int(shards),
-                 0 if nbt is None else nbt.numel(), int(training), 1)
+                 0 if nbt is None else nbt.numel(), int(training), 1, *bn_momentum(momentum))
 
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -200,6 +216,7 @@ SIGNATURES = {
     'bmnas_probe_barrier': ([_P, _P, _P, _I64, _I, _I, _P, _I, _P], _I),
     'bmnas_conv_family_calls': ([C.POINTER(C.c_long), _I, _I], _I),
     'bmnas_bn_finalize': ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P], _I),
+    'bmnas_bn_finalize_ex': ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, C.c_float, _I, _P, _P], _I),
     'bmnas_node_mix_fwd': ([_P, _P, _P, _P, _P, BnFin, _P, _P, _I, _I, _I, Dropout, Dropout, _P], _I),
     'bmnas_node_mix_conv_fwd_ok': ([_I, _I, _I, _I], _I),
     'bmnas_node_mix_conv_fwd': ([_P, _P, _P, _P, _P, BnFin, _P, _P, Dropout, Dropout, _PP, _I, _P, _I, _P, _P, _P, _I,
@@ -881,14 +898,14 @@ def fold_weight(W, Weff, M, Cc):
     _check(load().bmnas_fold_weight(W.data_ptr(), _ptr(Weff), M, Cc, _stream()), 'fold_weight')
 
 
-def bn_finalize(part, n_part, b, L, M, bn_w, bn_b, rm, rv, nbt, training, chan):
-    """nbt: int64 tensor of 1..k consecutive counters (or None)."""
-    _check(load().bmnas_bn_finalize(_ptr(part), n_part, b, L, M, bn_w.data_ptr(), bn_b.data_ptr(),
-                                    None if rm is None else rm.data_ptr(),
-                                    None if rv is None else rv.data_ptr(),
-                                    None if nbt is None else nbt.data_ptr(),
-                                    0 if nbt is None else nbt.numel(), int(training),
-                                    chan.data_ptr(), _stream()), 'bn_finalize')
+def bn_finalize(part, n_part, b, L, M, bn_w, bn_b, rm, rv, nbt, training, chan, momentum=0.1):
+    """nbt: int64 tensor of 1..k consecutive counters (or None).  momentum: nn.BatchNorm1d's (float | None)."""
+    _check(load().bmnas_bn_finalize_ex(_ptr(part), n_part, b, L, M, bn_w.data_ptr(), bn_b.data_ptr(),
+                                       None if rm is None else rm.data_ptr(),
+                                       None if rv is None else rv.data_ptr(),
+                                       None if nbt is None else nbt.data_ptr(),
+                                       0 if nbt is None else nbt.numel(), int(training), *bn_momentum(momentum),
+                                       chan.data_ptr(), _stream()), 'bn_finalize')
 
 
 def node_mix_fwd(x, y, p1, U, chan, gamma, out, b, Cc, L, dglu, dfc, fin=NO_FIN, nxt=None):

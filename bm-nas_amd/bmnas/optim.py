@@ -42,6 +42,12 @@ momentum buffers without writing them.
 `bmnas_avg_multi` launch (csrc/average.hip) over the same descriptor table and chunk list, `param` the averaged tensor and
 `grad` the live one, and no host synchronisation; inside a captured step its scalar rows ride behind the optimizer's
 (`staging_layout(extra_bytes=...)`, `capture_safe(extra=...)`, `rider_rows()`).
+
+`update_bn` (after it) is torch.optim.swa_utils.update_bn for the native BatchNorm kernels: one cumulative-statistics pass
+over a loader (BatchNorm momentum None), optionally as replays of one captured forward.  BatchNorm momentum is read when
+a launch is issued: like Adam's switches it may change between eager steps, but a captured plan (GraphedTrainStep,
+GraphedForward) keeps the momentum it was captured under — a float is baked into the graph, None replays correctly
+because the factor comes from the device counter.
 """
 import collections
 import math
@@ -1320,3 +1326,60 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
             self._copy_frozen(pl['model'], n)
         self._write_row(pl, slot, n)
         self._n = n + 1
+
+
+def update_bn(loader, model, device=None, *, unpack=None, criterion=None, graph=True):
+    """torch.optim.swa_utils.update_bn — the pass that ends the SWA recipe — for a model on the native BatchNorm
+    kernels: every BatchNorm's running statistics are reset and recomputed as the CUMULATIVE average over one pass of
+    `loader` (momentum None: factor 1 / num_batches_tracked, which the kernels derive from the device counter), with the
+    model in training mode and no gradients; momenta and the training mode are restored afterwards, also when a forward
+    raises.  Modules on the composed edited-list routes run torch's own BatchNorm under momentum None: right by
+    construction.
+
+        unpack(batch, device) -> (inputs, labels)   the trainers' callable (a list of modalities cannot go through torch's
+                                                    `input = input[0]`); without it torch's convention holds: a list /
+                                                    tuple batch means its first element, moved to `device` when given
+        criterion, graph=True                       the forwards are replays of ONE private bmnas.graph.GraphedForward,
+                                                    captured after the momenta are set and dropped at the end (a plan
+                                                    captured under other momenta must not be used: value mode bakes the
+                                                    scalar in); a ragged batch or a failed capture runs eagerly
+
+    No host synchronisation per batch.  Not for data parallelism: every rank would see only its shard.
+    -> dict(batches, replays, eager): how the forwards of this pass ran."""
+    report = dict(batches=0, replays=0, eager=0)
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    if not bns:
+        return report
+    momenta = {m: m.momentum for m in bns}
+    was_training = model.training
+    fwd = None
+    try:
+        for m in bns:
+            m.reset_running_stats()              # in place: NodeMixedOp's stacked views stay views
+            m.momentum = None
+        model.train()
+        with torch.no_grad():
+            for batch in loader:
+                if unpack is not None:
+                    inputs, labels = unpack(batch, device)
+                else:
+                    inputs, labels = (batch[0] if isinstance(batch, (list, tuple)) else batch), None
+                    if device is not None:
+                        inputs = inputs.to(device)
+                report['batches'] += 1
+                if graph and criterion is not None and labels is not None and fwd is not False:
+                    if fwd is None:
+                        from .graph import GraphedForward
+                        fwd = GraphedForward.try_build(model, criterion, inputs, labels)
+                    if fwd and fwd.matches(model, inputs, labels):
+                        fwd(inputs, labels)
+                        report['replays'] += 1
+                        continue
+                model(inputs)
+                report['eager'] += 1
+    finally:
+        del fwd
+        for m, mom in momenta.items():
+            m.momentum = mom
+        model.train(was_training)
+    return report

@@ -6,11 +6,13 @@
 // turns them into the fused affine scale[m] = bn_w * rstd, shift[m] = bn_b - mean * scale in LDS at
 // its start — four adjacent channels per thread, one memory round trip — and workgroup 0 also
 // writes chan = mean | rstd | scale | shift for the backward pass and updates the running
-// statistics exactly like nn.BatchNorm1d (momentum 0.1, unbiased variance, num_batches_tracked).
+// statistics exactly like nn.BatchNorm1d (its momentum — a float, or None: the cumulative average 1 / num_batches_tracked
+// — unbiased variance, num_batches_tracked).
 // Eval mode: the same from the running statistics.  Replaces bmnas_bn_finalize on the search path
 // (reference: nn.BatchNorm1d at node_operations.py:26,34 / :45,53, node_search.py:40,62).
 #pragma once
 #include "common.hpp"
+#include "../../include/bmnas_hip.h"
 
 constexpr float kEpsBn = 1e-5f;      // nn.BatchNorm1d's default
 
@@ -23,8 +25,32 @@ struct BnFin {
   float* running_var;
   long long* nbt;          // n_nbt consecutive int64 counters, nullable
   int shards, n_nbt, training;
-  int on;                  // 0: `chan` already holds the finalised values (bmnas_bn_finalize ran)
+  int on;                  // 0: `chan` already holds the finalised values (bmnas_bn_finalize ran); bit 2 (kFinCum):
+                           // BMNAS_BN_MOM_CUMULATIVE, the factor is 1 / (nbt[0] + 1) with nbt[0] as this launch found it
+  float mom;               // running = (1 - mom) * running + mom * batch (to_fin: 0.1f in BMNAS_BN_MOM_DEFAULT)
 };
+constexpr int kFinCum = 4;
+
+// The momentum fields of a bmnas_bn_fin_t -> BnFin (host); BMNAS_E_ARG on an unknown mode, a NaN, or cumulative mode
+// in training with running statistics and no counter to derive the factor from
+inline int fin_momentum(const bmnas_bn_fin_t& f, BnFin* o) {
+  if (f.momentum_mode == BMNAS_BN_MOM_DEFAULT) { o->mom = 0.1f; return 0; }
+  if (f.momentum_mode == BMNAS_BN_MOM_VALUE) {
+    if (f.momentum != f.momentum) return BMNAS_E_ARG;
+    o->mom = f.momentum;
+    return 0;
+  }
+  if (f.momentum_mode != BMNAS_BN_MOM_CUMULATIVE) return BMNAS_E_ARG;
+  if (f.training && f.running_mean && (!f.num_batches_tracked || f.n_nbt < 1)) return BMNAS_E_ARG;
+  if (f.training && f.n_nbt > 4) return BMNAS_E_LIMIT;      // (bn_fin_fill: thread 0 owns every counter)
+  o->mom = 0.f;
+  if (o->on) o->on |= kFinCum;
+  return 0;
+}
+
+__device__ __forceinline__ float wave_uniform(float v) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
 
 // sc / sh: LDS, M floats each.  Ends with a __syncthreads().
 // Thread t owns the four adjacent channels 4t .. 4t + 3 (M % 4 == 0, M <= 4 * BS): straight-line code,
@@ -33,7 +59,6 @@ struct BnFin {
 template <int BS>
 __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ chan, const int M, const int N,
                                             float* sc, float* sh, const bool writer) {
-  constexpr float kMom = 0.1f;
   constexpr int kMaxShards = 4;
   if (!f.on) {
     for (int m0 = 4 * (int)threadIdx.x; m0 < M; m0 += 4 * BS) {   // one trip for M <= 4 * BS
@@ -46,6 +71,12 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
   }
   const bool wr = writer && !(f.on & 2);                      // (bit 1: timing experiments only)
   const bool upd = wr && f.training && f.running_mean != nullptr;
+  const bool cnt = wr && f.training && f.nbt != nullptr;
+  const bool cum = (f.on & kFinCum) != 0;
+  // (the factor is a kernel argument: pinned to a scalar register HERE, with the other arguments — left to itself the
+  // compiler fetched it where it is first used, a scalar round trip behind the trip's vector loads in every workgroup)
+  const float mom_arg = f.mom;
+  asm volatile("" : : "s"(mom_arg));
   for (int m0 = 4 * (int)threadIdx.x; m0 < M; m0 += 4 * BS) {   // one trip for M <= 4 * BS
     // EVERY load unconditional, from an always-valid address where its operand is absent (eval mode has no
     // sums, the conv may have no bias, training may not track running statistics): a load under `if` is a
@@ -69,9 +100,12 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
     float4 cb4 = ld4((has_cb ? f.conv_bias : f.bn_w) + m0);
     float4 rm4 = ld4((need_run ? f.running_mean : f.bn_w) + m0);
     float4 rv4 = ld4((need_run ? f.running_var : f.bn_w) + m0);
-    long long nb = 0;
-    const bool bump = wr && f.training && f.nbt != nullptr && m0 < f.n_nbt;
-    if (bump) nb = f.nbt[m0];                                  // (counters 4t .. 4t + 3 of thread t: n_nbt <= M)
+    // ONE counter load, unconditional like the rest and issued with them: the first of the thread's own counters
+    // m0 .. m0 + 3 (n_nbt <= M), stored back + 1 below — or, under cumulative momentum, counter 0 as the launch found
+    // it, which every thread of the writer needs (thread 0, which then owns all n_nbt <= 4 counters: the same load)
+    // — or eight bytes of bn_w
+    const bool bump = cnt && m0 < f.n_nbt;
+    const long long nb = *(bump ? f.nbt + m0 : ((cum && upd) ? f.nbt : reinterpret_cast<const long long*>(f.bn_w)));
     if (!has_cb) cb4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!need_run) {
       rm4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -93,6 +127,8 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
     const float rvq[4] = {rv4.x, rv4.y, rv4.z, rv4.w};
     float mean[4], rstd[4], scale[4], shift[4], nrm[4], nrv[4];
     const float inv = 1.f / (float)N;
+    // (wave-uniform, kept in scalar registers: the kernels around this sit at a register count that decides occupancy)
+    const float mom = wave_uniform(cum ? 1.f / (float)(nb + 1) : mom_arg), keep = wave_uniform(1.f - mom);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (f.training) {
@@ -100,8 +136,8 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
         const float var = fmaxf(q[j] * inv - dm * dm, 0.f);
         mean[j] = dm + cq[j];
         rstd[j] = 1.f / sqrtf(var + kEpsBn);
-        nrm[j] = (1.f - kMom) * rmq[j] + kMom * mean[j];
-        nrv[j] = (1.f - kMom) * rvq[j] + kMom * (var * (float)N / (float)(N - 1));
+        nrm[j] = keep * rmq[j] + mom * mean[j];
+        nrv[j] = keep * rvq[j] + mom * (var * (float)N / (float)(N - 1));
       } else {
         mean[j] = rmq[j];
         rstd[j] = 1.f / sqrtf(rvq[j] + kEpsBn);
@@ -122,10 +158,13 @@ __device__ __forceinline__ void bn_fin_fill(const BnFin& f, float* __restrict__ 
         st4(f.running_var + m0, make_float4(nrv[0], nrv[1], nrv[2], nrv[3]));
       }
       if (bump) {
-        f.nbt[m0] = nb + 1;
+        // (cumulative momentum: counter 0 waits for the barrier — every wave of the writer reads it, and one that
+        // runs ahead must not bump it under the others)
+        if (!(cum && m0 == 0)) f.nbt[m0] = nb + 1;
         for (int j = 1; j < 4 && m0 + j < f.n_nbt; ++j) f.nbt[m0 + j] += 1;
       }
     }
   }
   __syncthreads();
+  if (cnt && cum && threadIdx.x == 0 && f.n_nbt > 0) f.nbt[0] += 1;
 }

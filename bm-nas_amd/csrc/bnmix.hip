@@ -16,7 +16,12 @@
 
 namespace {
 
-constexpr float kMomentum = 0.1f;
+// bn_finalize_k in cumulative-momentum mode leaves the counters alone — every channel's wavefront reads counter 0 as
+// the launch found it, in whatever order the workgroups run — and this launch behind it increments them
+__global__ void bn_count_k(int64_t* nbt, int n_nbt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_nbt) nbt[i] += 1;
+}
 
 __global__ __launch_bounds__(256) void bn_finalize_k(const float* __restrict__ part, int n_part,
                                                      int b, int L, int M,
@@ -24,7 +29,7 @@ __global__ __launch_bounds__(256) void bn_finalize_k(const float* __restrict__ p
                                                      const float* __restrict__ bn_b,
                                                      float* running_mean, float* running_var,
                                                      int64_t* nbt, int n_nbt, int training,
-                                                     float* __restrict__ chan) {
+                                                     float mom, int cum, float* __restrict__ chan) {
   // one wavefront per channel: lanes stride over that channel's partials (part[m][p][2]),
   // Chan's parallel-variance combine, two wave reductions
   const int lane = threadIdx.x & 63;
@@ -71,11 +76,12 @@ __global__ __launch_bounds__(256) void bn_finalize_k(const float* __restrict__ p
     rstd = 1.f / sqrtf(var + kEpsBn);
     if (lane == 0) {
       if (running_mean != nullptr) {
-        running_mean[m] = (1.f - kMomentum) * running_mean[m] + kMomentum * mean;
+        if (cum) mom = 1.f / (float)(nbt[0] + 1);
+        running_mean[m] = (1.f - mom) * running_mean[m] + mom * mean;
         const float unbiased = m2 / (float)(N - 1);
-        running_var[m] = (1.f - kMomentum) * running_var[m] + kMomentum * unbiased;
+        running_var[m] = (1.f - mom) * running_var[m] + mom * unbiased;
       }
-      if (m < n_nbt && nbt != nullptr) nbt[m] += 1;
+      if (!cum && m < n_nbt && nbt != nullptr) nbt[m] += 1;
     }
   } else {
     mean = running_mean[m];
@@ -1282,18 +1288,38 @@ __global__ __launch_bounds__(256) void cell_prologue_pair_k(ArchPack P, FoldPack
 
 extern "C" int bmnas_version(void) { return 100; }
 
+extern "C" int bmnas_bn_finalize_ex(const float* part, int n_part, int b, int L, int M,
+                                    const float* bn_w, const float* bn_b, float* running_mean,
+                                    float* running_var, int64_t* num_batches_tracked, int n_nbt,
+                                    int training, float momentum, int momentum_mode, float* chan, void* stream) {
+  if (!bn_w || !bn_b || !chan || M < 1 || b < 1 || L < 1) return BMNAS_E_ARG;
+  if (training && (!part || n_part < 1 || b * L < 2)) return BMNAS_E_ARG;
+  if (!training && (!running_mean || !running_var)) return BMNAS_E_ARG;
+  bmnas_bn_fin_t d{};                                      // (the momentum rules of the in-kernel finalisation)
+  d.running_mean = running_mean; d.num_batches_tracked = num_batches_tracked; d.n_nbt = n_nbt;
+  d.training = training; d.momentum = momentum; d.momentum_mode = momentum_mode;
+  BnFin f{};
+  f.on = 1;
+  if (int e = fin_momentum(d, &f)) return e;
+  const bool count_after = (f.on & kFinCum) && training && num_batches_tracked && n_nbt > 0;
+  hipLaunchKernelGGL(bn_finalize_k, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, part,
+                     n_part, b, L, M, bn_w, bn_b, running_mean, running_var, num_batches_tracked,
+                     n_nbt, training, f.mom, count_after ? 1 : 0, chan);
+  BMNAS_CHECK_LAUNCH();
+  if (count_after) {
+    hipLaunchKernelGGL(bn_count_k, dim3((n_nbt + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       num_batches_tracked, n_nbt);
+    BMNAS_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
 extern "C" int bmnas_bn_finalize(const float* part, int n_part, int b, int L, int M,
                                  const float* bn_w, const float* bn_b, float* running_mean,
                                  float* running_var, int64_t* num_batches_tracked, int n_nbt,
                                  int training, float* chan, void* stream) {
-  if (!bn_w || !bn_b || !chan || M < 1 || b < 1 || L < 1) return BMNAS_E_ARG;
-  if (training && (!part || n_part < 1 || b * L < 2)) return BMNAS_E_ARG;
-  if (!training && (!running_mean || !running_var)) return BMNAS_E_ARG;
-  hipLaunchKernelGGL(bn_finalize_k, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, part,
-                     n_part, b, L, M, bn_w, bn_b, running_mean, running_var, num_batches_tracked,
-                     n_nbt, training, chan);
-  BMNAS_CHECK_LAUNCH();
-  return 0;
+  return bmnas_bn_finalize_ex(part, n_part, b, L, M, bn_w, bn_b, running_mean, running_var, num_batches_tracked,
+                              n_nbt, training, 0.f, BMNAS_BN_MOM_DEFAULT, chan, stream);
 }
 
 extern "C" int bmnas_node_mix_fwd_next(const float* x, const float* y, const float* p1, const float* U,

@@ -149,7 +149,7 @@ inline int to_fin(const bmnas_bn_fin_t& f, BnFin* o) {
   o->running_mean = f.running_mean; o->running_var = f.running_var;
   o->nbt = reinterpret_cast<long long*>(f.num_batches_tracked);
   o->shards = f.shards; o->n_nbt = f.n_nbt; o->training = f.training ? 1 : 0;
-  return 0;
+  return fin_momentum(f, o);
 }
 // ... for a launch over b samples of length L: batch statistics need two values per channel
 inline int fin_for(const bmnas_bn_fin_t& fin, int b, int L, BnFin* f) {

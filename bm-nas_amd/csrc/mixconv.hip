@@ -193,6 +193,7 @@ extern "C" int bmnas_node_mix_conv_fwd(const float* x, const float* y, const flo
       f.running_mean = fin.running_mean; f.running_var = fin.running_var;
       f.nbt = reinterpret_cast<long long*>(fin.num_batches_tracked);
       f.shards = fin.shards; f.n_nbt = fin.n_nbt; f.training = fin.training ? 1 : 0;
+      if (int e = fin_momentum(fin, &f)) return e;
     }
     a.fin = f;
   }

@@ -44,7 +44,7 @@ class _ReshapeBase(nn.Module):
         bn = self.bn
         if pooled.is_cuda and self.conv.in_channels % 16 == 0 and self.C % 16 == 0 and self.L in (4, 8, 16):
             return ConvBnActFn.apply('relu', self.dropout.p, self.training, bn.running_mean, bn.running_var,
-                                     bn.num_batches_tracked, self.conv.weight, self.conv.bias, bn.weight,
+                                     bn.num_batches_tracked, bn.momentum, self.conv.weight, self.conv.bias, bn.weight,
                                      bn.bias, pooled.contiguous())
         from bmnas import lib
         lib.note_off_path(type(self).__name__, f'pooled input {tuple(pooled.shape)} on {pooled.device} '
@@ -121,7 +121,7 @@ def reshape_tails(layers, pooled):
             grp = same
     if grp:
         ls = [layers[i] for i in grp]
-        buffers = [(m.bn.running_mean, m.bn.running_var, m.bn.num_batches_tracked) for m in ls]
+        buffers = [(m.bn.running_mean, m.bn.running_var, m.bn.num_batches_tracked, m.bn.momentum) for m in ls]
         params = []
         for m in ls:
             params += [m.conv.weight, m.conv.bias, m.bn.weight, m.bn.bias]

@@ -171,15 +171,42 @@ def averaging_options(args, status):
     return dict(decay=decay, swa_start=swa_start, skip_frozen=bool(getattr(args, 'average_skip_frozen', True)))
 
 
+def update_bn_option(args, status, world=None):
+    """args.swa_update_bn (optional, default False; needs args.ema_decay or args.swa_start): the averaged module's
+    BatchNorm statistics are recomputed by bmnas.optim.update_bn — one cumulative pass over the training loader — before
+    it is evaluated, instead of being averaged like weights (the step the SWA recipe ends with).  -> bool.  Refused in a
+    search like the averaging options, and under data parallelism (world: the number of ranks; None: asks
+    torch.distributed): every rank would see only its shard of the training data and the ranks' statistics would differ."""
+    if not getattr(args, 'swa_update_bn', False):
+        return False
+    if status != 'eval':
+        raise ValueError("args.swa_update_bn belongs to the weight averaging of a found-stage run (status 'eval'): "
+                         f"refused in a search (status {status!r})")
+    if getattr(args, 'ema_decay', None) is None and getattr(args, 'swa_start', None) is None:
+        raise ValueError('args.swa_update_bn recomputes the BatchNorm statistics of the AVERAGED model: set '
+                         'args.ema_decay or args.swa_start with it')
+    if world is None:
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    if world > 1:
+        raise ValueError(f'args.swa_update_bn is not available under data parallelism ({world} ranks): every rank would '
+                         'see only its shard of the training loader, so the ranks would end with different statistics')
+    return True
+
+
 def make_averager(model, args, status):
-    """-> (bmnas.optim.AveragedModel of `model`, its options), or (None, None) without the options.  use_buffers=True:
-    the native BatchNorm kernels fix momentum 0.1, so swa_utils.update_bn's cumulative pass is not available — averaged
-    running statistics stand in for it."""
+    """-> (bmnas.optim.AveragedModel of `model`, its options), or (None, None) without the options.  use_buffers=True
+    — averaged running statistics stand in for swa_utils.update_bn's cumulative pass — unless args.swa_update_bn asks
+    for that pass (update_bn_option; opts['update_bn']): then the buffers are not averaged and the loop recomputes them
+    with bmnas.optim.update_bn before the averaged module is evaluated."""
     opts = averaging_options(args, status)
     if opts is None:
+        update_bn_option(args, status)           # (alone it is an error, not a silent no-op)
         return None, None
+    opts['update_bn'] = update_bn_option(args, status)
     from bmnas.optim import AveragedModel
-    return AveragedModel(model, decay=opts['decay'], use_buffers=True, skip_frozen=opts['skip_frozen']), opts
+    return AveragedModel(model, decay=opts['decay'], use_buffers=not opts['update_bn'],
+                         skip_frozen=opts['skip_frozen']), opts
 
 
 def search_setup(model, args, criterion, device, num_batches_per_epoch, weight_decay):

@@ -78,7 +78,7 @@ class Found_NodeCell(nn.Module):
             # out_conv's BatchNorm / ReLU / dropout tail, the residual and the node's LayerNorm as ONE launch each way
             bn = self.bn
             o, sums = ConvBnReluLnFn.apply(self.out_dropout.p, self.training, self.want_sums, bn.running_mean,
-                                           bn.running_var, bn.num_batches_tracked, self.out_conv.weight,
+                                           bn.running_var, bn.num_batches_tracked, bn.momentum, self.out_conv.weight,
                                            self.out_conv.bias, bn.weight, bn.bias, self.ln.weight, self.ln.bias, x,
                                            *tail)
             if self.want_sums:
@@ -87,7 +87,7 @@ class Found_NodeCell(nn.Module):
         if self.node_multiplier != 1:
             bn = self.bn
             out = ConvBnActFn.apply('relu', self.out_dropout.p, self.training, bn.running_mean,
-                                    bn.running_var, bn.num_batches_tracked, self.out_conv.weight,
+                                    bn.running_var, bn.num_batches_tracked, bn.momentum, self.out_conv.weight,
                                     self.out_conv.bias, bn.weight, bn.bias, *tail)
         else:
             out = tail[0]

@@ -59,7 +59,7 @@ class _CatConvBn(nn.Module):
     def forward(self, x, y):
         bn = self.bn
         return ConvBnActFn.apply(self._act, self.dropout.p, self.training, bn.running_mean,
-                                 bn.running_var, bn.num_batches_tracked, self.conv.weight,
+                                 bn.running_var, bn.num_batches_tracked, bn.momentum, self.conv.weight,
                                  self.conv.bias, bn.weight, bn.bias, x, y)
 
     def forward_thru(self, x, y):
@@ -68,7 +68,7 @@ class _CatConvBn(nn.Module):
         autograd `add` launches)."""
         bn = self.bn
         return ConvBnActThruFn.apply(self._act, self.dropout.p, self.training, bn.running_mean,
-                                     bn.running_var, bn.num_batches_tracked, self.conv.weight,
+                                     bn.running_var, bn.num_batches_tracked, bn.momentum, self.conv.weight,
                                      self.conv.bias, bn.weight, bn.bias, x, y)
 
 
@@ -301,14 +301,19 @@ class NodeMixedOp(nn.Module):
             if not self._stack_ok():
                 self._restack()
             st = self._stack
+            if glu.bn.momentum != cfc.bn.momentum:           # ONE launch finalises both: one momentum
+                raise _lib.BmnasError(
+                    f'NodeMixedOp: the stacked BatchNorms share one launch and need one momentum, but '
+                    f'{type(glu).__name__}.bn has momentum={glu.bn.momentum!r} and {type(cfc).__name__}.bn has '
+                    f'momentum={cfc.bn.momentum!r}')
             P.__dict__.update(stack_W=st.W, stack_bias=st.bias, stack_bn_w=st.bn_w, stack_bn_b=st.bn_b,
-                              stack_rm=st.rm, stack_rv=st.rv, stack_nbt=st.nbt)
+                              stack_rm=st.rm, stack_rv=st.rv, stack_nbt=st.nbt, stack_mom=glu.bn.momentum)
         elif glu is not None or cfc is not None:
             m = glu if glu is not None else cfc
             P.__dict__.update(stack_W=m.conv.weight.detach().view(P.M, 2 * self.C), stack_bias=m.conv.bias.detach(),
                               stack_bn_w=m.bn.weight.detach(), stack_bn_b=m.bn.bias.detach(),
                               stack_rm=m.bn.running_mean, stack_rv=m.bn.running_var,
-                              stack_nbt=m.bn.num_batches_tracked)
+                              stack_nbt=m.bn.num_batches_tracked, stack_mom=m.bn.momentum)
         return P
 
     def param_list(self):

@@ -49,6 +49,7 @@ class NodeCell(nn.Module):
             p.out_conv_b = self.out_conv.bias.detach()
             p.bn_w, p.bn_b = self.bn.weight.detach(), self.bn.bias.detach()
             p.bn_rm, p.bn_rv, p.bn_nbt = self.bn.running_mean, self.bn.running_var, self.bn.num_batches_tracked
+            p.bn_mom = self.bn.momentum
             p.out_p = self.out_dropout.p
         return p
 
@@ -104,7 +105,7 @@ class NodeCell(nn.Module):
         if self.node_multiplier != 1:
             bn = self.bn
             out = ConvBnActFn.apply('relu', self.out_dropout.p, self.training, bn.running_mean,
-                                    bn.running_var, bn.num_batches_tracked, self.out_conv.weight,
+                                    bn.running_var, bn.num_batches_tracked, bn.momentum, self.out_conv.weight,
                                     self.out_conv.bias, bn.weight, bn.bias, *tail)
         else:
             out = tail[0]

@@ -19,7 +19,10 @@ Differences, all on the host side of the hot path:
     args.ema_decay / args.swa_start / args.average_skip_frozen) on bmnas.optim.AveragedModel — an EMA updated after
     every weight step (inside the replay when the step is captured, eagerly on ragged batches) or an SWA snapshot at
     the end of every epoch from args.swa_start on; the phases that do not learn then evaluate the AVERAGED module and
-    `best_test_averaged.pt` is saved next to `best_test_model.pt`.  With no option set nothing changes.
+    `best_test_averaged.pt` is saved next to `best_test_model.pt`.  args.swa_update_bn adds the step the SWA recipe
+    ends with: the averaged module's BatchNorm statistics are not averaged but recomputed by one cumulative pass over
+    the training loader (bmnas.optim.update_bn) before its first evaluation after the weights changed
+    (run.stats['update_bn_passes']).  With no option set nothing changes.
 """
 import copy
 import os
@@ -252,6 +255,12 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     if averaged is not None:
         stats['averaged_updates'] = 0
         stats['averaged_forwards'] = 0
+    # args.swa_update_bn: the averaged module's BatchNorm statistics come from a cumulative pass over the training
+    # loader (bmnas.optim.update_bn), taken before the first evaluation after its weights changed
+    bn_pass = averaged is not None and avg_opts['update_bn']
+    bn_pass_at = 0                   # stats['averaged_updates'] when the last pass ran
+    if bn_pass:
+        stats['update_bn_passes'] = 0
     # SWA: the phase after which an epoch's snapshot is taken — its last learning one (train and dev both learn here)
     swa_phase = ([ph for ph in eval_phases if ph in ('train', 'dev')] or [None])[-1] if averaged is not None else None
     best = dict(best_dev=None, best_dev_genotype=None, best_dev_epoch=0, best_test=None,
@@ -294,6 +303,11 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
             # a phase that does not learn evaluates the averaged weights, once there are any (SWA: from its first snapshot)
             use_avg = averaged is not None and not learn and stats['averaged_updates'] > 0
             net, net_graphs = (averaged.module, avg_graphs) if use_avg else (model, f_graphs)
+            if use_avg and bn_pass and bn_pass_at != stats['averaged_updates']:
+                from bmnas.optim import update_bn
+                update_bn(dataloaders['train'], averaged.module, device, unpack=unpack, criterion=criterion)
+                bn_pass_at = stats['averaged_updates']
+                stats['update_bn_passes'] += 1
             if use_avg:
                 averaged.module.eval()
             meter.reset(device)

@@ -289,13 +289,29 @@ int bmnas_bn_finalize(const float* part, int n_part, int b, int L, int M, const 
                       int64_t* num_batches_tracked, int n_nbt, int training, float* chan,
                       void* stream);
 
+/* nn.BatchNorm1d.momentum for the running statistics, running = (1 - f) * running + f * batch:
+ *   BMNAS_BN_MOM_DEFAULT     f = 0.1, nn.BatchNorm1d's default (a zero-initialised descriptor means this)
+ *   BMNAS_BN_MOM_VALUE       f = momentum (any float that is not NaN; 0 leaves the buffers as they are)
+ *   BMNAS_BN_MOM_CUMULATIVE  f = 1 / (n + 1), n = the launch's FIRST num_batches_tracked counter before this launch
+ *                            increments it: torch's `momentum=None` (num_batches_tracked += 1; f = 1 / num_batches_tracked).
+ * The counters of several BatchNorms stacked in one launch are incremented together by every launch, so they advance
+ * in lock step and the first one serves every channel.  Cumulative mode in training with running statistics needs at
+ * least one counter (BMNAS_E_ARG without) and takes at most four (BMNAS_E_LIMIT).  The mode reaches nothing but running_mean / running_var: the output,
+ * `chan` and every gradient are the same in all three. */
+enum { BMNAS_BN_MOM_DEFAULT = 0, BMNAS_BN_MOM_VALUE = 1, BMNAS_BN_MOM_CUMULATIVE = 2 };
+/* bmnas_bn_finalize with a momentum (bmnas_bn_finalize is this with BMNAS_BN_MOM_DEFAULT). */
+int bmnas_bn_finalize_ex(const float* part, int n_part, int b, int L, int M, const float* bn_w,
+                         const float* bn_b, float* running_mean, float* running_var,
+                         int64_t* num_batches_tracked, int n_nbt, int training, float momentum,
+                         int momentum_mode, float* chan, void* stream);
+
 /* BatchNorm finalisation INSIDE the kernel that applies it (bmnas_node_mix_fwd, bmnas_node_mix_ln_fwd,
  * bmnas_bn_relu_fwd) instead of a bmnas_bn_finalize launch in front of it.  on = 0: `chan` already
  * holds mean | rstd | scale | shift.  on = 1: every workgroup derives scale / shift in LDS —
  * training: from `stat` (the sums a bmnas_conv1x1_fwd with stat_shards = shards accumulated; conv_bias
  * is the shift they were taken about), eval: from the running statistics — and workgroup 0 writes
  * `chan` (now an OUTPUT, for the backward kernels) and, in training mode, updates running_mean /
- * running_var / the n_nbt counters like nn.BatchNorm1d. */
+ * running_var / the n_nbt counters like nn.BatchNorm1d, with the momentum that momentum_mode selects. */
 typedef struct {
   const float* stat;
   const float* conv_bias;
@@ -305,6 +321,8 @@ typedef struct {
   float* running_var;
   int64_t* num_batches_tracked;
   int shards, n_nbt, training, on;
+  float momentum;    /* read in BMNAS_BN_MOM_VALUE mode only */
+  int momentum_mode; /* BMNAS_BN_MOM_* above */
 } bmnas_bn_fin_t;
 
 /* ---- K2: the gamma-weighted NodeMixedOp combine -------------------------------------------
