@@ -166,8 +166,22 @@ class GraphedTrainStep:
                     pass
         return n
 
-    def __init__(self, model, criterion, optimizer, inputs, labels, warmup=2, metric_forward=False, k=1, averaged=None):
-        """averaged: a bmnas.optim.AveragedModel of `model`; its update (`averaged.update_parameters(model)`, one
+    def __init__(self, model, criterion, optimizer, inputs, labels, warmup=2, metric_forward=False, k=1, averaged=None,
+                 accumulate=1):
+        """accumulate: micro-batches per optimizer step.  m > 1 captures m static micro-batches — each forward +
+        criterion + `autograd.grad`, its gradients handed to a bmnas.optim.GradAccumulator (`self.accumulator`) —, then ONE
+        combine launch (bmnas_grad_combine_multi), ONE `optimizer.step()` and, if given, one averager update: all one
+        replay.  Driven like k: `stage(i, inputs, labels)` per micro-batch, then `replay_staged()` -> [(loss_i, logits_i)].
+        `inputs` / `labels` may be lists of m micro-batches (of shapes of their own: an uneven split); one batch stands for
+        m of its shape.  The weights are constants of the capture: n_i / N for a criterion with reduction='mean' (the
+        combined gradient is that of the N samples together, what m data-parallel ranks would all-reduce), 1 for 'sum'
+        (bmnas.optim.accum_weights).  A class-weighted CrossEntropyLoss mean is normalised per micro-batch by its own
+        weight sum: the caveat README states for data parallelism.  BatchNorm sees each micro-batch on its own, and its
+        running statistics advance once per micro-batch.  The dropout step counter spans all m passes: every pass draws
+        masks of its own.  Refused: with k > 1, with metric_forward, under data parallelism (a reducer) — where the
+        update would not be inside the graph —, and m > lib.accum_max().  accumulate=1 is the step as it always was:
+        no accumulator, no combine launch.
+        averaged: a bmnas.optim.AveragedModel of `model`; its update (`averaged.update_parameters(model)`, one
         bmnas_avg_multi launch) then follows `optimizer.step()` INSIDE the graph, for each of the k steps.  Its scalar row
         of a replay, 32 bytes per step, rides behind the optimizer's rows (capture_safe(extra=...)): by value in the
         batch-copy launch's blob, or through the copy-node fallback when the rows no longer fit it.  Needs the update
@@ -185,6 +199,31 @@ class GraphedTrainStep:
         (train_searchable/mmimdb.py:66-84: Architect.step, then the metric forward on the same batch, which sees the
         updated alphas).  One batch copy and one replay instead of two of each; `__call__` then returns
         (loss, logits, metric_loss, metric_logits).  Needs the update inside the graph (`in_graph_step`)."""
+        self.accumulate = int(accumulate)
+        if self.accumulate < 1:
+            raise ValueError('accumulate >= 1')
+        if self.accumulate > 1:
+            from . import lib
+            if int(k) > 1:
+                raise RuntimeError('accumulate > 1 cannot be combined with k > 1 steps per replay')
+            if metric_forward:
+                raise RuntimeError('accumulate > 1 cannot be combined with metric_forward')
+            red = getattr(optimizer, '_bmnas_reducer', None)
+            if red is not None and (red.world > 1 or getattr(red, 'selftest', False)):
+                raise RuntimeError('accumulate > 1 is not supported under data parallelism (a reducer of world size '
+                                   'above 1): the optimizer step would not be inside the captured graph')
+            if self.accumulate > lib.accum_max():
+                raise RuntimeError(f'accumulate = {self.accumulate} exceeds lib.accum_max() = {lib.accum_max()} '
+                                   '(BMNAS_ACCUM_MAX parts per combine launch)')
+            # m micro-batches: lists of m (inputs, labels), or one batch that stands for m of its shape
+            if torch.is_tensor(labels):
+                micro = [(inputs, labels)] * self.accumulate
+            else:
+                micro = list(zip(inputs, labels))
+                if len(micro) != self.accumulate or len(inputs) != len(labels):
+                    raise RuntimeError(f'accumulate = {self.accumulate} needs {self.accumulate} micro-batches, got '
+                                       f'{len(inputs)} input lists and {len(labels)} label tensors')
+            inputs, labels = micro[0]
         import gc
         gc.collect()
         live = self._live_graph_tensors(labels.device)
@@ -209,8 +248,17 @@ class GraphedTrainStep:
         if self.k < 1:
             raise ValueError('k >= 1')
         # one static batch per captured step; slot 0 doubles as `static_batch()`
-        self.slots = [([x.detach().clone().requires_grad_(x.requires_grad) for x in inputs], labels.detach().clone())
-                      for _ in range(self.k)]
+        if self.accumulate > 1:
+            from . import optim
+            self.slots = [([x.detach().clone().requires_grad_(x.requires_grad) for x in xs], y.detach().clone())
+                          for xs, y in micro]
+            self.accum_weights = optim.accum_weights([y.shape[0] for _, y in self.slots],
+                                                     getattr(criterion, 'reduction', 'mean'))
+            self.accumulator = optim.GradAccumulator(optimizer)
+        else:
+            self.slots = [([x.detach().clone().requires_grad_(x.requires_grad) for x in inputs],
+                           labels.detach().clone()) for _ in range(self.k)]
+            self.accumulator = None
         self.inputs, self.labels = self.slots[0]
         self._staged = []
         self._batch_in = _BatchIn(self.inputs, self.labels)
@@ -239,6 +287,8 @@ class GraphedTrainStep:
         from . import nn as bnn
 
         def fn():
+            if self.accumulate > 1:
+                return accumulated()
             if self.k == 1:
                 return one(self.inputs, self.labels)
             out = ()
@@ -246,7 +296,22 @@ class GraphedTrainStep:
                 out += one(xs_i, y_i)
             return out
 
-        def one(xs_, y_):
+        def accumulated():
+            # m passes, each leaving its gradients in tensors of its own (the graph's static autograd.grad outputs); ONE
+            # combine launch sums them into the accumulation tensors, which .grad then points at
+            out = ()
+            for (xs_i, y_i), w_i in zip(self.slots, self.accum_weights):
+                loss, logits, grads = backward(xs_i, y_i)
+                self.accumulator.add(grads, w_i)
+                out += (loss, logits)
+            self.accumulator.combine()
+            if armed[0]:
+                optimizer.step()
+                if averaged is not None:
+                    averaged.update_parameters(model)
+            return out
+
+        def backward(xs_, y_):
             # the criterion of a fused head is evaluated by the head's backward launch: the static
             # `loss` output is complete when the replay is (bmnas.nn.fused_criterion)
             with bnn.fused_criterion():
@@ -261,6 +326,10 @@ class GraphedTrainStep:
                 else:
                     grads = torch.autograd.grad(loss, self.targets, grad_outputs=unit_grad(loss.device),
                                                 allow_unused=True)
+            return loss, logits, grads
+
+        def one(xs_, y_):
+            loss, logits, grads = backward(xs_, y_)
             if reducer is not None:
                 have = [(v, g) for v, g in zip(views, grads) if g is not None]
                 torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
@@ -322,6 +391,8 @@ class GraphedTrainStep:
         try:
             if self.in_graph_step:
                 # no H2D node in the graph: the scalars (of every one of the k steps) ride with the batch copy
+                if self.accumulator is not None:
+                    self.accumulator.capture_safe(self.accumulate)
                 if averaged is None:
                     optimizer.capture_safe(poke=True, slots=self.k)
                 else:
@@ -341,26 +412,39 @@ class GraphedTrainStep:
             self.plan = optimizer.captured_plan() if self.in_graph_step else None
             # ... and THIS plan's rider rows: the averager may ride in other captured steps too
             self.avg_plan = averaged.captured_plan() if averaged is not None else None
+            # ... and the accumulator's tables (uploaded here, in front of the first replay) and static parts
+            self.accum_plan = self.accumulator.captured_plan() if self.accumulator is not None else None
             self.static_grads = [t.grad for t in self.targets]
         except BaseException:
             if averaged is not None:
                 averaged.abandon_capture()
+            if self.accumulator is not None:
+                self.accumulator.abandon_capture()
             raise
         finally:
             model.load_state_dict(state)        # also when the capture fails and the caller stays eager
 
     @staticmethod
-    def try_build(model, criterion, optimizer, inputs, labels, logger=None, metric_forward=False, k=1, averaged=None):
+    def try_build(model, criterion, optimizer, inputs, labels, logger=None, metric_forward=False, k=1, averaged=None,
+                  accumulate=1):
         """-> a GraphedTrainStep, or False when this step cannot be captured (inputs that are not a
         flat list of tensors, a module that synchronises with the host, ...); callers then keep
         the eager path."""
-        if not (isinstance(inputs, (list, tuple)) and all(torch.is_tensor(x) for x in inputs)
-                and torch.is_tensor(labels)):
+        if accumulate > 1 and not torch.is_tensor(labels):           # lists of m micro-batches
+            flat_ok = (isinstance(inputs, (list, tuple)) and isinstance(labels, (list, tuple)) and len(labels) > 0 and
+                       all(isinstance(xs, (list, tuple)) and all(torch.is_tensor(x) for x in xs) for xs in inputs) and
+                       all(torch.is_tensor(y) for y in labels))
+            device = labels[0].device if flat_ok else None
+        else:
+            flat_ok = (isinstance(inputs, (list, tuple)) and all(torch.is_tensor(x) for x in inputs)
+                       and torch.is_tensor(labels))
+            device = labels.device if flat_ok else None
+        if not flat_ok:
             return False
         from .dist import all_ranks_agree
         try:
             step = GraphedTrainStep(model, criterion, optimizer, inputs, labels, metric_forward=metric_forward, k=k,
-                                    averaged=averaged)
+                                    averaged=averaged, accumulate=accumulate)
         except Exception as e:                       # noqa: BLE001 — capture errors are of many types
             torch.cuda.synchronize()
             from . import functions
@@ -372,7 +456,7 @@ class GraphedTrainStep:
         # data parallel: every rank replays, or none does (capture success is decided per rank; the eager
         # reducer issues the same collective as a replaying rank, but the step's structure — where Adam
         # runs, which buffers hold the gradients — should not differ between replicas either)
-        if not all_ranks_agree(bool(step), labels.device):
+        if not all_ranks_agree(bool(step), device):
             if step and logger is not None:
                 logger.info('another rank could not capture its step: staying eager on every rank')
             step = False
@@ -399,6 +483,12 @@ class GraphedTrainStep:
         return (len(inputs) == len(self.inputs) and labels.shape == self.labels.shape and
                 all(a.shape == b.shape for a, b in zip(inputs, self.inputs)))
 
+    def matches_group(self, batches):
+        """accumulate > 1: whether `batches` — m (inputs, labels) pairs — have the shapes of the m captured micro-batches."""
+        return (len(batches) == len(self.slots) and
+                all(len(xs) == len(sx) and y.shape == sy.shape and all(a.shape == b.shape for a, b in zip(xs, sx))
+                    for (xs, y), (sx, sy) in zip(batches, self.slots)))
+
     def static_batch(self):
         """(inputs, labels) the captured step reads: a producer that writes the batch INTO these tensors (and then
         passes them to `__call__`) saves the copy itself — 5.9 us of kernel for the 9.4 MB of an MM-IMDB b128 batch, ~1 us net:
@@ -408,13 +498,25 @@ class GraphedTrainStep:
     def stage(self, i, inputs, labels):
         """k > 1: hand over batch i (0 ... k - 1, in order) of the next replay.  Call it AFTER the scheduler has set the
         learning rates this batch's step runs with: the step's Adam scalars are fixed here.  -> those learning rates, as
-        staged (one per scalar row)."""
+        staged (one per scalar row).
+        accumulate > 1: hand over micro-batch i (0 ... m - 1, in order); the ONE step's scalars are fixed — and returned —
+        with the last one, the earlier calls return None."""
         opt = self.optimizer
         if i == 0:
             opt.activate(self.plan)          # an eager step in between must not leak into the replay
             self._staged = []
         if i != len(self._staged) // (len(self.inputs) + 1):
             raise RuntimeError('GraphedTrainStep.stage: batches must be staged in order, one call per slot')
+        if self.accumulate > 1:
+            # m micro-batches, ONE optimizer step: its scalars are fixed when the LAST micro-batch is handed over (the
+            # step runs with the rates after its group's last batch)
+            self._staged += list(inputs) + [labels]
+            if i < self.accumulate - 1:
+                return None
+            opt.prepare_replay()
+            if self.averaged is not None:
+                self.averaged.prepare_replay(self.avg_plan)
+            return opt.staged_lrs()
         opt.prepare_replay(slot=i)
         if self.averaged is not None:
             self.averaged.prepare_replay(self.avg_plan, slot=i)
@@ -426,20 +528,21 @@ class GraphedTrainStep:
         """-> [(loss, logits[, metric_loss, metric_logits])] * k of the k staged batches (static tensors, overwritten by
         the next replay)."""
         opt = self.optimizer
-        if len(self._staged) != self.k * (len(self.inputs) + 1):
-            raise RuntimeError(f'GraphedTrainStep.replay_staged: {self.k} batches must be staged first')
+        n_slots = len(self.slots)
+        if len(self._staged) != n_slots * (len(self.inputs) + 1):
+            raise RuntimeError(f'GraphedTrainStep.replay_staged: {n_slots} batches must be staged first')
         # ONE launch in front of the replay: the k batches into the static tensors + the k steps' Adam scalars
         self._batch_in(self._staged[:-1], self._staged[-1], opt.replay_blob())
         self._staged = []
         out = self._g.replay()
         opt.mark_launched()
         n = 4 if self.metric_forward else 2
-        return [tuple(out[n * i:n * (i + 1)]) for i in range(self.k)]
+        return [tuple(out[n * i:n * (i + 1)]) for i in range(n_slots)]
 
     def __call__(self, inputs, labels):
         opt = self.optimizer
-        if self.k != 1:
-            raise RuntimeError('a k-step GraphedTrainStep is driven by stage() / replay_staged()')
+        if self.k != 1 or self.accumulate != 1:
+            raise RuntimeError('a k-step or accumulating GraphedTrainStep is driven by stage() / replay_staged()')
         if self.in_graph_step:
             opt.activate(self.plan)          # an eager step in between must not leak into the replay
             opt.prepare_replay()

@@ -274,6 +274,8 @@ SIGNATURES = {
     'bmnas_grad_scale_multi': ([_P, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_sgd_multi': ([_P, _P, _I, _P, _I, _P, _I, _P, _P, _P], _I),
     'bmnas_avg_multi': ([_P, _P, _I, _P, _P, _P], _I),
+    'bmnas_accum_max': ([], _I),
+    'bmnas_grad_combine_multi': ([_P, _P, _I, _P, _I, C.POINTER(C.c_float), _P], _I),
     'bmnas_unroll_virtual_step': ([_P, _P, _I, _P, _I, _P], _I),
     'bmnas_unroll_perturb': ([_P, _P, _I, _P, _I, _P, C.c_float, _P, _P], _I),
     'bmnas_unroll_restore': ([_P, _P, _I, _P], _I),
@@ -1203,6 +1205,23 @@ def avg_multi(table, chunks, n_chunks, rows, n_averaged):
         raise BmnasError('avg_multi: n_averaged must be an int64 device tensor')
     _check(load().bmnas_avg_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, rows.data_ptr(),
                                   n_averaged.data_ptr(), _stream()), 'avg_multi')
+
+
+def accum_max():
+    """BMNAS_ACCUM_MAX: how many parts one grad_combine_multi launch sums."""
+    return load().bmnas_accum_max()
+
+
+def grad_combine_multi(table, chunks, n_chunks, parts, m, weights):
+    """grad = sum_i weights[i] * part_i for every tensor of `table` (bmnas_adam_tensor_t[]: `grad` is the destination,
+    nothing else is read) in one launch.  parts: device tensor holding m `float*` per descriptor, tensor-major (NULL: that
+    part is left out).  weights: m host floats, passed by value — a captured launch keeps them."""
+    ws = [float(w) for w in weights]
+    if len(ws) != m:
+        raise BmnasError(f'grad_combine_multi: {len(ws)} weights for m = {m}')
+    arr = (C.c_float * max(len(ws), 1))(*ws)
+    _check(load().bmnas_grad_combine_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, parts.data_ptr(), m, arr,
+                                           _stream()), 'grad_combine_multi')
 
 
 UNROLL_MOMENTUM = 1                          # BMNAS_UNROLL_* (include/bmnas_hip.h)

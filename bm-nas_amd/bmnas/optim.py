@@ -43,6 +43,10 @@ momentum buffers without writing them.
 `grad` the live one, and no host synchronisation; inside a captured step its scalar rows ride behind the optimizer's
 (`staging_layout(extra_bytes=...)`, `capture_safe(extra=...)`, `rider_rows()`).
 
+`GradAccumulator` (in front of `AveragedModel`) sums up to `lib.accum_max()` micro-batch gradients per tensor into a
+persistent `.grad` with ONE `bmnas_grad_combine_multi` launch (csrc/accum.hip) per optimizer step, eager and captured;
+`accum_weights` gives the n_i / N weights that make m micro-batches the gradient of their union.
+
 `update_bn` (after it) is torch.optim.swa_utils.update_bn for the native BatchNorm kernels: one cumulative-statistics pass
 over a loader (BatchNorm momentum None), optionally as replays of one captured forward.  BatchNorm momentum is read when
 a launch is issued: like Adam's switches it may change between eager steps, but a captured plan (GraphedTrainStep,
@@ -1017,6 +1021,240 @@ class UnrolledStep:
         self._upload()
         lib.unroll_combine(pl['dev_atab'], chunks, n, pl['dev_eta'], pl['R'])
         return out
+
+
+def accum_weights(sizes, reduction='mean'):
+    """The weights of m micro-batch gradients in the gradient of their union: n_i / N for a criterion that averages
+    (`reduction='mean'`: each micro-batch's loss is a mean over its own n_i samples), 1 for one that sums.  Formed in
+    double; the combine launch takes them as fp32.  With these weights the combined gradient is what m data-parallel
+    ranks holding the same shards would all-reduce.  A class-weighted CrossEntropyLoss mean is
+    normalised per micro-batch by its own weight sum — the caveat README states for data parallelism holds here too."""
+    sizes = [int(n) for n in sizes]
+    if not sizes or any(n <= 0 for n in sizes):
+        raise lib.BmnasError(f'accum_weights: micro-batch sizes must be positive, got {sizes}')
+    if reduction == 'sum':
+        return [1.0] * len(sizes)
+    if reduction != 'mean':
+        raise lib.BmnasError(f"accum_weights: reduction must be 'mean' or 'sum', got {reduction!r}")
+    total = sum(sizes)
+    return [n / total for n in sizes]
+
+
+class GradAccumulator:
+    """Gradient accumulation over up to `lib.accum_max()` micro-batches as ONE launch per optimizer step
+    (`bmnas_grad_combine_multi`, csrc/accum.hip): what autograd's AccumulateGrad does with m adds per tensor over m
+    `backward()` calls, and — with `accum_weights` — what the gradient reduction of the reference's nn.DataParallel
+    (`--parallel`, models/search/ntu_darts_searchable.py) computes over its replicas.
+
+        acc = GradAccumulator(optimizer)
+        for (inputs, labels), w in zip(micro_batches, accum_weights(sizes)):
+            grads = torch.autograd.grad(criterion(model(inputs), labels), acc.tensors, allow_unused=True)
+            acc.add(grads, w)                      # keeps references, launches nothing
+        acc.combine()                              # one launch: p.grad = sum_i w_i * part_i
+        optimizer.step()
+
+    The tensors are the optimizer's (`for g in param_groups for p in g['params']`); `grads` follows that order, None
+    entries allowed (`allow_unused`).  A tensor some part covered gets `p.grad` set to its persistent fp32 accumulation
+    tensor (+4 B per parameter, allocated on first use); a NULL part is left out of its sum.  A tensor no part covered
+    gets `p.grad = None`.  The optimizer and the clipping norm downstream see an ordinary `.grad`: every Adam and SGD
+    variant and `max_grad_norm` (the norm of the COMBINED gradient) work unchanged.
+
+    Eager: descriptors, part pointers and the chunk list go up in one pinned async copy guarded by an event — skipped
+    when the bytes are those the device already holds.  The weights travel by value in the launch.  combine()
+    synchronises nothing.
+    Captured (bmnas.graph.GraphedTrainStep(accumulate=m)): `capture_safe(m)` before the capture, `captured_plan()` after
+    it, `abandon_capture()` when it failed.  Inside the capture combine() issues the launch only; the tables — the
+    addresses of the graph's static `autograd.grad` outputs — are uploaded by captured_plan(), eagerly, before the first
+    replay: the graph holds no H2D node of the accumulator.  The plan keeps the parts alive; the weights are constants of
+    the capture."""
+
+    def __init__(self, optimizer):
+        if optimizer is None or not hasattr(optimizer, 'param_groups'):
+            raise lib.BmnasError('bmnas.optim.GradAccumulator needs an optimizer')
+        self.optimizer = optimizer
+        self._acc = {}                   # parameter -> its accumulation tensor
+        self._acc_storage = set()        # their storages' addresses (what add() refuses as a part)
+        self._parts = []                 # [(grads, weight)] since the last combine()
+        self._eager = None
+        self._capturing = None           # the plan of an open capture (capture_safe() ... captured_plan())
+        self._chunk_cache = {}
+        self.launches = 0                # bmnas_grad_combine_multi calls issued from Python (a replayed one is none)
+        self.uploads = 0                 # pinned H2D copies issued so far (a skipped one does not count)
+        self.captures = 0
+
+    @property
+    def tensors(self):
+        return [p for g in self.optimizer.param_groups for p in g['params']]
+
+    @property
+    def pending(self):
+        """How many parts wait for combine()."""
+        return len(self._parts)
+
+    def accumulation_tensor(self, p):
+        """p's accumulation tensor (None before the first plan was built)."""
+        return self._acc.get(p)
+
+    def reset(self):
+        """Drop the pending parts."""
+        self._parts = []
+
+    def add(self, grads, weight):
+        """One micro-batch's gradients (a list aligned with `tensors`, None entries allowed) and its weight.  Validates,
+        keeps references, launches nothing."""
+        ts = self.tensors
+        grads = list(grads)
+        if len(grads) != len(ts):
+            raise lib.BmnasError(f'bmnas.optim.GradAccumulator.add: {len(grads)} gradients for {len(ts)} tensors')
+        if len(self._parts) >= lib.accum_max():
+            raise lib.BmnasError(f'bmnas.optim.GradAccumulator.add: at most {lib.accum_max()} parts per step '
+                                 '(BMNAS_ACCUM_MAX); call combine() first')
+        for g, p in zip(grads, ts):
+            if g is None:
+                continue
+            if (not torch.is_tensor(g) or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device
+                    or g.numel() != p.numel()):
+                raise lib.BmnasError('bmnas.optim.GradAccumulator.add: a part must be contiguous fp32 on the parameter '
+                                     "device, of the parameter's size")
+            if g.untyped_storage().data_ptr() in self._acc_storage:
+                raise lib.BmnasError('bmnas.optim.GradAccumulator.add: a part aliases an accumulation tensor (a '
+                                     '`.grad` that combine() set?); the launch reads every part while it writes there')
+        self._parts.append((grads, float(weight)))
+
+    # ------------------------------------------------------------------ plan
+    def _build(self, ts, m):
+        """A plan with room for every tensor and m parts each: ONE pinned buffer and its device copy,
+        descriptor table | part pointers (tensor-major) | chunk list.  Allocates the accumulation tensors."""
+        if not ts:
+            raise lib.BmnasError('bmnas.optim.GradAccumulator: the optimizer holds no tensors')
+        dev = ts[0].device
+        for p in ts:
+            if not p.is_cuda:
+                raise lib.BmnasError('bmnas.optim.GradAccumulator needs parameters on the GPU (HIP kernel, no CPU path)')
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise lib.BmnasError(f'bmnas.optim.GradAccumulator: parameter must be contiguous fp32 on {dev}')
+            if p not in self._acc:
+                self._acc[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                self._acc_storage.add(self._acc[p].untyped_storage().data_ptr())
+        E = lib.adam_chunk_elems()
+        tab_bytes = len(ts) * _DESC.itemsize
+        chunks_at = (tab_bytes + len(ts) * m * 8 + 15) // 16 * 16
+        nbytes = chunks_at + max(1, sum((p.numel() + E - 1) // E for p in ts)) * 8
+        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        return dict(ids=tuple(id(p) for p in ts), m=m, pin=pin, host=pin.numpy(), dev=devbuf, tab_bytes=tab_bytes,
+                    chunks_at=chunks_at, dev_tab=devbuf[:tab_bytes], dev_parts=devbuf[tab_bytes:chunks_at],
+                    dev_chunks=devbuf[chunks_at:], n_chunks=0, sent=None, event=None)
+
+    def _fill(self, pl, ts, active, parts):
+        """Write the descriptors, part pointers and chunk list of this step's tensors (`active`: indices into ts)."""
+        m, host = len(parts), pl['host']
+        host[:] = 0
+        tab = host[:len(active) * _DESC.itemsize].view(_DESC)
+        tab['grad'] = [self._acc[ts[i]].data_ptr() for i in active]
+        tab['numel'] = [ts[i].numel() for i in active]
+        ptrs = host[pl['tab_bytes']:pl['tab_bytes'] + len(active) * m * 8].view('<u8').reshape(len(active), m)
+        for j, (gs, _) in enumerate(parts):
+            ptrs[:, j] = [0 if gs[i] is None else gs[i].data_ptr() for i in active]
+        key = tuple(active)
+        if key not in self._chunk_cache:
+            E = lib.adam_chunk_elems()
+            self._chunk_cache[key] = np.array(
+                [(a, c) for a, i in enumerate(active) for c in range((ts[i].numel() + E - 1) // E)],
+                dtype=np.int32).reshape(-1)
+        chunks = self._chunk_cache[key]
+        host[pl['chunks_at']:pl['chunks_at'] + chunks.nbytes].view(np.int32)[:] = chunks
+        pl['n_chunks'] = len(chunks) // 2
+
+    @staticmethod
+    def _wait(pl):
+        """Block until the last upload has read the plan's pinned buffer (the host may run ahead of the GPU)."""
+        if pl['event'] is not None:
+            pl['event'].synchronize()
+
+    def _upload(self, pl):
+        """One pinned async copy of everything staged — unless the device already holds exactly these bytes."""
+        if pl['sent'] is not None and np.array_equal(pl['sent'], pl['host']):
+            return
+        pl['dev'].copy_(pl['pin'], non_blocking=True)
+        if pl['event'] is None:
+            pl['event'] = torch.cuda.Event()
+        pl['event'].record()
+        pl['sent'] = pl['host'].copy()
+        self.uploads += 1
+
+    # ------------------------------------------------------------------ the step
+    @torch.no_grad()
+    def combine(self):
+        """One launch: p.grad = sum_i w_i * part_i for every tensor a part covered (None for the others); clears the
+        list.  Returns nothing, synchronises nothing."""
+        if not self._parts:
+            raise lib.BmnasError('bmnas.optim.GradAccumulator.combine: no parts (call add() first)')
+        ts = self.tensors
+        m = len(self._parts)
+        active = [i for i in range(len(ts)) if any(gs[i] is not None for gs, _ in self._parts)]
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            pl = self._capturing
+            if pl is None or pl['m'] != m or pl['ids'] != tuple(id(p) for p in ts) or pl.get('parts') is not None:
+                raise lib.BmnasError('bmnas.optim.GradAccumulator: call capture_safe(m) before capturing combine() in a '
+                                     'graph (once per captured combine, with the number of parts it sums)')
+            if not active:
+                raise lib.BmnasError('bmnas.optim.GradAccumulator: a captured combine() needs at least one gradient')
+        else:
+            pl = self._eager
+            if pl is None or pl['ids'] != tuple(id(p) for p in ts):
+                pl = self._eager = self._build(ts, lib.accum_max())
+            self._wait(pl)
+        parts, self._parts = self._parts, []
+        if active:
+            self._fill(pl, ts, active, parts)
+            if capturing:
+                pl['parts'] = parts              # the graph's static autograd.grad outputs: alive as long as the plan
+            else:
+                self._upload(pl)
+            lib.grad_combine_multi(pl['dev_tab'], pl['dev_chunks'], pl['n_chunks'], pl['dev_parts'], m,
+                                   [w for _, w in parts])
+            self.launches += 1
+        hit = set(active)
+        for i, p in enumerate(ts):
+            p.grad = self._acc[p] if i in hit else None
+        if not capturing and hasattr(self.optimizer, '_touch'):
+            self.optimizer._touch += 1           # .grad re-pointed outside a replay (as zero_grad does)
+
+    # ------------------------------------------------------------------ hipGraph support
+    def capture_safe(self, m):
+        """Build the plan of ONE captured combine() over m parts: its buffers (and every accumulation tensor) are
+        allocated NOW, outside the capture — the graph bakes their addresses."""
+        if self._capturing is not None:
+            raise lib.BmnasError('bmnas.optim.GradAccumulator: capture_safe() while another capture is open (take it '
+                                 'with captured_plan(), or drop it with abandon_capture(), first)')
+        m = int(m)
+        if not 1 <= m <= lib.accum_max():
+            raise lib.BmnasError(f'bmnas.optim.GradAccumulator: m must be in 1 .. {lib.accum_max()}, got {m}')
+        self._parts = []
+        self._capturing = self._build(self.tensors, m)
+
+    def abandon_capture(self):
+        """Drop the plan of a capture that failed."""
+        self._capturing = None
+        self._parts = []
+
+    def captured_plan(self):
+        """The plan a capture has just baked into a graph; uploads its tables (eagerly, in front of the first replay) and
+        closes the capture."""
+        pl = self._capturing
+        if pl is None:
+            raise lib.BmnasError('bmnas.optim.GradAccumulator: no open capture (capture_safe() + a captured combine() '
+                                 'first)')
+        if pl.get('parts') is None:
+            raise lib.BmnasError('bmnas.optim.GradAccumulator: the capture holds no combine()')
+        self._capturing = None
+        self._upload(pl)
+        self._wait(pl)
+        pl['weights'] = [w for _, w in pl['parts']]
+        self.captures += 1
+        return pl
 
 
 # bmnas_avg_row_t (include/bmnas_hip.h)

@@ -22,7 +22,18 @@ Differences, all on the host side of the hot path:
     `best_test_averaged.pt` is saved next to `best_test_model.pt`.  args.swa_update_bn adds the step the SWA recipe
     ends with: the averaged module's BatchNorm statistics are not averaged but recomputed by one cumulative pass over
     the training loader (bmnas.optim.update_bn) before its first evaluation after the weights changed
-    (run.stats['update_bn_passes']).  With no option set nothing changes.
+    (run.stats['update_bn_passes']).  With no option set nothing changes;
+  * optional: gradient accumulation (`accum_steps`: args.accum_steps = m > 1).  The weight steps of the learning phases
+    hold m batches and take ONE optimizer step per group — the reference's `--batchsize 96 --parallel` step on fewer
+    GPUs than the paper's: nn.DataParallel sums the mean-reduced gradients of its shards, here m micro-batches are
+    combined with weights n_i / N (bmnas.optim.GradAccumulator, one bmnas_grad_combine_multi launch).  A full group
+    of one shape is one replay of a GraphedTrainStep(accumulate=m); the ragged tail of a phase — fewer than m batches,
+    or a shorter last one — is ONE eager accumulated step over what is there, never a run of single steps:
+    ceil(batches / m) optimizer steps per phase.  The cosine scheduler still advances once per batch (the schedule's
+    length is unchanged; a step runs with the rates after its group's last batch), the EMA updates once per optimizer
+    step, `_observe('batch', ...)` fires per micro-batch, the architecture step stays one per dev batch.  BatchNorm
+    running statistics advance once per MICRO-batch (nn.DataParallel keeps only replica 0's).  Absent or 1, the loop does
+    what it does without it.
 """
 import copy
 import os
@@ -223,6 +234,41 @@ def steps_per_replay(args):
     return max(1, min(k, 8))
 
 
+def accum_steps(args):
+    """How many batches the learning phases accumulate into ONE optimizer step (`args.accum_steps`; absent, None or
+    unreadable: 1; at most bmnas.lib.accum_max(), the parts one combine launch sums)."""
+    v = getattr(args, 'accum_steps', None)
+    try:
+        m = int(v) if v is not None else 1
+    except (TypeError, ValueError):
+        m = 1
+    if m <= 1:
+        return 1
+    from bmnas import lib
+    return min(m, lib.accum_max())
+
+
+def check_accum(args, world=None):
+    """What `run` refuses at its start with args.accum_steps > 1: k steps per replay (each of the k steps would need its
+    own group), the unrolled architecture step (it draws training batches of its own between weight steps), and data
+    parallelism (one all-reduce per group is not built).  -> accum_steps(args)."""
+    m = accum_steps(args)
+    if m <= 1:
+        return 1
+    if steps_per_replay(args) > 1:
+        raise ValueError(f'args.accum_steps = {m} cannot be combined with steps_per_replay = {steps_per_replay(args)} '
+                         '(k optimizer steps per replay and m batches per optimizer step are two groupings of the '
+                         'same batches: set one of them)')
+    if bool(getattr(args, 'unrolled', False)):
+        raise ValueError(f'args.accum_steps = {m} cannot be combined with args.unrolled (the unrolled architecture step '
+                         'reads the weight optimizer between weight steps)')
+    world = _world() if world is None else world
+    if world > 1:
+        raise ValueError(f'args.accum_steps = {m} is not available under data parallelism ({world} ranks): scale the '
+                         'number of ranks, or accumulate in a single process')
+    return m
+
+
 def _observe(event, **info):
     """tests/test_outer_loop_golden_gpu.py pins the loop against the reference's trainers through this hook
     (run.observer = callable(event, **info)); None in production: no host synchronisation is added."""
@@ -237,6 +283,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     """-> dict(best_dev, best_dev_genotype, best_test, best_test_genotype, last_genotype, nan_abort).
     init: what the first epoch's metric is compared with (the reference starts from best_f1 = init_f1 with `>`,
     train_searchable/mmimdb.py:19,162, and from best_acc = 0 with `>=`, ntu.py:18,135); None: always accepted."""
+    m_accum = check_accum(args)              # (first: a refused combination moves nothing)
     cosine = isinstance(scheduler, sc.LRCosineAnnealingScheduler)
     device = _model_device(model, device)
     from bmnas.graph import GraphedTrainStep
@@ -246,6 +293,12 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     wk_graph, wk_attempts = None, 0
     f_graphs = _ForwardGraphs.of(model, criterion, args, logger)
     stats = run.stats = dict(graph_replays=0, eager_steps=0, forward_replays=0, k_step_replays=0)
+    # gradient accumulation (args.accum_steps = m > 1): the accumulate=m graph of the full groups and the accumulator of
+    # the eager tails; absent or 1 none of this exists and nothing below changes
+    wa_graph, wa_attempts, accumulator = None, 0, None
+    if m_accum > 1:
+        stats['accum_groups'] = 0            # optimizer steps taken over a group of held batches
+        stats['accum_replays'] = 0           # ... of which as ONE replay of the accumulate=m graph
     # weight averaging (found-stage runs only; refused in a search): None without the options — and nothing below changes
     from models.search._common import make_averager
     averaged, avg_opts = make_averager(model, args, status)
@@ -438,6 +491,66 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
                              learn=True, how='graph', lr=lr)
 
+            def accum_group(batches):
+                """Up to m held batches as ONE optimizer step: a full group of one shape is a replay of the accumulate=m
+                graph; anything else — the tail of a phase, no capture — is one eager accumulated step, the gradients
+                of the micro-batches combined with weights n_i / N by the same bmnas.optim.GradAccumulator."""
+                nonlocal wa_graph, wa_attempts, accumulator, loss_sum
+                from bmnas.optim import GradAccumulator, accum_weights
+                stats['accum_groups'] += 1
+                x0, y0 = batches[0]
+                flat = all(isinstance(x_, (list, tuple)) for x_, _ in batches)
+                one_shape = flat and len(batches) == m_accum and all(
+                    y_.shape == y0.shape and len(x_) == len(x0) and all(a.shape == b.shape for a, b in zip(x_, x0))
+                    for x_, y_ in batches)
+                if use_graph and one_shape:
+                    if wa_graph is None and wa_attempts < 3:
+                        wa_attempts += 1
+                        wa_graph = GraphedTrainStep.try_build(model, criterion, optimizer, x0, y0, logger, averaged=ema,
+                                                              accumulate=m_accum) or None
+                    if wa_graph and wa_graph.matches_group(batches):
+                        for j, (x_, y_) in enumerate(batches):
+                            if cosine:
+                                scheduler.step()
+                                scheduler.update_optimizer(optimizer)
+                            wa_graph.stage(j, x_, y_)        # (the step's scalars are fixed with the LAST micro-batch)
+                        outs = wa_graph.replay_staged()
+                        stats['accum_replays'] += 1
+                        averaged_step(in_replay=wa_graph.averaged is not None)
+                        for (loss, output), (x_, y_) in zip(outs, batches):
+                            loss_sum += loss.detach().double() * y_.size(0)
+                            meter.update(output.detach(), y_)
+                            stats['graph_replays'] += 1
+                            _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
+                                     learn=True, how='graph')
+                        return
+                if accumulator is None:
+                    accumulator = GradAccumulator(optimizer)
+                accumulator.reset()
+                targets = accumulator.tensors
+                ws = accum_weights([y_.size(0) for _, y_ in batches], getattr(criterion, 'reduction', 'mean'))
+                for (x_, y_), w_ in zip(batches, ws):
+                    stats['eager_steps'] += 1
+                    if cosine:
+                        scheduler.step()
+                        scheduler.update_optimizer(optimizer)
+                    output = net(x_)
+                    if isinstance(output, tuple):
+                        output = output[-1]
+                    loss = criterion(output, y_)
+                    live = [t for t in targets if t.requires_grad]
+                    got_g = iter(torch.autograd.grad(loss, live, allow_unused=True))
+                    grads = [next(got_g) if t.requires_grad else None for t in targets]
+                    accumulator.add([g if g is None else g.contiguous() for g in grads], w_)
+                    loss_sum += loss.detach().double() * y_.size(0)
+                    meter.update(output.detach(), y_)
+                    _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
+                             learn=True, how='eager')
+                    output = loss = grads = got_g = None     # (no autograd graph may outlive the step: a later capture)
+                accumulator.combine()
+                optimizer.step()
+                averaged_step()
+
             def k_arch_batches(batches):
                 """The dev phase of a search: k (architecture step + metric forward) pairs as ONE replay."""
                 nonlocal loss_sum
@@ -460,12 +573,17 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
             arch_phase = (status == 'search' and phase in ('dev', 'test') and architect is not None and not learn
                           and f_graphs.on and hasattr(architect, 'step_k') and not unrolled)
             group = k_batches if learn else (k_arch_batches if arch_phase else None)
+            accumulating = learn and m_accum > 1         # (then k_steps == 1 and the world is one process: check_accum)
+            hold_n = m_accum if accumulating else k_steps
             held, held_w = [], []                       # batches waiting for their k-step replay (+ their shard weights)
 
             def flush():
                 # (a shard weight belongs to ITS batch: uneven scatters of different global sizes must not share a replay)
                 nonlocal held, held_w
-                if len(held) == k_steps and len(set(held_w)) == 1:
+                if accumulating:
+                    if held:                            # a full group, or the tail of the phase: ONE optimizer step
+                        accum_group(held)
+                elif len(held) == k_steps and len(set(held_w)) == 1:
                     _set_weight(held_w[0])
                     group(held)
                 else:                                   # the ragged tail of a phase: single steps
@@ -479,10 +597,11 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 if split:
                     inputs, labels = _shard_batch(inputs, labels)
                 seen += labels.size(0)
-                if group is not None and k_steps > 1 and isinstance(inputs, (list, tuple)) and labels.size(0):
+                if accumulating or (group is not None and k_steps > 1 and isinstance(inputs, (list, tuple))
+                                    and labels.size(0)):
                     held.append((inputs, labels))
                     held_w.append(_weight())
-                    if len(held) == k_steps:
+                    if len(held) == hold_n:
                         flush()
                     continue
                 w_now = _weight()

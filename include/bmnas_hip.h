@@ -1012,6 +1012,29 @@ typedef struct {
 int bmnas_avg_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
                     const bmnas_avg_row_t* rows, int64_t* n_averaged, void* stream);
 
+/* ---- gradient accumulation: grad = sum_i w_i * part_i in one launch (csrc/accum.hip) --------------------------
+ * Replaces autograd's AccumulateGrad over m backward passes (m adds per tensor) and, with w_i = n_i / N over m
+ * mean-reduced micro-batches, the gradient reduction of nn.DataParallel in the reference's train_darts_model
+ * (models/search/ntu_darts_searchable.py: `--parallel`, batch 96 scattered over the GPUs).  One launch per optimizer
+ * step over the descriptor table and (tensor, chunk) list of bmnas_adam_multi, whatever m is.
+ *   The destination is a descriptor's `grad` (written as bmnas_grad_scale_multi writes it); `param`, `exp_avg`,
+ *     `exp_avg_sq` and `hyp_row` are not read and may be NULL / anything.
+ *   parts: DEVICE array of m pointers per descriptor, tensor-major: parts[t * m + i] is part i of tensor t (fp32, the
+ *     tensor's size, any 4-byte alignment; it must not overlap the destination).  NULL: micro-batch i gave tensor t no
+ *     gradient.
+ *   weights: HOST array of m floats, taken by value into the kernel arguments (a captured launch keeps them).
+ * Per element, every operation rounded on its own (no fused multiply-add), over the non-NULL parts in ascending i:
+ *     acc = w_i0 * g_i0;   acc = acc + w_i * g_i
+ *   A NULL part is left out, not added as zero; with every part NULL the element is +0.  w == 1 leaves the bits of the
+ *   part (m = 1, w = 1: a bit copy).  NaN propagates.
+ * Reads the non-NULL parts, writes `grad`: 4 (m + 1) B per parameter.  No atomics: bit-identical from run to run.
+ * BMNAS_E_ARG (nothing launched): NULL tensors / chunks / parts / weights; m < 1; m > BMNAS_ACCUM_MAX; n_chunks < 0.
+ * n_chunks == 0 is a no-op. */
+#define BMNAS_ACCUM_MAX 8
+int bmnas_accum_max(void);
+int bmnas_grad_combine_multi(const bmnas_adam_tensor_t* tensors, const int32_t* chunks, int n_chunks,
+                             const float* const* parts, int m, const float* weights, void* stream);
+
 /* ---- unrolled (second-order) architecture step of DARTS (csrc/unroll.hip) -----------------------------------
  * The reference still passes `unrolled=args.unrolled` to its Architect (models/search/darts/train_search.py:151,
  * the flag at :42 and main_darts_found_ntu.py:48) and keeps `network_weight_decay` for it
