@@ -801,14 +801,19 @@ class ConvBnReluLnFn(Function):
                 *dsrcs)
 
 
+POOL_DTYPES = tuple(lib.POOL_DTYPES)      # element types of the pooling launches' inputs: fp32, bf16, fp16
+
+
 class PoolGroupFn(Function):
     """The AdaptiveMaxPool2d in front of every reshape conv (aux_models.py:62-70, 101-108), all modalities in ONE
     launch per direction (csrc/pool.hip), output in the (b, C_in, L) layout the grouped GEMM reads.
-    dims[i] = (C, H, W, oh, ow) of input i viewed as (b, C, H, W)."""
+    dims[i] = (C, H, W, oh, ow) of input i viewed as (b, C, H, W).  Inputs are fp32, bf16 or fp16, each its own (the
+    feature maps of a backbone under torch.autocast are pooled as they are); the outputs are fp32 — the exact widening
+    of the winning elements — and every input's gradient has the input's dtype."""
 
     @staticmethod
     def forward(ctx, dims, *xs):
-        xs = [_c(_f32(x)) for x in xs]
+        xs = [_c(x if x.dtype in POOL_DTYPES else _f32(x)) for x in xs]
         _require_gpu(xs[0], 'reshape-layer pooling')
         b, dev = xs[0].shape[0], xs[0].device
         outs = [torch.empty((b, d[0], d[3] * d[4]), device=dev, dtype=torch.float32) for d in dims]
@@ -816,6 +821,7 @@ class PoolGroupFn(Function):
         idxs = [torch.empty((b, d[0], d[3] * d[4]), device=dev, dtype=torch.int32) if need else None for d in dims]
         lib.adaptive_maxpool_group(xs, dims, outs, idxs, b)
         ctx.dims, ctx.idxs, ctx.shapes, ctx.b = dims, idxs, [tuple(x.shape) for x in xs], b
+        ctx.dtypes = [x.dtype for x in xs]
         return tuple(outs)
 
     @staticmethod
@@ -825,7 +831,7 @@ class PoolGroupFn(Function):
         if sel:
             dev = ctx.idxs[sel[0]].device
             g = [torch.zeros_like(ctx.idxs[i], dtype=torch.float32) if gs[i] is None else _c(gs[i]) for i in sel]
-            dx = [torch.empty(ctx.shapes[i], device=dev, dtype=torch.float32) for i in sel]
+            dx = [torch.empty(ctx.shapes[i], device=dev, dtype=ctx.dtypes[i]) for i in sel]
             lib.adaptive_maxpool_group_bwd(g, [ctx.idxs[i] for i in sel], dx, [ctx.dims[i] for i in sel], ctx.b)
             for i, t in zip(sel, dx):
                 dxs[i] = t

@@ -126,6 +126,18 @@ class PoolProb(C.Structure):
                 ('C', C.c_int), ('H', C.c_int), ('W', C.c_int), ('oh', C.c_int), ('ow', C.c_int)]
 
 
+class PoolProbEx(C.Structure):
+    """bmnas_pool_prob_ex_t: bmnas_pool_prob_t with untyped x / dx and their element type"""
+    _fields_ = [('x', C.c_void_p), ('out', C.c_void_p), ('idx', C.c_void_p), ('g', C.c_void_p), ('dx', C.c_void_p),
+                ('C', C.c_int), ('H', C.c_int), ('W', C.c_int), ('oh', C.c_int), ('ow', C.c_int), ('dtype', C.c_int)]
+
+
+DT_F32, DT_BF16, DT_F16 = 0, 1, 2                  # BMNAS_DT_*
+
+
+POOL_DTYPES = {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_F16}   # of the pooling launches' x / dx
+
+
 class ConvFwdProb(C.Structure):
     """bmnas_conv_fwd_prob_t"""
     _fields_ = [('src', C.c_void_p), ('W', C.c_void_p), ('bias', C.c_void_p), ('U', C.c_void_p),
@@ -248,6 +260,8 @@ SIGNATURES = {
     'bmnas_bn_mish_bwd': ([_P, _P, _P, _P, _P, _I, _I, _I, Dropout, _P], _I),
     'bmnas_adaptive_maxpool_fwd_group': ([C.POINTER(PoolProb), _I, _I, _P], _I),
     'bmnas_adaptive_maxpool_bwd_group': ([C.POINTER(PoolProb), _I, _I, _P], _I),
+    'bmnas_adaptive_maxpool_fwd_group_ex': ([C.POINTER(PoolProbEx), _I, _I, _P], _I),
+    'bmnas_adaptive_maxpool_bwd_group_ex': ([C.POINTER(PoolProbEx), _I, _I, _P], _I),
     'bmnas_conv1x1_group_ok': ([_I, C.POINTER(C.c_int), _I, _I, _I], _I),
     'bmnas_conv1x1_fwd_group': ([C.POINTER(ConvFwdProb), _I, _I, _I, _I, _I, _P], _I),
     'bmnas_bn_relu_fwd_group': ([C.POINTER(BnReluFwdProb), _I, _I, _I, _I, _P], _I),
@@ -684,25 +698,37 @@ def node_mix_lnp_bwd(gy, pre, ln_w, stats, lnp0, lnp1, g_in, dresid, acc_resid, 
                                          _ptr(bn_part), _stream()), 'node_mix_lnp_bwd')
 
 
+def _pool_ptr(t):
+    """(address, BMNAS_DT_*) of a pooling input / input gradient"""
+    if t.dtype not in POOL_DTYPES:
+        raise TypeError(f'bmnas pooling takes fp32, bf16 or fp16 tensors (got {t.dtype})')
+    assert t.is_cuda and t.is_contiguous(), (t.device, t.is_contiguous())
+    return t.data_ptr(), POOL_DTYPES[t.dtype]
+
+
 def adaptive_maxpool_group(xs, dims, outs, idxs, b):
     """Forward of the grouped AdaptiveMaxPool2d: xs[i] contiguous (b, C_i, ...) viewed as (b, C_i, H_i, W_i) with
-    dims[i] = (C, H, W, oh, ow); outs[i] (b, C, oh * ow); idxs[i] int32 like outs[i], or None."""
+    dims[i] = (C, H, W, oh, ow), fp32, bf16 or fp16 (each problem its own); outs[i] fp32 (b, C, oh * ow); idxs[i] int32
+    like outs[i], or None."""
     n = len(xs)
-    probs = (PoolProb * n)()
+    probs = (PoolProbEx * n)()
     for i in range(n):
         Cc, H, W, oh, ow = dims[i]
-        probs[i] = PoolProb(_ptr(xs[i]), _ptr(outs[i]), None if idxs[i] is None else idxs[i].data_ptr(), None, None,
-                            Cc, H, W, oh, ow)
-    _check(load().bmnas_adaptive_maxpool_fwd_group(probs, n, b, _stream()), 'adaptive_maxpool_fwd_group')
+        x, dt = _pool_ptr(xs[i])
+        probs[i] = PoolProbEx(x, _ptr(outs[i]), None if idxs[i] is None else idxs[i].data_ptr(), None, None,
+                              Cc, H, W, oh, ow, dt)
+    _check(load().bmnas_adaptive_maxpool_fwd_group_ex(probs, n, b, _stream()), 'adaptive_maxpool_fwd_group_ex')
 
 
 def adaptive_maxpool_group_bwd(gs, idxs, dxs, dims, b):
+    """Backward: gs[i] fp32 like outs[i]; dxs[i] of the type its input had, every element written."""
     n = len(gs)
-    probs = (PoolProb * n)()
+    probs = (PoolProbEx * n)()
     for i in range(n):
         Cc, H, W, oh, ow = dims[i]
-        probs[i] = PoolProb(None, None, idxs[i].data_ptr(), _ptr(gs[i]), _ptr(dxs[i]), Cc, H, W, oh, ow)
-    _check(load().bmnas_adaptive_maxpool_bwd_group(probs, n, b, _stream()), 'adaptive_maxpool_bwd_group')
+        dx, dt = _pool_ptr(dxs[i])
+        probs[i] = PoolProbEx(None, None, idxs[i].data_ptr(), _ptr(gs[i]), dx, Cc, H, W, oh, ow, dt)
+    _check(load().bmnas_adaptive_maxpool_bwd_group_ex(probs, n, b, _stream()), 'adaptive_maxpool_bwd_group_ex')
 
 
 def conv1x1_group_ok(c_ins, b, L, M):

@@ -31,6 +31,21 @@ class GlobalPooling1D(nn.Module):
         return torch.mean(x, 2)
 
 
+HALF = (torch.bfloat16, torch.float16)     # what a backbone under torch.autocast hands over; pooled natively as it is
+
+
+def _poolable(f, on_device=None):
+    """Can the grouped pooling launch (PoolGroupFn) take this feature?  on_device: stands in for f.is_cuda (pool_groups)."""
+    return (torch.is_tensor(f) and (f.is_cuda if on_device is None else on_device)
+            and f.dtype in (torch.float32,) + HALF and f.dim() >= 2
+            and f.numel() > 0 and f[0, 0].numel() < (1 << 31))
+
+
+def _widen(pooled):
+    """A half pooled tensor widens to fp32 (exact) in front of the conv: everything behind the pool is fp32."""
+    return pooled.float() if torch.is_tensor(pooled) and pooled.dtype in HALF else pooled
+
+
 class _ReshapeBase(nn.Module):
     def __init__(self, C_in, C, L, args):
         super().__init__()
@@ -42,6 +57,7 @@ class _ReshapeBase(nn.Module):
     def _tail(self, pooled):
         """conv -> bn -> relu -> dropout on a (b, C_in, L) tensor."""
         bn = self.bn
+        pooled = _widen(pooled)
         if pooled.is_cuda and self.conv.in_channels % 16 == 0 and self.C % 16 == 0 and self.L in (4, 8, 16):
             return ConvBnActFn.apply('relu', self.dropout.p, self.training, bn.running_mean, bn.running_var,
                                      bn.num_batches_tracked, bn.momentum, self.conv.weight, self.conv.bias, bn.weight,
@@ -50,6 +66,12 @@ class _ReshapeBase(nn.Module):
         lib.note_off_path(type(self).__name__, f'pooled input {tuple(pooled.shape)} on {pooled.device} '
                           f'(needs HIP device, C_in % 16 == 0, C % 16 == 0, L in 4/8/16)')
         return self.dropout(F.relu(bn(self.conv(pooled))))
+
+    def forward(self, x):
+        if x.dtype in HALF and _poolable(x):
+            # a half feature on the device: the native pool as a group of one (its fp32 output is what the tail takes)
+            return self._tail(PoolGroupFn.apply([self.pool_dims(x)], x)[0])
+        return self._tail(self.pooled(x))
 
 
 class ReshapeInputLayer(_ReshapeBase):
@@ -71,9 +93,6 @@ class ReshapeInputLayer(_ReshapeBase):
         H = x.size(2) if x.dim() > 2 else 1
         return (x.size(1), H, max(1, x[0, 0].numel() // H), self.L, 1)
 
-    def forward(self, x):
-        return self._tail(self.pooled(x))
-
 
 class ReshapeInputLayer_MMIMDB(_ReshapeBase):
     """(b, C_in[, H, W]) -> adaptive max pool to (sqrt L, sqrt L) -> (b, C, L)."""
@@ -94,9 +113,6 @@ class ReshapeInputLayer_MMIMDB(_ReshapeBase):
         side = int(math.sqrt(self.L * 1.0))
         return (x.size(1), H, max(1, x[0, 0].numel() // H), side, side)
 
-    def forward(self, x):
-        return self._tail(self.pooled(x))
-
 
 def reshape_tails(layers, pooled):
     """[layer._tail(f) for layer, f in zip(layers, pooled)] — the conv -> bn -> relu -> dropout stacks of the
@@ -106,6 +122,7 @@ def reshape_tails(layers, pooled):
     own, exactly as before."""
     from bmnas import lib
     outs = [None] * len(layers)
+    pooled = [_widen(f) if isinstance(layer, _ReshapeBase) else f for layer, f in zip(layers, pooled)]
     idx = [i for i, (layer, f) in enumerate(zip(layers, pooled))
            if isinstance(layer, _ReshapeBase) and torch.is_tensor(f) and f.is_cuda and f.dim() == 3
            and f.dtype == torch.float32]
@@ -135,24 +152,34 @@ def reshape_tails(layers, pooled):
     return outs
 
 
+def pool_groups(layers, features, on_device=None):
+    """The grouped pooling launches reshape_all makes: a list of index lists, one per launch (one batch size, at most
+    lib.MAX_GROUP members).  Device features go through the launch when there are at least two of them with one batch
+    size; a bf16 / fp16 feature goes through it in any case, alone if need be — its pooled tensor is fp32, which the
+    torch pool would not give.  on_device=True decides as if every tensor lay on the device (a meta tensor shows the
+    routing without a launch)."""
+    from bmnas import lib
+    idx = [i for i, (layer, f) in enumerate(zip(layers, features))
+           if isinstance(layer, _ReshapeBase) and _poolable(f, on_device)]
+    if not (len(idx) >= 2 and len({features[i].shape[0] for i in idx}) == 1):
+        idx = [i for i in idx if features[i].dtype in HALF]
+    by_batch = {}
+    for i in idx:
+        by_batch.setdefault(features[i].shape[0], []).append(i)
+    return [same[k:k + lib.MAX_GROUP] for same in by_batch.values() for k in range(0, len(same), lib.MAX_GROUP)]
+
+
 def reshape_all(layers, features):
     """[layer(f) for layer, f in zip(layers, features)] with the conv stacks grouped (reshape_tails)."""
-    idx = [i for i, (layer, f) in enumerate(zip(layers, features))
-           if isinstance(layer, _ReshapeBase) and torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32
-           and f.dim() >= 2 and f.numel() > 0 and f[0, 0].numel() < (1 << 31)]
     pooled = list(features)
-    if len(idx) >= 2 and len({features[i].shape[0] for i in idx}) == 1:
+    native = set()
+    for part in pool_groups(layers, features):
         # the adaptive max pools of all modalities in one launch (PoolGroupFn), at most lib.MAX_GROUP at a time
-        from bmnas import lib
-        for k in range(0, len(idx), lib.MAX_GROUP):
-            part = idx[k:k + lib.MAX_GROUP]
-            dims = [layers[i].pool_dims(features[i]) for i in part]
-            res = PoolGroupFn.apply(dims, *[features[i] for i in part])
-            for i, r in zip(part, res):
-                pooled[i] = r
-        idx = set(idx)
-    else:
-        idx = set()
-    pooled = [f if (i in idx or not isinstance(layer, _ReshapeBase)) else layer.pooled(f)
+        dims = [layers[i].pool_dims(features[i]) for i in part]
+        res = PoolGroupFn.apply(dims, *[features[i] for i in part])
+        for i, r in zip(part, res):
+            pooled[i] = r
+        native.update(part)
+    pooled = [f if (i in native or not isinstance(layer, _ReshapeBase)) else layer.pooled(f)
               for i, (layer, f) in enumerate(zip(layers, pooled))]
     return reshape_tails(layers, pooled)

@@ -1,5 +1,7 @@
 """Shared pieces of the per-dataset search drivers (the reference repeats them three times in
 {mmimdb,ntu,ego}_darts_searchable.py).  Not part of the reference's public surface."""
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.optim as op
@@ -57,6 +59,23 @@ def make_criterion(kind, args, device=None):
     raise ValueError(f'criterion kind {kind!r}')
 
 
+BACKBONE_DTYPES = {'bf16': torch.bfloat16, 'fp16': torch.float16}
+
+
+def backbone_dtype_option(args):
+    """args.backbone_dtype (optional; the reference's argument sets have none): 'bf16' or 'fp16' runs the backbones —
+    and only them — under torch.autocast, so the reshape layers are handed half feature maps, which their pooling
+    launch reads as they are (half the bytes of the step's largest tensors; the pooled tensors and everything behind
+    them stay fp32).  Absent or None: the backbones run as they always did.  -> torch dtype or None."""
+    value = getattr(args, 'backbone_dtype', None)
+    if value is None:
+        return None
+    if value not in BACKBONE_DTYPES:
+        from bmnas.lib import BmnasError
+        raise BmnasError(f"args.backbone_dtype must be 'bf16', 'fp16' or absent / None, got {value!r}")
+    return BACKBONE_DTYPES[value]
+
+
 class HyperNetBase(nn.Module):
     """backbones (set by the subclass) -> reshape_layers -> fusion_net -> central_classifier.
     Attribute names are the reference's: trainers reach into .reshape_layers / .fusion_net."""
@@ -66,6 +85,7 @@ class HyperNetBase(nn.Module):
     def _build_head(self, args, criterion, reshape_layers, num_input_nodes, num_keep_edges,
                     genotype=None, logger=None):
         self.args = args
+        self._backbone_dtype = backbone_dtype_option(args)
         self.criterion = criterion
         self._criterion = criterion
         self.reshape_layers = reshape_layers
@@ -99,6 +119,15 @@ class HyperNetBase(nn.Module):
             else:
                 layers.append(nn.ReLU())
         return layers
+
+    def backbone_autocast(self):
+        """The context the forwards run their backbones in (never self.fuse): torch.autocast to args.backbone_dtype on
+        the model's device, or nothing at all without the option."""
+        dtype = getattr(self, '_backbone_dtype', None)
+        if dtype is None:
+            return contextlib.nullcontext()
+        p = next(self.parameters(), None)
+        return torch.autocast(device_type='cuda' if p is None else p.device.type, dtype=dtype)
 
     def reshape_input_features(self, input_features):
         # = [layer(f) for layer, f in zip(self.reshape_layers, input_features)], the conv stacks of all

@@ -43,8 +43,9 @@ class _RGBDepthBase(HyperNetBase):
         rgb, depth = inputs
         self.rgb_net.eval()                           # frozen feature extractors
         self.depth_net.eval()
-        rgb_features = self.rgb_net(rgb)[0:-1]
-        depth_features = self.depth_net(depth)[0:-1]
+        with self.backbone_autocast():
+            rgb_features = self.rgb_net(rgb)[0:-1]
+            depth_features = self.depth_net(depth)[0:-1]
         return self.fuse(list(rgb_features) + list(depth_features))
 
 

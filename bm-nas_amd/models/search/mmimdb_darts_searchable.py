@@ -33,8 +33,9 @@ class _ImageTextBase(HyperNetBase):
 
     def forward(self, tensor_tuple):
         text, image = tensor_tuple
-        image_features = self.imagenet(image)[0:-1]
-        text_features = self.textnet(text)[0:-1]
+        with self.backbone_autocast():
+            image_features = self.imagenet(image)[0:-1]
+            text_features = self.textnet(text)[0:-1]
         return self.fuse(list(image_features) + list(text_features))
 
 

@@ -35,8 +35,9 @@ class _SkeletonImageBase(HyperNetBase):
 
     def forward(self, tensor_tuple):
         skeleton, image = tensor_tuple[1], tensor_tuple[0]
-        visual_features = self.rgbnet(image)[-5:-1]
-        skel_features, _ = self.skenet(skeleton)
+        with self.backbone_autocast():
+            visual_features = self.rgbnet(image)[-5:-1]
+            skel_features, _ = self.skenet(skeleton)
         return self.fuse(list(visual_features) + list(skel_features[-4:]))
 
 

@@ -555,6 +555,28 @@ typedef struct {
 } bmnas_pool_prob_t;
 int bmnas_adaptive_maxpool_fwd_group(const bmnas_pool_prob_t* probs, int n, int b, void* stream);
 int bmnas_adaptive_maxpool_bwd_group(const bmnas_pool_prob_t* probs, int n, int b, void* stream);
+/* The same two launches with a per-problem element type of x / dx, so that the bf16 / fp16 feature maps a backbone
+ * produces under torch.autocast are pooled as they are (no widening copy): bmnas_pool_prob_t with untyped x / dx and
+ * a type code; a zero-initialised descriptor is an fp32 problem, and one group may mix the types.  out, g and idx keep
+ * their types: the pooled tensor is the fp32 widening of the winning element (exact), the rule above is unchanged.
+ * Backward: the fp32 sum over the covering windows is rounded once, to nearest even, to the element type (a NaN stays
+ * a NaN).  Half x / dx must be 2-byte aligned and need nothing more: 16-byte accesses are used wherever they lie
+ * inside the tensor, and no access touches a byte outside [x, x + 2 b C H W).  An unknown type code returns
+ * BMNAS_E_ARG before any launch.  The two entry points above forward here with dtype 0. */
+#define BMNAS_DT_F32 0
+#define BMNAS_DT_BF16 1
+#define BMNAS_DT_F16 2
+typedef struct {
+  const void* x;         /* forward: (b, C, H, W) of `dtype` */
+  float* out;            /* forward: (b, C, oh * ow) */
+  int* idx;              /* forward: written if not NULL; backward: read */
+  const float* g;        /* backward: gradient of out */
+  void* dx;              /* backward: (b, C, H, W) of `dtype`, every element written */
+  int C, H, W, oh, ow;
+  int dtype;             /* BMNAS_DT_* */
+} bmnas_pool_prob_ex_t;
+int bmnas_adaptive_maxpool_fwd_group_ex(const bmnas_pool_prob_ex_t* probs, int n, int b, void* stream);
+int bmnas_adaptive_maxpool_bwd_group_ex(const bmnas_pool_prob_ex_t* probs, int n, int b, void* stream);
 int bmnas_conv1x1_group_ok(int n, const int* C_in, int b, int L, int M);
 int bmnas_conv1x1_fwd_group(const bmnas_conv_fwd_prob_t* probs, int n, int stat_shards, int b, int L, int M,
                             void* stream);
