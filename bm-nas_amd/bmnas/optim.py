@@ -33,6 +33,11 @@ the refusals that open `prepare_replay` —; each class says which state tensors
 what keys a scalar row (`_row_count`) and what it holds (`prepare_replay`), which entries of the plan are its own
 (`_plan_fields`) and which launch updates (`_update`).
 
+Every plan of this file — the optimizers', `UnrolledStep`'s, `GradAccumulator`'s, `AveragedModel`'s — keeps what it stages
+in one `_Staging`: the pinned buffer, its device copy, the one async copy between them and the event that keeps the host
+from rewriting the pinned bytes before that copy has read them (explained there, once).  The bytes are laid out by
+`staging_layout`, the (tensor, chunk) list every launch walks comes from `_chunk_pairs`.
+
 `UnrolledStep` (beside `clip_grad_norm_`, at the end) is no optimizer: it holds the weight-side arithmetic of DARTS'
 unrolled architecture step — virtual weight step, +-R perturbation, restore, and the combine over alpha — on the kernels
 of csrc/unroll.hip, over the same descriptor table, chunk list and norm launch, reading a weight optimizer's groups and
@@ -89,7 +94,12 @@ def staging_layout(n_rows, n_tensors, slots=1, clip=False, tail_ptrs_per_tensor=
     slots > 1: a captured graph that holds `slots` consecutive optimizer steps (bmnas.graph.GraphedTrainStep(k=...)): every
     step has its own scalar rows and its own descriptor table (each step's backward leaves its gradients in tensors of
     its own).  -> sizes (`hyp_slot`, `tab_slot`: a slot's stride in its region) and, per slot, where its rows, its clip
-    scalar (None without clipping), its table and its tail pointers start."""
+    scalar (None without clipping), its table and its tail pointers start.
+
+    The other plans are cases of it: UnrolledStep's is a clipped one-slot plan with (r, eta) where max_grad_norm goes and
+    the alpha table behind `nbytes`; GradAccumulator's has no rows and its part pointers as the tail; AveragedModel's has
+    no rows but a rider's — its own, or none when they ride in an optimizer's buffer.  The last two keep their chunk list
+    in the same buffer, at `_chunks_at`."""
     row_bytes = n_rows * 32
     hyp_slot = row_bytes + (16 if clip else 0)
     if extra_bytes < 0 or extra_bytes % 32:
@@ -104,17 +114,89 @@ def staging_layout(n_rows, n_tensors, slots=1, clip=False, tail_ptrs_per_tensor=
                          slots * hyp_slot)
 
 
-def _chunk_list(numels, device):
-    """-> (int32 tensor (n, 2) on `device`, n): one (tensor index, chunk index) per workgroup of a multi-tensor launch."""
+def _chunks_at(lay):
+    """Where the chunk list of a plan that keeps it INSIDE its staging buffer starts: behind the layout, 16-byte aligned."""
+    return (lay.nbytes + 15) // 16 * 16
+
+
+def _chunk_pairs(numels):
+    """-> int32 array (n, 2): one (tensor index, chunk index) per workgroup of a multi-tensor launch over tensors of
+    `numels` elements (an empty tensor takes none)."""
     E = lib.adam_chunk_elems()
-    chunks = [(i, c) for i, n in enumerate(numels) for c in range((n + E - 1) // E)]
-    return torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(device), len(chunks)
+    return np.array([(i, c) for i, n in enumerate(numels) for c in range((n + E - 1) // E)],
+                    dtype=np.int32).reshape(-1, 2)
+
+
+def _chunk_list(numels, device):
+    """-> (int32 tensor (n, 2) on `device`, n): `_chunk_pairs` as a device tensor of its own."""
+    pairs = _chunk_pairs(numels)
+    return torch.from_numpy(pairs).to(device), len(pairs)
+
+
+class _Staging:
+    """A plan's pinned staging buffer (`pin`, `host` its numpy view) and its device copy (`dev`).  Whatever a plan stages
+    — descriptor tables, scalar rows, pointers, a chunk list — goes up in ONE async H2D copy.  The copy reads the pinned
+    bytes when the stream gets there, not when it is issued, and the host may run ahead of the GPU: `mark()` records an
+    event behind the copy, `wait()` blocks on it, and nobody rewrites `host` without `wait()` first — rewriting earlier
+    would silently change a step still in flight.  `upload()` is the whole sequence for plans whose bytes often repeat:
+    it is skipped when `host` equals `sent`, the bytes the device already holds."""
+
+    def __init__(self, nbytes, device):
+        self.pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+        self.host = self.pin.numpy()
+        self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self.event = None
+        self.sent = None
+
+    def wait(self):
+        """Block until the last marked copy has read the pinned buffer (at once when there was none)."""
+        if self.event is not None:
+            self.event.synchronize()
+
+    def copy(self):
+        """The bare copy: stream work only, so it can be captured in a graph."""
+        self.dev.copy_(self.pin, non_blocking=True)
+
+    def mark(self):
+        """Record, on the current stream, that everything queued so far has read the pinned buffer."""
+        if self.event is None:
+            self.event = torch.cuda.Event()
+        self.event.record()
+
+    def upload(self):
+        """copy() + mark(), unless the device already holds exactly these bytes; -> whether a copy was issued."""
+        if self.sent is not None and np.array_equal(self.sent, self.host):
+            return False
+        self.copy()
+        self.mark()
+        self.sent = self.host.copy()
+        return True
+
+
+def _param_device(params, name):
+    """-> the one GPU `params` live on; refuses, in `name`'s name, what the kernels cannot take."""
+    dev = params[0].device
+    for p in params:
+        if not p.is_cuda:
+            raise lib.BmnasError(f'{name} needs parameters on the GPU (HIP kernel, no CPU path)')
+        if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+            raise lib.BmnasError(f'{name}: parameter must be contiguous fp32 on {dev}')
+    return dev
+
+
+def _check_like(t, p, name, what):
+    """Refuse, in `name`'s name, a tensor (`what` in the message) that a launch could not read or write beside p."""
+    if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != p.device
+            or t.numel() != p.numel()):
+        raise lib.BmnasError(f"{name}: {what} must be contiguous fp32 on the parameter device, of the parameter's size")
 
 
 class _OneLaunch:
     """What bmnas.optim.Adam and bmnas.optim.SGD share: the plan and its builder (`_build`, over `staging_layout`), the
     eager step over a plan, the captured plan and its replay protocol (capture_safe / captured_plan / activate /
-    prepare_replay / replay_blob / wait_staging / mark_launched), switching between plans, and max_grad_norm.  Mixed in
+    prepare_replay / replay_blob / wait_staging / mark_launched), switching between plans, and max_grad_norm.  A plan's
+    scalars change with every step, so it never takes `_Staging.upload()`'s short-cut: a step is wait_staging(), the bare
+    `copy()` in `_launch` (which a capture turns into the graph's copy node) and mark_launched().  Mixed in
     FRONT of the torch optimizer class.  The class supplies `_NAME`, `_SHARED` (what the tensors of a row share, for
     `_switch`'s refusal), `_variant()` (the key of a plan: clipping first, then `_switches()`), `_row_count(p, switches)`
     (a tensor's row count as the state has it now), `_plan_fields(switches)`, `_state_ptrs(plan)`, `_update(...)` (the
@@ -172,13 +254,9 @@ class _OneLaunch:
         key = self._variant()
         clip, sw = key[0], key[1:]
         self._flush_counts()
-        dev = active[0][0].device
+        dev = _param_device([p for p, _ in active], self._NAME)
         rows, row_idx, row_of = [], {}, []
         for p, gi in active:
-            if not p.is_cuda:
-                raise lib.BmnasError(f'{self._NAME} needs parameters on the GPU (HIP kernel, no CPU path)')
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise lib.BmnasError(f'{self._NAME}: parameter must be contiguous fp32 on {dev}')
             rk = (gi, self._row_count(p, sw))
             if rk not in row_idx:
                 row_idx[rk] = len(rows)
@@ -186,9 +264,8 @@ class _OneLaunch:
             row_of.append(row_idx[rk])
         fields, tail = self._plan_fields(sw)
         lay = staging_layout(len(rows), len(active), slots, clip, tail, extra)
-        pin = torch.zeros(lay.nbytes, dtype=torch.uint8).pin_memory()
-        host = pin.numpy()
-        devbuf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=dev)
+        stage = _Staging(lay.nbytes, dev)
+        host, devbuf = stage.host, stage.dev
         tabs = [host[o:o + lay.tab_bytes].view(_DESC) for o in lay.tab_at]
         for tab in tabs:
             tab['numel'] = [p.numel() for p, _ in active]
@@ -199,10 +276,9 @@ class _OneLaunch:
                           groups=[gi for gi, _ in rows], count=[c for _, c in rows],
                           # hyp_all: what a replay carries by value — every slot's scalar rows and, behind them, a rider's
                           # `extra` bytes (an AveragedModel's rows; none: the optimizer's rows alone, as ever)
-                          pin=pin, hyp=hyps[0], hyps=hyps, hyp_all=host[:lay.extra_at + extra], tabs=tabs,
+                          stage=stage, hyp=hyps[0], hyps=hyps, hyp_all=host[:lay.extra_at + extra], tabs=tabs,
                           extra=host[lay.extra_at:lay.extra_at + extra],
-                          dev_extra=devbuf[lay.extra_at:lay.extra_at + extra],
-                          dev=devbuf, dev_hyp=devbuf[:lay.hyp_bytes],
+                          dev_extra=devbuf[lay.extra_at:lay.extra_at + extra], dev_hyp=devbuf[:lay.hyp_bytes],
                           dev_hyps=[devbuf[o:o + lay.hyp_slot] for o in lay.rows_at],
                           dev_tabs=[devbuf[o:o + lay.tab_bytes] for o in lay.tab_at],
                           chunks=chunks, n_chunks=n_chunks, slots=slots, cap_slot=0, clip=clip, key=key, **fields)
@@ -259,7 +335,7 @@ class _OneLaunch:
     def _launch(self, slot=0):
         pl = self._plan
         if not pl.get('poke') and slot == 0:
-            pl['dev'].copy_(pl['pin'], non_blocking=True)       # (one copy node serves every slot of the graph)
+            pl['stage'].copy()               # (captured: one copy node serves every slot of the graph)
         args, clip_args = (pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_hyps'][slot]), ()
         if pl['clip']:
             lib.grad_sqnorm_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['partials'][slot])
@@ -281,10 +357,10 @@ class _OneLaunch:
         tab['grad'] = [gr.data_ptr() for gr in grads]
 
     def wait_staging(self):
-        """Block until the last launch has consumed the pinned staging buffer (the host may run
-        ahead of the GPU; rewriting the buffer earlier would change a step still in flight)."""
-        if self._plan is not None and self._plan.get('event') is not None:
-            self._plan['event'].synchronize()
+        """Block until the last launch has consumed the current plan's pinned staging buffer (`_Staging.wait`)."""
+        stage = None if self._plan is None else self._plan.get('stage')
+        if stage is not None:
+            stage.wait()
 
     def mark_launched(self, force=False):
         """Record, on the current stream, that everything queued so far (a step() or a graph
@@ -293,9 +369,7 @@ class _OneLaunch:
         pl = self._plan
         if pl.get('poke') and not force:
             return
-        if pl.get('event') is None:
-            pl['event'] = torch.cuda.Event()
-        pl['event'].record()
+        pl['stage'].mark()
 
     # ------------------------------------------------------------------ torch.optim API
     @torch.no_grad()
@@ -397,7 +471,7 @@ class _OneLaunch:
             return None
         if pl.get('tab_dirty'):
             self.wait_staging()
-            pl['dev'].copy_(pl['pin'], non_blocking=True)
+            pl['stage'].copy()
             self.mark_launched(force=True)       # the pinned buffer must not be rewritten before this copy has read it
             self.wait_staging()                  # (rare: once after a capture / load_state_dict)
             pl['tab_dirty'] = False
@@ -764,10 +838,9 @@ class UnrolledStep:
         combine(da, gp, gn)   da -= eta (gp - gn) / (2 R)                         gp / gn = grad_alpha L_train(w+ / w-)
 
     It owns the plan: the descriptor tables of the weights and of alpha, the chunk lists, the norm partials, ONE
-    persistent backup tensor per weight tensor (+4 B per parameter, where DARTS copies the whole model) and one pinned
-    staging buffer with its device copy.  Pointers and scalars go up in one pinned async copy per call — skipped when the
-    bytes are those the device already holds —, guarded by an event; R, the norm and eta reach the kernels through device
-    memory: no call synchronises with the host.  Eager only.
+    persistent backup tensor per weight tensor (+4 B per parameter, where DARTS copies the whole model) and one staging
+    buffer.  Pointers and scalars go up with one `_Staging.upload()` per call (`uploads` counts those that copied); R, the
+    norm and eta reach the kernels through device memory: no call synchronises with the host.  Eager only.
 
     The weight tensors are the network optimizer's own (`for g in param_groups for p in g['params']`); `grads`, `v` are
     lists in that order.  A tensor whose gradient is None in the virtual pass is left out of every launch of that step.
@@ -824,25 +897,19 @@ class UnrolledStep:
 
     @staticmethod
     def _check_like(t, p, what):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != p.device or t.numel() != p.numel():
-            raise lib.BmnasError(f'bmnas.optim.UnrolledStep: {what} must be contiguous fp32 on the parameter device, of '
-                                 "the parameter's size")
+        _check_like(t, p, 'bmnas.optim.UnrolledStep', what)
 
     def _zeros(self, p):
         if p not in self._zero:
             self._zero[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         return self._zero[p]
 
-    def _build(self, active, key):
-        """active: [(p, group index, has momentum_buffer)] of this step.  One pinned buffer and its device copy:
-        scalar rows | r, eta | weight table | alpha table."""
-        dev = active[0][0].device
+    def _build(self, active, key, dev):
+        """active: [(p, group index, has momentum_buffer)] of this step, all on `dev`.  One staging buffer: a clipped
+        one-slot `staging_layout` — scalar rows | r, eta (where max_grad_norm goes) | weight table — and the alpha table
+        behind it."""
         rows, row_idx, row_of = [], {}, []
         for p, gi, has in active:
-            if not p.is_cuda:
-                raise lib.BmnasError('bmnas.optim.UnrolledStep needs parameters on the GPU (HIP kernel, no CPU path)')
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise lib.BmnasError(f'bmnas.optim.UnrolledStep: parameter must be contiguous fp32 on {dev}')
             if p not in self._bak:
                 self._bak[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
             if (gi, has) not in row_idx:
@@ -852,14 +919,11 @@ class UnrolledStep:
         for a in self.arch:
             if a.device != dev or a.dtype != torch.float32:
                 raise lib.BmnasError(f'bmnas.optim.UnrolledStep: architecture tensors must be fp32 on {dev}')
-        row_bytes = len(rows) * 32
-        hyp_bytes = (row_bytes + 16 + 63) // 64 * 64
-        wtab_bytes, atab_bytes = len(active) * _DESC.itemsize, len(self.arch) * _DESC.itemsize
-        nbytes = hyp_bytes + wtab_bytes + atab_bytes
-        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-        host = pin.numpy()
-        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        wtab = host[hyp_bytes:hyp_bytes + wtab_bytes].view(_DESC)
+        lay = staging_layout(len(rows), len(active), clip=True)
+        stage = _Staging(lay.nbytes + len(self.arch) * _DESC.itemsize, dev)
+        host, devbuf = stage.host, stage.dev
+        (rows_at,), (scal_at,), (wtab_at,) = lay.rows_at, lay.clip_at, lay.tab_at
+        wtab = host[wtab_at:lay.nbytes].view(_DESC)
         wtab['param'] = [p.data_ptr() for p, _, _ in active]
         wtab['exp_avg_sq'] = [self._bak[p].data_ptr() for p, _, _ in active]
         wtab['numel'] = [p.numel() for p, _, _ in active]
@@ -867,33 +931,15 @@ class UnrolledStep:
         parts = lib.grad_norm_parts()
         chunks, n_chunks = _chunk_list([p.numel() for p, _, _ in active], dev)
         self._plan = dict(
-            key=key, active=active, rows=rows, pin=pin, host=host, dev=devbuf, sent=None, event=None,
-            hyp=host[:row_bytes].view(np.float32).reshape(len(rows), 8),
-            scal=host[row_bytes:row_bytes + 16].view(np.float32),
-            wtab=wtab, atab=host[hyp_bytes + wtab_bytes:].view(_DESC),
-            dev_hyp=devbuf[:hyp_bytes], dev_r=devbuf[row_bytes:row_bytes + 4], dev_eta=devbuf[row_bytes + 4:row_bytes + 8],
-            dev_wtab=devbuf[hyp_bytes:hyp_bytes + wtab_bytes], dev_atab=devbuf[hyp_bytes + wtab_bytes:],
+            key=key, active=active, rows=rows, stage=stage,
+            hyp=host[rows_at:rows_at + lay.row_bytes].view(np.float32).reshape(len(rows), 8),
+            scal=host[scal_at:scal_at + 16].view(np.float32),
+            wtab=wtab, atab=host[lay.nbytes:].view(_DESC),
+            dev_hyp=devbuf[:lay.hyp_bytes], dev_r=devbuf[scal_at:scal_at + 4], dev_eta=devbuf[scal_at + 4:scal_at + 8],
+            dev_wtab=devbuf[wtab_at:lay.nbytes], dev_atab=devbuf[lay.nbytes:],
             chunks=chunks, n_chunks=n_chunks, n_parts=min(n_chunks, parts),
             partials=torch.empty(parts, dtype=torch.float32, device=dev), R=torch.zeros(1, dtype=torch.float32, device=dev),
             flags=lib.UNROLL_MOMENTUM if any(has for _, _, has in active) else 0, achunks={})
-
-    def _wait(self):
-        """Block until the last upload has read the pinned buffer (the host may run ahead of the GPU)."""
-        ev = self._plan['event']
-        if ev is not None:
-            ev.synchronize()
-
-    def _upload(self):
-        """One pinned async copy of everything staged — unless the device already holds exactly these bytes."""
-        pl = self._plan
-        if pl['sent'] is not None and np.array_equal(pl['sent'], pl['host']):
-            return
-        pl['dev'].copy_(pl['pin'], non_blocking=True)
-        if pl['event'] is None:
-            pl['event'] = torch.cuda.Event()
-        pl['event'].record()
-        pl['sent'] = pl['host'].copy()
-        self.uploads += 1
 
     # ------------------------------------------------------------------ the four calls
     @torch.no_grad()
@@ -913,14 +959,13 @@ class UnrolledStep:
                 gs.append(gr)
         if not active:
             raise lib.BmnasError('bmnas.optim.UnrolledStep: no weight tensor has a gradient')
-        if not all(p.is_cuda for p, _, _ in active):
-            raise lib.BmnasError('bmnas.optim.UnrolledStep needs parameters on the GPU (HIP kernel, no CPU path)')
+        dev = _param_device([p for p, _, _ in active], 'bmnas.optim.UnrolledStep')   # (in front of _eager: it needs a GPU)
         self._eager('virtual_step')
         key = tuple((id(p), gi, has) for p, gi, has in active)
         if self._plan is None or self._plan['key'] != key:
-            self._build(active, key)
+            self._build(active, key, dev)
         pl = self._plan
-        self._wait()
+        pl['stage'].wait()
         bufs = []
         for p, gi, has in active:
             buf = self.optimizer.state[p]['momentum_buffer'] if has else None
@@ -934,7 +979,7 @@ class UnrolledStep:
         pl['wtab']['param'] = [p.data_ptr() for p, _, _ in active]
         pl['wtab']['grad'] = [gr.data_ptr() for gr in gs]
         pl['wtab']['exp_avg'] = bufs
-        self._upload()
+        self.uploads += pl['stage'].upload()
         lib.unroll_virtual_step(pl['dev_wtab'], pl['chunks'], pl['n_chunks'], pl['dev_hyp'], pl['flags'])
         self._normed = False
         self._stepped = True
@@ -959,9 +1004,9 @@ class UnrolledStep:
                 t = self._zeros(p)               # no validation gradient: the tensor is not perturbed
             self._check_like(t, p, 'vectors')
             vs.append(t)
-        self._wait()
+        pl['stage'].wait()
         pl['wtab']['grad'] = [t.data_ptr() for t in vs]
-        self._upload()
+        self.uploads += pl['stage'].upload()
         if not self._normed:
             lib.grad_sqnorm_multi(pl['dev_wtab'], pl['chunks'], pl['n_chunks'], pl['partials'])
             self._normed = True
@@ -1008,9 +1053,9 @@ class UnrolledStep:
             return out
         ck = tuple(idx)
         if ck not in pl['achunks']:
-            pl['achunks'][ck] = _chunk_list([self.arch[i].numel() for i in idx], pl['dev'].device)
+            pl['achunks'][ck] = _chunk_list([self.arch[i].numel() for i in idx], pl['stage'].dev.device)
         chunks, n = pl['achunks'][ck]
-        self._wait()
+        pl['stage'].wait()
         tab = pl['atab']
         tab[:] = np.zeros((), dtype=_DESC)
         m = len(idx)
@@ -1018,7 +1063,7 @@ class UnrolledStep:
         tab['grad'][:m] = [c[1].data_ptr() for c in cols]
         tab['exp_avg'][:m] = [c[2].data_ptr() for c in cols]
         tab['numel'][:m] = [c[0].numel() for c in cols]
-        self._upload()
+        self.uploads += pl['stage'].upload()
         lib.unroll_combine(pl['dev_atab'], chunks, n, pl['dev_eta'], pl['R'])
         return out
 
@@ -1059,9 +1104,8 @@ class GradAccumulator:
     gets `p.grad = None`.  The optimizer and the clipping norm downstream see an ordinary `.grad`: every Adam and SGD
     variant and `max_grad_norm` (the norm of the COMBINED gradient) work unchanged.
 
-    Eager: descriptors, part pointers and the chunk list go up in one pinned async copy guarded by an event — skipped
-    when the bytes are those the device already holds.  The weights travel by value in the launch.  combine()
-    synchronises nothing.
+    Eager: descriptors, part pointers and the chunk list go up with one `_Staging.upload()` (`uploads` counts those that
+    copied).  The weights travel by value in the launch.  combine() synchronises nothing.
     Captured (bmnas.graph.GraphedTrainStep(accumulate=m)): `capture_safe(m)` before the capture, `captured_plan()` after
     it, `abandon_capture()` when it failed.  Inside the capture combine() issues the launch only; the tables — the
     addresses of the graph's static `autograd.grad` outputs — are uploaded by captured_plan(), eagerly, before the first
@@ -1112,10 +1156,7 @@ class GradAccumulator:
         for g, p in zip(grads, ts):
             if g is None:
                 continue
-            if (not torch.is_tensor(g) or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device
-                    or g.numel() != p.numel()):
-                raise lib.BmnasError('bmnas.optim.GradAccumulator.add: a part must be contiguous fp32 on the parameter '
-                                     "device, of the parameter's size")
+            _check_like(g, p, 'bmnas.optim.GradAccumulator.add', 'a part')
             if g.untyped_storage().data_ptr() in self._acc_storage:
                 raise lib.BmnasError('bmnas.optim.GradAccumulator.add: a part aliases an accumulation tensor (a '
                                      '`.grad` that combine() set?); the launch reads every part while it writes there')
@@ -1123,65 +1164,39 @@ class GradAccumulator:
 
     # ------------------------------------------------------------------ plan
     def _build(self, ts, m):
-        """A plan with room for every tensor and m parts each: ONE pinned buffer and its device copy,
-        descriptor table | part pointers (tensor-major) | chunk list.  Allocates the accumulation tensors."""
+        """A plan with room for every tensor and m parts each: ONE staging buffer — a `staging_layout` without scalar rows,
+        descriptor table | part pointers (tensor-major, the table's tail) — and the chunk list behind it.  Allocates the
+        accumulation tensors."""
         if not ts:
             raise lib.BmnasError('bmnas.optim.GradAccumulator: the optimizer holds no tensors')
-        dev = ts[0].device
+        dev = _param_device(ts, 'bmnas.optim.GradAccumulator')
         for p in ts:
-            if not p.is_cuda:
-                raise lib.BmnasError('bmnas.optim.GradAccumulator needs parameters on the GPU (HIP kernel, no CPU path)')
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise lib.BmnasError(f'bmnas.optim.GradAccumulator: parameter must be contiguous fp32 on {dev}')
             if p not in self._acc:
                 self._acc[p] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 self._acc_storage.add(self._acc[p].untyped_storage().data_ptr())
-        E = lib.adam_chunk_elems()
-        tab_bytes = len(ts) * _DESC.itemsize
-        chunks_at = (tab_bytes + len(ts) * m * 8 + 15) // 16 * 16
-        nbytes = chunks_at + max(1, sum((p.numel() + E - 1) // E for p in ts)) * 8
-        pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-        devbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        return dict(ids=tuple(id(p) for p in ts), m=m, pin=pin, host=pin.numpy(), dev=devbuf, tab_bytes=tab_bytes,
-                    chunks_at=chunks_at, dev_tab=devbuf[:tab_bytes], dev_parts=devbuf[tab_bytes:chunks_at],
-                    dev_chunks=devbuf[chunks_at:], n_chunks=0, sent=None, event=None)
+        lay = staging_layout(0, len(ts), tail_ptrs_per_tensor=m)
+        parts_at, chunks_at = lay.tail_at[0], _chunks_at(lay)
+        stage = _Staging(chunks_at + max(1, len(_chunk_pairs([p.numel() for p in ts]))) * 8, dev)
+        return dict(ids=tuple(id(p) for p in ts), m=m, stage=stage, parts_at=parts_at, chunks_at=chunks_at,
+                    dev_tab=stage.dev[:parts_at], dev_parts=stage.dev[parts_at:chunks_at],
+                    dev_chunks=stage.dev[chunks_at:], n_chunks=0)
 
     def _fill(self, pl, ts, active, parts):
         """Write the descriptors, part pointers and chunk list of this step's tensors (`active`: indices into ts)."""
-        m, host = len(parts), pl['host']
+        m, host = len(parts), pl['stage'].host
         host[:] = 0
         tab = host[:len(active) * _DESC.itemsize].view(_DESC)
         tab['grad'] = [self._acc[ts[i]].data_ptr() for i in active]
         tab['numel'] = [ts[i].numel() for i in active]
-        ptrs = host[pl['tab_bytes']:pl['tab_bytes'] + len(active) * m * 8].view('<u8').reshape(len(active), m)
+        ptrs = host[pl['parts_at']:pl['parts_at'] + len(active) * m * 8].view('<u8').reshape(len(active), m)
         for j, (gs, _) in enumerate(parts):
             ptrs[:, j] = [0 if gs[i] is None else gs[i].data_ptr() for i in active]
         key = tuple(active)
         if key not in self._chunk_cache:
-            E = lib.adam_chunk_elems()
-            self._chunk_cache[key] = np.array(
-                [(a, c) for a, i in enumerate(active) for c in range((ts[i].numel() + E - 1) // E)],
-                dtype=np.int32).reshape(-1)
+            self._chunk_cache[key] = _chunk_pairs([ts[i].numel() for i in active])
         chunks = self._chunk_cache[key]
-        host[pl['chunks_at']:pl['chunks_at'] + chunks.nbytes].view(np.int32)[:] = chunks
-        pl['n_chunks'] = len(chunks) // 2
-
-    @staticmethod
-    def _wait(pl):
-        """Block until the last upload has read the plan's pinned buffer (the host may run ahead of the GPU)."""
-        if pl['event'] is not None:
-            pl['event'].synchronize()
-
-    def _upload(self, pl):
-        """One pinned async copy of everything staged — unless the device already holds exactly these bytes."""
-        if pl['sent'] is not None and np.array_equal(pl['sent'], pl['host']):
-            return
-        pl['dev'].copy_(pl['pin'], non_blocking=True)
-        if pl['event'] is None:
-            pl['event'] = torch.cuda.Event()
-        pl['event'].record()
-        pl['sent'] = pl['host'].copy()
-        self.uploads += 1
+        host[pl['chunks_at']:pl['chunks_at'] + chunks.nbytes].view(np.int32)[:] = chunks.reshape(-1)
+        pl['n_chunks'] = len(chunks)
 
     # ------------------------------------------------------------------ the step
     @torch.no_grad()
@@ -1205,14 +1220,14 @@ class GradAccumulator:
             pl = self._eager
             if pl is None or pl['ids'] != tuple(id(p) for p in ts):
                 pl = self._eager = self._build(ts, lib.accum_max())
-            self._wait(pl)
+            pl['stage'].wait()
         parts, self._parts = self._parts, []
         if active:
             self._fill(pl, ts, active, parts)
             if capturing:
                 pl['parts'] = parts              # the graph's static autograd.grad outputs: alive as long as the plan
             else:
-                self._upload(pl)
+                self.uploads += pl['stage'].upload()
             lib.grad_combine_multi(pl['dev_tab'], pl['dev_chunks'], pl['n_chunks'], pl['dev_parts'], m,
                                    [w for _, w in parts])
             self.launches += 1
@@ -1250,8 +1265,8 @@ class GradAccumulator:
         if pl.get('parts') is None:
             raise lib.BmnasError('bmnas.optim.GradAccumulator: the capture holds no combine()')
         self._capturing = None
-        self._upload(pl)
-        self._wait(pl)
+        self.uploads += pl['stage'].upload()
+        pl['stage'].wait()
         pl['weights'] = [w for _, w in pl['parts']]
         self.captures += 1
         return pl
@@ -1386,42 +1401,35 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
         """The plan of `slots` launches over `trio`: per slot a descriptor table (averaged tensors first, then RAW ones),
         one chunk list, and the rows — slot s's row at index s and, when both kinds are present, ONE shared RAW row
         behind them.  rows / dev_rows: where the rows live when they ride in an optimizer's staging buffer (host bytes
-        and their device copy); None: in this plan's own buffer, in front of the tables.  The chunk list lies behind the
-        tables in the same pinned buffer: building a plan and uploading it copies nothing from pageable memory, so even
-        the first update synchronises nothing."""
+        and their device copy); None: in this plan's own buffer, where `staging_layout` puts a rider's rows (in front of
+        the tables).  The chunk list lies behind the tables in the same staging buffer: building a plan and uploading it
+        copies nothing from pageable memory, so even the first update synchronises nothing."""
         avg = [(a, p) for a, p, k in trio if k == 'avg' and a.numel()]
         raw = [(a, p) for a, p, k in trio if k == 'raw' and a.numel()]
         order = avg + raw
-        dev = order[0][0].device
         n_rows = slots + (1 if avg and raw else 0)
         own = rows is None
-        row_bytes = (n_rows * 32 + 63) // 64 * 64 if own else 0
-        tab_bytes = len(order) * _DESC.itemsize
         numels = [a.numel() for a, _ in avg] + [a.numel() * a.element_size() // 4 for a, _ in raw]
-        E = lib.adam_chunk_elems()
-        chunk_list = np.array([(i, c) for i, n in enumerate(numels) for c in range((n + E - 1) // E)],
-                              dtype=np.int32).reshape(-1, 2)
-        n_chunks = len(chunk_list)
-        chunks_at = (row_bytes + slots * tab_bytes + 15) // 16 * 16
-        pin = torch.zeros(chunks_at + n_chunks * 8, dtype=torch.uint8).pin_memory()
-        host = pin.numpy()
-        devbuf = torch.zeros(chunks_at + n_chunks * 8, dtype=torch.uint8, device=dev)
-        host[chunks_at:].view(np.int32)[:] = chunk_list.reshape(-1)
+        lay = staging_layout(0, len(order), slots=slots, extra_bytes=n_rows * 32 if own else 0)
+        pairs, chunks_at = _chunk_pairs(numels), _chunks_at(lay)
+        stage = _Staging(chunks_at + pairs.nbytes, order[0][0].device)
+        host, devbuf = stage.host, stage.dev
+        host[chunks_at:].view(np.int32)[:] = pairs.reshape(-1)
         if own:
-            rows, dev_rows = host[:n_rows * 32], devbuf[:n_rows * 32]
+            rows_at = slice(lay.extra_at, lay.extra_at + n_rows * 32)
+            rows, dev_rows = host[rows_at], devbuf[rows_at]
         if rows.nbytes != n_rows * 32:
             raise lib.BmnasError(f'bmnas.optim.AveragedModel: {n_rows} rows need {n_rows * 32} bytes, got {rows.nbytes}')
         rows = rows.view(_AVG_ROW)
-        tabs = [host[row_bytes + s * tab_bytes:row_bytes + (s + 1) * tab_bytes].view(_DESC) for s in range(slots)]
+        tabs = [host[o:o + lay.tab_bytes].view(_DESC) for o in lay.tab_at]
         for s, tab in enumerate(tabs):
             tab['numel'] = numels
             tab['hyp_row'] = [s] * len(avg) + [slots if avg else s] * len(raw)
         if avg and raw:
             rows[slots] = (0.0, 0.0, lib.AVG_RAW, 0, 0, 0)    # (its count is never read: tensor 0 is an averaged one)
-        return dict(order=order, numels=numels, raw_only=not avg, slots=slots, own=own, pin=pin, host=host, dev=devbuf,
+        return dict(order=order, numels=numels, raw_only=not avg, slots=slots, own=own, stage=stage,
                     rows=rows, dev_rows=dev_rows, tabs=tabs, chunks=devbuf[chunks_at:],
-                    dev_tabs=[devbuf[row_bytes + s * tab_bytes:row_bytes + (s + 1) * tab_bytes] for s in range(slots)],
-                    n_chunks=n_chunks, sent=None, event=None, cap_slot=0)
+                    dev_tabs=[devbuf[o:o + lay.tab_bytes] for o in lay.tab_at], n_chunks=len(pairs), cap_slot=0)
 
     @staticmethod
     def _write_ptrs(pl):
@@ -1431,23 +1439,6 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
 
     def _write_row(self, pl, slot, n):
         pl['rows'][slot] = avg_row(n, self.decay, raw=pl['raw_only'])
-
-    @staticmethod
-    def _wait(pl):
-        """Block until the last upload has read the plan's pinned buffer (the host may run ahead of the GPU)."""
-        if pl['event'] is not None:
-            pl['event'].synchronize()
-
-    @staticmethod
-    def _upload(pl):
-        """One pinned async copy of everything staged — unless the device already holds exactly these bytes."""
-        if pl['sent'] is not None and np.array_equal(pl['sent'], pl['host']):
-            return
-        pl['dev'].copy_(pl['pin'], non_blocking=True)
-        if pl['event'] is None:
-            pl['event'] = torch.cuda.Event()
-        pl['event'].record()
-        pl['sent'] = pl['host'].copy()
 
     def _launch(self, pl, slot=0):
         lib.avg_multi(pl['dev_tabs'][slot], pl['chunks'], pl['n_chunks'], pl['dev_rows'], self.n_averaged)
@@ -1461,11 +1452,11 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
         if pl is None or len(pl['order']) != len(order) or any(
                 m != a.numel() * a.element_size() // 4 for m, (a, _) in zip(pl['numels'], order)):
             pl = self._eager[key] = self._build(trio)
-        self._wait(pl)
+        pl['stage'].wait()
         pl['order'] = order                          # (the tensors may have been re-pointed: addresses are re-read)
         self._write_ptrs(pl)
         self._write_row(pl, 0, n)
-        self._upload(pl)
+        pl['stage'].upload()
         self._launch(pl)
 
     def _copy_frozen(self, model, n):
@@ -1529,8 +1520,8 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
         trio = self._main(model)
         pl = self._build(trio, slots, rows, dev_rows)
         self._write_ptrs(pl)
-        self._upload(pl)
-        self._wait(pl)
+        pl['stage'].upload()
+        pl['stage'].wait()
         pl['model'] = model
         self._capturing = pl
 

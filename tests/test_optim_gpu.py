@@ -304,3 +304,20 @@ def test_overlapped_bucket_reduction_gives_the_same_gradients():
                 continue                     # mathematically zero in front of a train-mode BatchNorm: pure round-off
             # (the arch gradients are small differences of sharded atomic sums: 1e-4-level run-to-run)
             assert_close_scaled(f'{cname}:{k}', over, plain, rel=1e-3 if k.startswith('arch.') else 2e-5, floor=1e-9)
+
+
+def test_staging_uploads_once_per_change_and_guards_the_pinned_bytes():
+    """bmnas.optim._Staging, which every plan of bmnas.optim stages through (no kernel involved): an upload of bytes the
+    device already holds is skipped, a changed byte is not, and after wait() the device copy holds the host bytes."""
+    import numpy as np
+    from bmnas.optim import _Staging
+    _Staging(64, dev()).wait()                          # never uploaded: no event, returns at once
+    st = _Staging(64, dev())
+    assert st.host.shape == (64,) and st.host.dtype == np.uint8 and st.pin.is_pinned() and st.dev.device == dev()
+    st.host[:] = np.arange(64, dtype=np.uint8)
+    assert st.upload() is True and st.upload() is False
+    st.host[17] ^= 0xff
+    assert st.upload() is True
+    st.wait()
+    assert np.array_equal(st.dev.cpu().numpy(), st.host) and st.host[17] == 17 ^ 0xff
+    assert st.upload() is False

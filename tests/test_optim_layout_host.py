@@ -44,3 +44,33 @@ def test_chunk_list(monkeypatch):
     assert n == 1 and chunks.tolist() == [[1, 0]]
     chunks, n = optim._chunk_list((), device='cpu')
     assert n == 0 and chunks.shape == (0, 2)
+
+
+def test_chunk_pairs_is_what_chunk_list_returns(monkeypatch):
+    import numpy as np
+    from bmnas import lib, optim
+    monkeypatch.setattr(lib, 'adam_chunk_elems', lambda: 1024)
+    for numels, want in (((), []), ((0, 1024, 0), [[1, 0]]), ((1, 1025), [[0, 0], [1, 0], [1, 1]])):
+        pairs = optim._chunk_pairs(numels)
+        assert pairs.dtype == np.int32 and pairs.shape == (len(want), 2) and pairs.tolist() == want
+        chunks, n = optim._chunk_list(numels, 'cpu')
+        assert n == len(pairs) and chunks.shape == pairs.shape and chunks.tolist() == pairs.tolist()
+
+
+def test_the_other_plans_are_cases_of_the_staging_layout():
+    """UnrolledStep, GradAccumulator and AveragedModel take their offsets from staging_layout; the numbers are what their
+    own formulas gave before they did (they are what the kernels of csrc/unroll.hip, accum.hip and average.hip read)."""
+    from bmnas.optim import _chunks_at, staging_layout
+    # UnrolledStep: 2 rows, 3 weight tensors, 2 alpha tensors -> rows | r, eta | weight table | alpha table
+    lay = staging_layout(2, 3, clip=True)
+    assert (lay.rows_at, lay.clip_at, lay.tab_at, lay.hyp_bytes) == ([0], [64], [128], 128)
+    assert lay.nbytes == 272 and lay.nbytes + 2 * 48 == 368              # the alpha table starts at 272, the buffer ends at 368
+    # GradAccumulator: 3 tensors, m = 3 -> table | part pointers | chunk list
+    lay = staging_layout(0, 3, tail_ptrs_per_tensor=3)
+    assert (lay.tab_at, lay.tail_at, lay.nbytes) == ([0], [144], 216) and _chunks_at(lay) == 224
+    # AveragedModel with rows of its own: 2 slots and both kinds (3 rows), 3 tensors -> rows | tables | chunk list
+    lay = staging_layout(0, 3, slots=2, extra_bytes=3 * 32)
+    assert (lay.extra_at, lay.tab_at, lay.tab_bytes) == (0, [128, 272], 144) and _chunks_at(lay) == 416
+    # ... and with its rows riding in an optimizer's buffer
+    lay = staging_layout(0, 3, slots=2, extra_bytes=0)
+    assert (lay.tab_at, lay.tab_bytes) == ([0, 144], 144) and _chunks_at(lay) == 288
