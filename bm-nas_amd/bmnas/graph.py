@@ -592,22 +592,37 @@ class GraphedForward:
         fwd = GraphedForward.try_build(model, criterion, inputs, labels)
         loss, output = fwd(inputs, labels)            # static tensors, overwritten by the next call"""
 
-    def __init__(self, model, criterion, inputs, labels, warmup=2):
+    def __init__(self, model, criterion, inputs, labels, warmup=2, stats=None):
+        """stats: a bmnas.metrics.PhaseStats — the captured function then ends in `stats.update(loss, out, labels)`, so
+        a replay tallies its own batch (one more node, no host call).  `self.stats` tells the caller whether it does:
+        None when there is no stats object, or when its update of these tensors would not be the one native launch
+        (the caller then tallies behind the replay, as without it)."""
         self.training = model.training
         self.inputs = [x.detach().clone() for x in inputs]
         self.labels = labels.detach().clone()
         self._batch_in = _BatchIn(self.inputs, self.labels)
+        self.stats = stats
 
         def fn():
             with torch.no_grad():
                 out = model(self.inputs)
                 if isinstance(out, tuple):
                     out = out[-1]
-                return criterion(out, self.labels), out
+                loss = criterion(out, self.labels)
+                if self.stats is not None:
+                    if self.stats.native_ok(loss, out, self.labels):
+                        self.stats.update(loss, out, self.labels)
+                    else:
+                        self.stats = None            # (decided by the first warm-up pass: every later one agrees)
+                return loss, out
 
         # warm-up passes must not change training: their BatchNorm updates are undone (eval mode updates nothing:
         # no snapshot, no restore)
         state = {k: v.clone() for k, v in model.state_dict().items()} if model.training else None
+        # ... nor the phase's tally: the warm-up, rehearsal and capture executions leave the accumulator as they found it
+        # (not allocated yet: the first pass allocates it, and it is left empty)
+        tally = stats.acc.clone() if stats is not None and stats.acc is not None else None
+        counted = (stats.launches, stats.fallbacks) if stats is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         try:
@@ -631,9 +646,17 @@ class GraphedForward:
             torch.cuda.synchronize()
             if state is not None:
                 model.load_state_dict(state)
+            if stats is not None:
+                if stats.acc is not None:
+                    if tally is not None and tally.shape == stats.acc.shape:
+                        stats.acc.copy_(tally)
+                    else:
+                        stats.acc.zero_()
+                stats.launches, stats.fallbacks = counted     # (launches of a build are no batches of the phase)
+                stats.touch()
 
     @staticmethod
-    def try_build(model, criterion, inputs, labels, logger=None):
+    def try_build(model, criterion, inputs, labels, logger=None, stats=None):
         """-> a GraphedForward, or False (inputs that are not a flat list of device tensors, a module that
         synchronises with the host, a capture error): the caller keeps the eager forward.  No collective is
         involved, so under data parallelism every rank decides for itself."""
@@ -641,7 +664,7 @@ class GraphedForward:
                 and torch.is_tensor(labels) and labels.is_cuda):
             return False
         try:
-            return GraphedForward(model, criterion, inputs, labels)
+            return GraphedForward(model, criterion, inputs, labels, stats=stats)
         except Exception as e:                       # noqa: BLE001 — capture errors are of many types
             torch.cuda.synchronize()
             from . import functions
@@ -660,4 +683,6 @@ class GraphedForward:
 
     def __call__(self, inputs, labels):
         self._batch_in(inputs, labels)
+        if self.stats is not None:
+            self.stats.touch()                       # (the replay tallies: a host copy of the words is stale)
         return self._g.replay()

@@ -290,6 +290,9 @@ SIGNATURES = {
     'bmnas_avg_multi': ([_P, _P, _I, _P, _P, _P], _I),
     'bmnas_accum_max': ([], _I),
     'bmnas_grad_combine_multi': ([_P, _P, _I, _P, _I, C.POINTER(C.c_float), _P], _I),
+    'bmnas_phase_stats_words': ([_I], _I),
+    'bmnas_phase_stats_acc': ([_P, _P, _P, _I, _I, _P, _P], _I),
+    'bmnas_phase_stats_f1': ([_P, _P, _P, C.c_float, _I, _I, _P, _P], _I),
     'bmnas_unroll_virtual_step': ([_P, _P, _I, _P, _I, _P], _I),
     'bmnas_unroll_perturb': ([_P, _P, _I, _P, _I, _P, C.c_float, _P, _P], _I),
     'bmnas_unroll_restore': ([_P, _P, _I, _P], _I),
@@ -1248,6 +1251,47 @@ def grad_combine_multi(table, chunks, n_chunks, parts, m, weights):
     arr = (C.c_float * max(len(ws), 1))(*ws)
     _check(load().bmnas_grad_combine_multi(table.data_ptr(), chunks.data_ptr(), n_chunks, parts.data_ptr(), m, arr,
                                            _stream()), 'grad_combine_multi')
+
+
+STATS_MAX_CLASSES = 128                      # BMNAS_STATS_MAX_CLASSES (include/bmnas_hip.h)
+
+
+def phase_stats_words(O):
+    """Length in 64-bit words of the phase-statistics accumulator of O classes: 4 + 3 O (bmnas.metrics has the layout)."""
+    words = load().bmnas_phase_stats_words(int(O))
+    _check(min(words, 0), 'phase_stats_words')
+    return words
+
+
+def _phase_stats_args(name, logits, second, second_dtype, second_shape, loss, acc):
+    n, O = logits.shape
+    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous()):
+        raise BmnasError(f'{name}: logits must be a contiguous fp32 device tensor (n, O)')
+    if not (second.is_cuda and second.dtype == second_dtype and second.is_contiguous()
+            and tuple(second.shape) == second_shape):
+        raise BmnasError(f'{name}: expected a contiguous {second_dtype} device tensor of shape {second_shape}, got '
+                         f'{second.dtype} {tuple(second.shape)}')
+    if loss is not None and not (loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+        raise BmnasError(f'{name}: loss must be a one-element fp32 device tensor or None')
+    if not (acc.is_cuda and acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() >= 4 + 3 * O):
+        raise BmnasError(f'{name}: acc must be a contiguous int64 device tensor of at least {4 + 3 * O} words')
+    return n, O
+
+
+def phase_stats_acc(logits, labels, loss, acc):
+    """One launch: tally the batch (logits (n, O) fp32, labels (n,) int64, loss a 0-dim fp32 device tensor or None) into
+    the int64 accumulator `acc` — loss sum, launch and sample counts, correct predictions by torch's argmax rule."""
+    n, O = _phase_stats_args('phase_stats_acc', logits, labels, torch.int64, (logits.shape[0],), loss, acc)
+    _check(load().bmnas_phase_stats_acc(logits.data_ptr(), labels.data_ptr(), _opt(loss), n, O, acc.data_ptr(),
+                                        _stream()), 'phase_stats_acc')
+
+
+def phase_stats_f1(logits, targets, loss, logit_threshold, acc):
+    """One launch: tally the batch (logits and targets (n, O) fp32) into `acc` — loss sum, launch and sample counts and the
+    per-class tp / fp / fn of (logit > logit_threshold) against (target > 0.5)."""
+    n, O = _phase_stats_args('phase_stats_f1', logits, targets, torch.float32, tuple(logits.shape), loss, acc)
+    _check(load().bmnas_phase_stats_f1(logits.data_ptr(), targets.data_ptr(), _opt(loss), float(logit_threshold), n, O,
+                                       acc.data_ptr(), _stream()), 'phase_stats_f1')
 
 
 UNROLL_MOMENTUM = 1                          # BMNAS_UNROLL_* (include/bmnas_hip.h)

@@ -223,6 +223,26 @@ def update_bn_option(args, status, world=None):
     return True
 
 
+def device_stats_option(args, meter):
+    """args.device_stats (optional, default False; the reference's argument sets have none): the trainer loop keeps its
+    phase statistics — loss sum, accuracy or F1 counts — in one device accumulator tallied by ONE launch per batch
+    (bmnas.metrics.PhaseStats; inside the replay where the batch is a captured gradient-free forward) instead of the
+    aten launches of `loss_sum += ...; meter.update(...)`.  -> the PhaseStats that stands in for `meter` (kept ON the
+    meter across run() / evaluate() calls: captured forwards hold its accumulator), or None — the option is absent or
+    false, or the meter is not one of the loop's own (PhaseStats.from_meter): the loop then does what it always did."""
+    if not getattr(args, 'device_stats', False):
+        return None
+    from bmnas.metrics import PhaseStats
+    fresh = PhaseStats.from_meter(meter)
+    if fresh is None:
+        return None
+    kept = meter.__dict__.get('_bmnas_phase_stats')
+    if kept is not None and (kept.kind, kept.f1_type, kept.threshold) == (fresh.kind, fresh.f1_type, fresh.threshold):
+        return kept
+    meter.__dict__['_bmnas_phase_stats'] = fresh
+    return fresh
+
+
 def make_averager(model, args, status):
     """-> (bmnas.optim.AveragedModel of `model`, its options), or (None, None) without the options.  use_buffers=True
     — averaged running statistics stand in for swa_utils.update_bn's cumulative pass — unless args.swa_update_bn asks

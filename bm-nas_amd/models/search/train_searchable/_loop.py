@@ -155,6 +155,25 @@ class F1Meter:
         return float(f1_score(y_true, y_pred, average=self.f1_type, zero_division=1))
 
 
+def _tally(dstats, counters, loss_sum, meter, loss, output, labels, rode=False):
+    """One batch into the phase statistics.  dstats None (args.device_stats absent or false, or a meter that is not the
+    loop's own): the two statements the loop always had — loss_sum and meter are updated in place.  Else ONE tally
+    through the bmnas.metrics.PhaseStats: `rode` — the replay that produced (loss, output) ended in the tally itself
+    (_ForwardGraphs.tallied), nothing is issued; otherwise one launch behind the replay / eager step that reads the
+    (static) loss and output tensors.  counters: run.stats / evaluate.stats."""
+    if dstats is None:
+        loss_sum += loss.detach().double() * labels.size(0)
+        meter.update(output.detach(), labels)
+        return
+    if rode:
+        counters['stat_in_replay'] += 1
+        return
+    before = dstats.launches, dstats.fallbacks
+    dstats.update(loss.detach(), output.detach(), labels)
+    counters['stat_launches'] += dstats.launches - before[0]
+    counters['stat_fallbacks'] += dstats.fallbacks - before[1]
+
+
 def fusion_params(model):
     n = sum(count_parameters(layer) for layer in model.reshape_layers)
     return n + count_parameters(model.fusion_net)
@@ -170,12 +189,14 @@ class _ForwardGraphs:
         self.on = GraphedTrainStep.enabled(args)
         self.graphs, self.attempts, self.logger = [], 0, logger
         self.replays = 0
+        self.tallied = False         # whether the LAST replay tallied its batch itself (a graph built with stats=)
 
     def __deepcopy__(self, memo):
         """A deep copy of the model (bmnas.optim.AveragedModel) starts without graphs: these read the ORIGINAL's
         parameters, and a captured graph cannot be copied."""
         new = _ForwardGraphs.__new__(_ForwardGraphs)
         new.on, new.graphs, new.attempts, new.logger, new.replays = self.on, [], 0, self.logger, 0
+        new.tallied = False
         return new
 
     @staticmethod
@@ -199,23 +220,32 @@ class _ForwardGraphs:
         fg.replays = 0
         return fg
 
-    def __call__(self, model, criterion, inputs, labels):
-        """-> (loss, output) from a replay, or None: run the pass eagerly."""
+    def __call__(self, model, criterion, inputs, labels, stats=None):
+        """-> (loss, output) from a replay, or None: run the pass eagerly.  stats (args.device_stats: a
+        bmnas.metrics.PhaseStats): the graphs are built with it and end in its tally — `self.tallied` says whether the
+        replay just taken did; a graph serves only the stats object it was built for (None: the graphs of always)."""
+        self.tallied = False
         if not self.on:
             return None
         for g in self.graphs:
-            if g.matches(model, inputs, labels):
+            if getattr(g, 'stats_for', None) is stats and g.matches(model, inputs, labels):
                 self.replays += 1
+                self.tallied = g.stats is not None
                 return g(inputs, labels)
         if self.attempts >= 3:
             return None
         self.attempts += 1
         from bmnas.graph import GraphedForward
-        g = GraphedForward.try_build(model, criterion, inputs, labels, self.logger)
+        if stats is None:
+            g = GraphedForward.try_build(model, criterion, inputs, labels, self.logger)
+        else:
+            g = GraphedForward.try_build(model, criterion, inputs, labels, self.logger, stats=stats)
         if not g:
             return None
+        g.stats_for = stats
         self.graphs.append(g)
         self.replays += 1
+        self.tallied = g.stats is not None
         return g(inputs, labels)
 
 
@@ -293,6 +323,14 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     wk_graph, wk_attempts = None, 0
     f_graphs = _ForwardGraphs.of(model, criterion, args, logger)
     stats = run.stats = dict(graph_replays=0, eager_steps=0, forward_replays=0, k_step_replays=0)
+    # args.device_stats: the phase statistics in one device accumulator, one launch per batch (bmnas.metrics.PhaseStats);
+    # None — the option absent, or a meter that is not the loop's own — and `tally` below is the two statements of always
+    from models.search._common import device_stats_option
+    dstats = device_stats_option(args, meter)
+    if dstats is not None:                   # (without it run.stats has the keys it always had: read them with .get)
+        stats.update(stat_launches=0,        # batches tallied by one eager launch behind their replay / eager step
+                     stat_in_replay=0,       # ... by the captured forward's own last node: no host call
+                     stat_fallbacks=0)       # ... by PhaseStats' torch restatement (tensors the launch does not take)
     # gradient accumulation (args.accum_steps = m > 1): the accumulate=m graph of the full groups and the accumulator of
     # the eager tails; absent or 1 none of this exists and nothing below changes
     wa_graph, wa_attempts, accumulator = None, 0, None
@@ -365,6 +403,8 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 averaged.module.eval()
             meter.reset(device)
             loss_sum = torch.zeros((), device=device, dtype=torch.float64)
+            if dstats is not None:
+                dstats.reset(device)
             seen = 0
             loader = dataloaders[phase]
             split = _world() > 1 and not _is_sharded(loader)
@@ -419,8 +459,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                             scheduler.update_optimizer(optimizer)
                         loss, output = w_graph(inputs, labels)
                         averaged_step(in_replay=w_graph.averaged is not None)
-                        loss_sum += loss.detach().double() * labels.size(0)
-                        meter.update(output.detach(), labels)
+                        _tally(dstats, stats, loss_sum, meter, loss, output, labels)
                         stats['graph_replays'] += 1
                         _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
                                  learn=True, how='graph')
@@ -428,16 +467,20 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 if not learn:
                     # the metric pass: no gradients, one replay (the step above — architect.step in the dev phase —
                     # has already happened: this forward sees the updated alphas, like the reference's)
+                    rode = False
                     if got is None:
-                        got = net_graphs(net, criterion, inputs, labels)
+                        if dstats is None:
+                            got = net_graphs(net, criterion, inputs, labels)
+                        else:
+                            got = net_graphs(net, criterion, inputs, labels, stats=dstats)
+                            rode = net_graphs.tallied
                         if use_avg:
                             stats['averaged_forwards'] += 1
                     else:
                         stats['merged_metric_replays'] = stats.get('merged_metric_replays', 0) + 1
                     if got is not None:
                         loss, output = got
-                        loss_sum += loss.detach().double() * labels.size(0)
-                        meter.update(output.detach(), labels)
+                        _tally(dstats, stats, loss_sum, meter, loss, output, labels, rode)
                         stats['forward_replays'] += 1
                         _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
                                  learn=False, how='graph')
@@ -456,8 +499,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                         loss.backward()
                         optimizer.step()
                         averaged_step()
-                loss_sum += loss.detach().double() * labels.size(0)
-                meter.update(output.detach(), labels)
+                _tally(dstats, stats, loss_sum, meter, loss, output, labels)
                 _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
                          learn=learn, how='eager')
 
@@ -483,8 +525,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                 stats['k_step_replays'] += 1
                 for (loss, output), (x_, y_), lr in zip(wk_graph.replay_staged(), batches, lrs):
                     averaged_step(in_replay=wk_graph.averaged is not None)
-                    loss_sum += loss.detach().double() * y_.size(0)
-                    meter.update(output.detach(), y_)
+                    _tally(dstats, stats, loss_sum, meter, loss, output, y_)
                     stats['graph_replays'] += 1
                     # (lr: the rates THIS batch's step was staged with — the optimizer's own have moved on to the last
                     # batch of the group by now)
@@ -518,8 +559,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                         stats['accum_replays'] += 1
                         averaged_step(in_replay=wa_graph.averaged is not None)
                         for (loss, output), (x_, y_) in zip(outs, batches):
-                            loss_sum += loss.detach().double() * y_.size(0)
-                            meter.update(output.detach(), y_)
+                            _tally(dstats, stats, loss_sum, meter, loss, output, y_)
                             stats['graph_replays'] += 1
                             _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
                                      learn=True, how='graph')
@@ -542,8 +582,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     got_g = iter(torch.autograd.grad(loss, live, allow_unused=True))
                     grads = [next(got_g) if t.requires_grad else None for t in targets]
                     accumulator.add([g if g is None else g.contiguous() for g in grads], w_)
-                    loss_sum += loss.detach().double() * y_.size(0)
-                    meter.update(output.detach(), y_)
+                    _tally(dstats, stats, loss_sum, meter, loss, output, y_)
                     _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
                              learn=True, how='eager')
                     output = loss = grads = got_g = None     # (no autograd graph may outlive the step: a later capture)
@@ -561,8 +600,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     return
                 stats['k_step_replays'] += 1
                 for (loss, output), (x_, y_) in zip(outs, batches):
-                    loss_sum += loss.detach().double() * y_.size(0)
-                    meter.update(output.detach(), y_)
+                    _tally(dstats, stats, loss_sum, meter, loss, output, y_)
                     stats['forward_replays'] += 1
                     stats['merged_metric_replays'] = stats.get('merged_metric_replays', 0) + 1
                     _observe('batch', epoch=epoch, phase=phase, loss=loss, output=output, optimizer=optimizer,
@@ -617,8 +655,12 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
             if _world() > 1:
                 # what the ranks processed together (a DistributedSampler pads; a split covers every sample)
                 n = int(_all_sum(torch.tensor(float(seen), device=device, dtype=torch.float64)))
-            epoch_loss = float(_all_sum(loss_sum)) / n
-            epoch_metric = meter.compute(n)
+            if dstats is None:
+                epoch_loss = float(_all_sum(loss_sum)) / n
+                epoch_metric = meter.compute(n)
+            else:                                        # one device-to-host read (summed over the ranks inside)
+                epoch_loss = dstats.loss_sum() / n
+                epoch_metric = dstats.compute(n)
             logger.info('{} Loss: {:.4f}, {}: {:.4f}'.format(phase, epoch_loss, meter.name, epoch_metric))
             logger.info('Fusion Model Params: {}'.format(fusion_params(model)))
             genotype = model.genotype()
@@ -662,6 +704,11 @@ def evaluate(model, criterion, loader, n, device, logger, args, unpack, meter, p
     device = _model_device(model, device)
     meter.reset(device)
     loss_sum = torch.zeros((), device=device, dtype=torch.float64)
+    from models.search._common import device_stats_option
+    dstats = device_stats_option(args, meter)            # (as in run: None without args.device_stats)
+    counters = evaluate.stats = dict(stat_launches=0, stat_in_replay=0, stat_fallbacks=0)
+    if dstats is not None:
+        dstats.reset(device)
     split = _world() > 1 and not _is_sharded(loader)
     seen = 0
     f_graphs = _ForwardGraphs.of(model, criterion, args, logger)
@@ -670,7 +717,10 @@ def evaluate(model, criterion, loader, n, device, logger, args, unpack, meter, p
         if split:
             inputs, labels = _shard_batch(inputs, labels)
         seen += labels.size(0)
-        got = f_graphs(model, criterion, inputs, labels)
+        if dstats is None:
+            got = f_graphs(model, criterion, inputs, labels)
+        else:
+            got = f_graphs(model, criterion, inputs, labels, stats=dstats)
         if got is not None:
             loss, output = got
         else:
@@ -678,13 +728,16 @@ def evaluate(model, criterion, loader, n, device, logger, args, unpack, meter, p
             if isinstance(output, tuple):
                 output = output[-1]
             loss = criterion(output, labels)
-        loss_sum += loss.double() * labels.size(0)
-        meter.update(output, labels)
+        _tally(dstats, counters, loss_sum, meter, loss, output, labels, got is not None and f_graphs.tallied)
     evaluate.forward_replays = f_graphs.replays
     if _world() > 1:
         n = int(_all_sum(torch.tensor(float(seen), device=device, dtype=torch.float64)))
-    epoch_loss = float(_all_sum(loss_sum)) / n
-    metric = meter.compute(n)
+    if dstats is None:
+        epoch_loss = float(_all_sum(loss_sum)) / n
+        metric = meter.compute(n)
+    else:
+        epoch_loss = dstats.loss_sum() / n
+        metric = dstats.compute(n)
     logger.info('{} Loss: {:.4f}, {}: {:.4f}'.format(phase, epoch_loss, meter.name, metric))
     logger.info('Fusion Model Params: {}'.format(fusion_params(model)))
     return metric

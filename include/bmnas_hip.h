@@ -1270,6 +1270,36 @@ int bmnas_mha_core_bwd(const float* dO, const float* q, const float* k, const fl
                        int64_t v_ss, const float* P, float* dq, float* dk, float* dv, int64_t dq_ss, int64_t dk_ss,
                        int64_t dv_ss, int b, int C, int L, int heads, bmnas_dropout_t drop, void* stream);
 
+/* ---- phase statistics: loss sum, accuracy and F1 counts of a batch in one launch (csrc/stats.hip) ------------------
+ * The trainer loop's per-batch bookkeeping (`loss_sum += loss.double() * n`, `correct += (argmax == labels).sum()`,
+ * F1 of `sigmoid(output) > th`) as ONE launch that tallies a batch of (n, O) fp32 logits into a persistent DEVICE
+ * accumulator of 64-bit words, 8-byte aligned, bmnas_phase_stats_words(O) = 4 + 3 O of them (O < 1: BMNAS_E_ARG):
+ *   word 0          the loss sum, the bits of a double
+ *   word 1          launches tallied;   word 2   samples tallied;   word 3   correct predictions (accuracy tally)
+ *   words 4 + 3c, 5 + 3c, 6 + 3c   true positives, false positives, false negatives of class c (F1 tally)
+ * Zeroed by the caller (all-zero words are the empty tally).  Both calls add (double)loss * (double)n to word 0 — the
+ * product and the sum each rounded on their own, no fused multiply-add: the word holds the bits of the loop's own
+ * float64 accumulation — with `loss` a 0-dim fp32 DEVICE tensor read by address (NULL: no loss term), add 1 to word 1
+ * and n to word 2.
+ *   bmnas_phase_stats_acc: labels (n) int64.  Per sample the argmax over its O logits with torch's rule — the first
+ *     maximum wins, a NaN is a maximum and the first NaN wins —; word 3 gains the samples whose argmax equals the label.
+ *     A label outside [0, O) is never equal (nothing is indexed by it).
+ *   bmnas_phase_stats_f1: targets (n, O) fp32.  An element is predicted positive when logit > logit_threshold (strict;
+ *     a NaN is not), truly positive when target > 0.5; the per-class tp / fp / fn words gain the counts.  The caller
+ *     stages torch's `sigmoid(x) > th` as logit_threshold = log(th / (1 - th)).
+ * Integer sums only — per lane, per workgroup, then at most one 64-bit integer atomic per counter and workgroup —,
+ * words 0 - 2 have one writer per launch: every word is independent of the grid and bit-identical from run to run.
+ * Pointers need their type's natural alignment only (4 bytes for the fp32 tensors); no access leaves the tensors.
+ * Stream work only (no host synchronisation, no allocation): capturable.  1 <= O <= BMNAS_STATS_MAX_CLASSES (the fused
+ * head's class limit) and n >= 1; anything else, a NULL logits / labels / targets / acc or a misaligned pointer:
+ * BMNAS_E_ARG, nothing launched. */
+#define BMNAS_STATS_MAX_CLASSES 128
+int bmnas_phase_stats_words(int O);
+int bmnas_phase_stats_acc(const float* logits, const int64_t* labels, const float* loss, int n, int O, uint64_t* acc,
+                          void* stream);
+int bmnas_phase_stats_f1(const float* logits, const float* targets, const float* loss, float logit_threshold, int n,
+                         int O, uint64_t* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
