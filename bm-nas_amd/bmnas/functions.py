@@ -56,6 +56,39 @@ def arch_softmax(logits, device):
     return ArchSoftmaxFn.apply(logits)
 
 
+class ArchRelaxFn(Function):
+    """z_t = (a_t + G_t) / tau for EVERY architecture tensor as one autograd node and one launch (csrc/relax.hip;
+    bmnas.nn.ArchRelaxation owns `state`, the device block with tau, the seed and the noise counter).
+    ArchRelaxFn.apply(state, gumbel, advance, *logits) -> *z.  The backward, da_t = dz_t / tau, is one launch over the
+    inputs that need a gradient and received one — none under bmnas.cell.weight_grads_only."""
+
+    @staticmethod
+    def forward(ctx, state, gumbel, advance, *logits):
+        dev = state.device
+        # (the reference keeps the arch tensors wherever the model was built: copy over first, as arch_softmax does)
+        a = [_c(_f32(t if t.device == dev else t.to(dev))) for t in logits]
+        z = [torch.empty_like(t) for t in a]
+        lib.arch_relax_fwd(a, z, None, state, gumbel, advance)
+        ctx.state = state
+        ctx.devices = [t.device for t in logits]
+        ctx.set_materialize_grads(False)
+        return tuple(z)
+
+    @staticmethod
+    def backward(ctx, *dz):
+        n = len(dz)
+        out = [None] * n
+        if not K._NO_ARCH[0]:
+            sel = [i for i in range(n) if dz[i] is not None and ctx.needs_input_grad[3 + i]]
+            if sel:
+                g = [_c(dz[i]) for i in sel]
+                da = [torch.empty_like(t) for t in g]
+                lib.arch_relax_bwd(g, da, ctx.state)
+                for i, d in zip(sel, da):
+                    out[i] = d if d.device == ctx.devices[i] else d.to(ctx.devices[i])
+        return (None, None, None, *out)
+
+
 # --------------------------------------------------------------------------- K1
 class MixSumFn(Function):
     """out = sum_j w[j] * xs[j]  (w: (n_in,) device tensor)."""

@@ -18,6 +18,24 @@ def _step_arena_on():
     return os.environ.get('BMNAS_STEP_ARENA', '1') != '0'
 
 
+def _relax_counters(model):
+    """[(relaxation, its noise counter now)] of every bmnas.nn.ArchRelaxation set under `model`: the warm-up and
+    rehearsal passes of a build draw noise, and like their BatchNorm updates that is undone (`_relax_restore`) — the
+    first replay draws the noise of the counter the build found.  Device-to-device copies: no host synchronisation."""
+    mods = getattr(model, 'modules', None)
+    found = []
+    for m in (mods() if callable(mods) else ()):
+        r = getattr(m, 'relaxation', None)
+        if r is not None and hasattr(r, 'save_counter') and r.state.is_cuda:
+            found.append((r, r.save_counter()))
+    return found
+
+
+def _relax_restore(saved):
+    for r, c in saved:
+        r.restore_counter(c)
+
+
 class GraphedStep:
     """fn() must read its inputs from static tensors, set ``.grad = None`` on everything it
     differentiates (so the backward writes instead of accumulating) and return tensors that
@@ -365,6 +383,7 @@ class GraphedTrainStep:
         # initialisation; extra optimizer steps on the example batch would change training) and
         # their BatchNorm running-statistics updates are undone afterwards.
         state = {k: v.clone() for k, v in model.state_dict().items()}
+        relax = _relax_counters(model)          # ... and the noise draws of an architecture relaxation
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         try:
@@ -385,6 +404,7 @@ class GraphedTrainStep:
         except BaseException:
             torch.cuda.synchronize()
             model.load_state_dict(state)
+            _relax_restore(relax)
             raise
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -423,6 +443,7 @@ class GraphedTrainStep:
             raise
         finally:
             model.load_state_dict(state)        # also when the capture fails and the caller stays eager
+            _relax_restore(relax)
 
     @staticmethod
     def try_build(model, criterion, optimizer, inputs, labels, logger=None, metric_forward=False, k=1, averaged=None,
@@ -623,6 +644,7 @@ class GraphedForward:
         # (not allocated yet: the first pass allocates it, and it is left empty)
         tally = stats.acc.clone() if stats is not None and stats.acc is not None else None
         counted = (stats.launches, stats.fallbacks) if stats is not None else None
+        relax = _relax_counters(model)           # ... nor use up noise draws of an architecture relaxation
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         try:
@@ -646,6 +668,7 @@ class GraphedForward:
             torch.cuda.synchronize()
             if state is not None:
                 model.load_state_dict(state)
+            _relax_restore(relax)
             if stats is not None:
                 if stats.acc is not None:
                     if tally is not None and tally.shape == stats.acc.shape:

@@ -351,6 +351,8 @@ SIGNATURES = {
                                   _P, _P, _I64, _PP, _I, _P, _P, _P, _P, _I64, _P], _I),
     'bmnas_arch_softmax_multi': ([_PP, _PP, _PP, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I64,
                                  _P], _I),
+    'bmnas_arch_relax_fwd': ([_PP, _PP, _PP, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I64, _P, _I, _I, _P], _I),
+    'bmnas_arch_relax_bwd': ([_PP, _PP, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _P, _P], _I),
     'bmnas_fc_edges_ok': ([_I, _I, _I, _I, _I, _I], _I),
     'bmnas_fc_edges_gemm_fwd': ([C.POINTER(FcEdge), _I, _I, _I, _I, _I, _I, _P], _I),
     'bmnas_fc_edges_mix_fwd': ([C.POINTER(FcEdge), _I, _I, _P, _I, _U32, _I, _P, _I, _I, _I, _P], _I),
@@ -1460,6 +1462,62 @@ def arch_softmax_multi(a_list, dw_list, out_list, backward, n_shards=1, shard_st
     _check(load().bmnas_arch_softmax_multi(pa, pd, po, rows, cols, n, int(backward), n_shards,
                                            shard_stride, _stream()),
            'arch_softmax_multi')
+
+
+RELAX_STATE_WORDS = 3                        # bmnas_arch_relax_state_t as int64 words: tau (fp32, low half) | seed | step
+RELAX_MAX_ELEMS = 65536                      # elements one relax launch takes (include/bmnas_hip.h)
+RELAX_LAUNCHES = {'fwd': 0, 'bwd': 0}        # launches issued by the two wrappers below (tests/test_arch_relax_gpu.py)
+
+
+def _relax_state_ptr(state, name):
+    if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.int64 and state.is_contiguous()
+            and state.numel() >= RELAX_STATE_WORDS):
+        raise BmnasError(f'{name}: state must be a contiguous int64 device tensor of {RELAX_STATE_WORDS} words '
+                         '(bmnas_arch_relax_state_t)')
+    return state.data_ptr()
+
+
+def _relax_arrays(ts):
+    n = len(ts)
+    rows = (C.c_int * n)(*[t.shape[0] for t in ts])
+    cols = (C.c_int * n)(*[t.shape[1] for t in ts])
+    return n, rows, cols
+
+
+def arch_relax_fwd(a_list, z_list, noise_list, state, gumbel, advance, e0=0):
+    """z = (a + G) / tau over every (rows, cols) architecture tensor of a_list (bmnas_arch_relax_fwd): one launch per
+    MAX_PTRS tensors — the running element count goes into e0 and only the last launch advances the counter, so the
+    launches together give the bits of one.  noise_list: None, or one tensor / None per entry of a_list (receives G).
+    state: the int64 device words of bmnas_arch_relax_state_t."""
+    sp = _relax_state_ptr(state, 'arch_relax_fwd')
+    if noise_list is not None and len(noise_list) != len(a_list):
+        raise BmnasError('arch_relax_fwd: noise_list must have one entry per tensor')
+    if len(a_list) != len(z_list) or not a_list:
+        raise BmnasError('arch_relax_fwd: one output per (at least one) input tensor')
+    e = int(e0)
+    for lo in range(0, len(a_list), MAX_PTRS):
+        hi = min(lo + MAX_PTRS, len(a_list))
+        n, rows, cols = _relax_arrays(a_list[lo:hi])
+        pn = None if noise_list is None else _ptrs(noise_list[lo:hi])
+        last = hi == len(a_list)
+        _check(load().bmnas_arch_relax_fwd(_ptrs(a_list[lo:hi]), _ptrs(z_list[lo:hi]), pn, rows, cols, n, e, sp,
+                                           int(bool(gumbel)), int(bool(advance) and last), _stream()),
+               'arch_relax_fwd')
+        RELAX_LAUNCHES['fwd'] += 1
+        e += sum(t.numel() for t in a_list[lo:hi])
+
+
+def arch_relax_bwd(dz_list, da_list, state):
+    """da = dz / tau over the tensors of dz_list (bmnas_arch_relax_bwd), one launch per MAX_PTRS tensors."""
+    sp = _relax_state_ptr(state, 'arch_relax_bwd')
+    if len(dz_list) != len(da_list) or not dz_list:
+        raise BmnasError('arch_relax_bwd: one output per (at least one) input tensor')
+    for lo in range(0, len(dz_list), MAX_PTRS):
+        hi = min(lo + MAX_PTRS, len(dz_list))
+        n, rows, cols = _relax_arrays(dz_list[lo:hi])
+        _check(load().bmnas_arch_relax_bwd(_ptrs(dz_list[lo:hi]), _ptrs(da_list[lo:hi]), rows, cols, n, sp,
+                                           _stream()), 'arch_relax_bwd')
+        RELAX_LAUNCHES['bwd'] += 1
 
 
 # ----------------------------------------------------------------- optional kernel timing

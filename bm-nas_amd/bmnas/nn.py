@@ -125,6 +125,138 @@ def _crit_of(module, kind):
                          ignore_index=getattr(module, 'ignore_index', -100), reduction=module.reduction)
 
 
+def relax_schedule_tau(tau_max, tau_min, epochs, epoch):
+    """tau of epoch `epoch` on the exponential schedule tau_max * (tau_min / tau_max) ** (epoch / (epochs - 1)), formed
+    in float64; epochs == 1 gives tau_max; epochs past the last hold tau_min."""
+    if epochs == 1:
+        return float(tau_max)
+    e = min(max(int(epoch), 0), epochs - 1)
+    return float(tau_max) * (float(tau_min) / float(tau_max)) ** (e / (epochs - 1))
+
+
+class ArchRelaxation:
+    """What the search hypernet softmaxes instead of its raw architecture tensors (FusionNetwork.set_relaxation):
+         z = a / tau            an (annealed) temperature
+         z = (a + G) / tau      gumbel=True: Gumbel-softmax sampling, fresh noise G every training step
+    as ONE launch over all of them (bmnas.functions.ArchRelaxFn, csrc/relax.hip).  tau, the noise seed and the noise
+    counter live in a small DEVICE block the launch reads by address, so a captured step honours a tau edited between
+    replays and draws the noise of counter c, c + 1, ... on successive replays; nothing is frozen into a hipGraph.
+
+    Noise is drawn iff `gumbel` and the owning module is in training mode; in eval mode z = a / tau and the counter
+    stands still.  The stream is independent of the dropout stream (bmnas.cell.DROP): no dropout offset is consumed and
+    the masks of a step are the same with and without the relaxation.  seed: None takes torch.initial_seed()."""
+
+    def __init__(self, tau=1.0, gumbel=False, seed=None):
+        self.gumbel = bool(gumbel)
+        self.seed = int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
+        self.schedule = None                                      # (tau_max, tau_min, epochs)
+        self.epoch = None
+        self._state = torch.zeros(lib.RELAX_STATE_WORDS, dtype=torch.int64)     # moves to the device with its network
+        signed = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
+        self._state[1] = signed
+        self._tau = None
+        self.tau = tau
+
+    # -- the device block ---------------------------------------------------------------------------------------------
+    @property
+    def state(self):
+        """The int64 words of bmnas_arch_relax_state_t: tau (fp32 bits, low half of word 0) | seed | counter."""
+        return self._state
+
+    def to(self, device):
+        """Move the block (before any capture: a captured launch holds its address)."""
+        if self._state.device != torch.device(device):
+            self._state = self._state.to(device)
+        return self
+
+    @property
+    def tau(self):
+        """The last value set (the host's mirror: reading it does not synchronise)."""
+        return self._tau
+
+    @tau.setter
+    def tau(self, value):
+        value = float(value)
+        if not (value > 0.0 and value < float('inf')):
+            raise ValueError(f'ArchRelaxation: tau must be a finite float > 0, got {value!r}')
+        self._tau = value
+        self._state.view(torch.float32)[0:1].fill_(value)         # one device fill, outside any replay
+
+    @property
+    def counter(self):
+        """The noise counter, a one-element int64 view of the device block."""
+        return self._state[2:3]
+
+    def save_counter(self):
+        return self.counter.clone()
+
+    def restore_counter(self, t):
+        self.counter.copy_(t, non_blocking=True)
+
+    # -- schedule -----------------------------------------------------------------------------------------------------
+    def set_schedule(self, tau_max, tau_min, epochs):
+        tau_max, tau_min, epochs = float(tau_max), float(tau_min), int(epochs)
+        if not (tau_min > 0.0 and tau_max < float('inf')):
+            raise ValueError(f'ArchRelaxation: the schedule needs 0 < tau_min and a finite tau_max, got tau_min '
+                             f'{tau_min!r}, tau_max {tau_max!r}')
+        if tau_min > tau_max:
+            raise ValueError(f'ArchRelaxation: tau_min {tau_min!r} > tau_max {tau_max!r} (the schedule anneals downwards)')
+        if epochs < 1:
+            raise ValueError(f'ArchRelaxation: the schedule needs epochs >= 1, got {epochs!r}')
+        self.schedule = (tau_max, tau_min, epochs)
+        return self
+
+    def set_epoch(self, epoch):
+        """tau of this epoch on the schedule (no schedule: tau stays).  -> tau."""
+        self.epoch = int(epoch)
+        if self.schedule is not None:
+            self.tau = relax_schedule_tau(*self.schedule, self.epoch)
+        return self.tau
+
+    # -- state --------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        return dict(tau=self._tau, gumbel=self.gumbel, seed=self.seed, counter=self.counter.detach().cpu().clone(),
+                    schedule=None if self.schedule is None else tuple(self.schedule), epoch=self.epoch)
+
+    def load_state_dict(self, sd):
+        self.gumbel = bool(sd['gumbel'])
+        self.seed = int(sd['seed']) & 0xFFFFFFFFFFFFFFFF
+        self._state[1:2].fill_(self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed)
+        self.schedule = None if sd.get('schedule') is None else tuple(sd['schedule'])
+        self.epoch = sd.get('epoch')
+        self.tau = sd['tau']
+        self.counter.copy_(torch.as_tensor(sd['counter'], dtype=torch.int64).reshape(1))
+
+    # -- the launch ---------------------------------------------------------------------------------------------------
+    def draws(self, training):
+        return self.gumbel and bool(training)
+
+    def __call__(self, training, *logits):
+        """-> the tuple of z, one per tensor of `logits`, as ONE autograd node; with noise (and the counter moved on by
+        one) iff gumbel and training."""
+        from .functions import ArchRelaxFn
+        dev = next((t.device for t in logits if t.is_cuda), None)
+        if dev is None:
+            raise RuntimeError('bmnas: the architecture relaxation needs its tensors on a HIP device; the fusion-cell '
+                               'hot path runs only on the gfx950 kernels — there is no CPU fallback')
+        self.to(dev)
+        draw = self.draws(training)
+        return ArchRelaxFn.apply(self._state, draw, draw, *logits)
+
+    def peek(self, *logits, training=True):
+        """The forward with the counter left where it is -> (z, noise): what the NEXT training step will hand to the
+        softmax and the Gumbel noise it will draw (zeros without `gumbel` or in eval mode).  The audit export."""
+        dev = next((t.device for t in logits if t.is_cuda), None)
+        if dev is None:
+            raise RuntimeError('bmnas: ArchRelaxation.peek needs tensors on a HIP device')
+        self.to(dev)
+        a = [t.detach().to(dev).float().contiguous() for t in logits]
+        z = [torch.empty_like(t) for t in a]
+        noise = [torch.zeros_like(t) for t in a]
+        lib.arch_relax_fwd(a, z, noise, self._state, self.draws(training), False)
+        return z, noise
+
+
 class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
     def forward(self, input, target):
         plan = _criterion_plan(self, input, target)

@@ -243,6 +243,44 @@ def device_stats_option(args, meter):
     return fresh
 
 
+def relaxation_option(args, status, num_epochs, world=None):
+    """The relaxation of the architecture weights in a search (optional; the reference's argument sets have none of these
+    and its softmax is the one at temperature 1):
+      args.arch_tau      a float > 0 (default 1): the hypernet softmaxes a / tau
+      args.arch_tau_min  with it tau anneals from arch_tau down to arch_tau_min over the run's epochs, exponentially
+                         (bmnas.nn.ArchRelaxation.set_schedule; the loop calls set_epoch at the top of every epoch)
+      args.arch_gumbel   bool: Gumbel-softmax sampling, softmax((a + G) / tau) with fresh noise every training step; the
+                         noise seed is args.seed when present, else torch.initial_seed()
+    -> a bmnas.nn.ArchRelaxation for FusionNetwork.set_relaxation, or None when none of them is set (the run is then what
+    it always was).  Refused: a found-stage run (status 'eval': no architecture weights), args.unrolled (the + and - passes
+    of the difference quotient would need the same draw — ArchRelaxation.save_counter / restore_counter exist for that,
+    the step is not wired to them) and data parallelism (world: the number of ranks; None: asks torch.distributed and the
+    environment — an idle replica of an uneven scatter skips its forward and its noise counter would fall behind)."""
+    tau, tau_min = getattr(args, 'arch_tau', None), getattr(args, 'arch_tau_min', None)
+    gumbel = bool(getattr(args, 'arch_gumbel', False))
+    if tau is None and tau_min is None and not gumbel:
+        return None
+    if status == 'eval':
+        raise ValueError("args.arch_tau / args.arch_tau_min / args.arch_gumbel relax the architecture weights of a search: "
+                         "a found-stage run (status 'eval') has none")
+    if bool(getattr(args, 'unrolled', False)):
+        raise ValueError('args.arch_tau / args.arch_tau_min / args.arch_gumbel cannot be combined with args.unrolled (the '
+                         'two passes of its difference quotient would need the same noise draw; not wired)')
+    if world is None:
+        import torch.distributed as dist
+        world = max(data_parallel_world(args),
+                    dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1)
+    if world > 1:
+        raise ValueError(f'args.arch_tau / args.arch_tau_min / args.arch_gumbel are not available under data parallelism '
+                         f'({world} ranks): a replica that idles through a batch would fall behind in the noise counter')
+    tau = 1.0 if tau is None else float(tau)
+    seed = getattr(args, 'seed', None)
+    relax = bnn.ArchRelaxation(tau=tau, gumbel=gumbel, seed=None if seed is None else int(seed))
+    if tau_min is not None:
+        relax.set_schedule(tau, float(tau_min), int(num_epochs))
+    return relax
+
+
 def make_averager(model, args, status):
     """-> (bmnas.optim.AveragedModel of `model`, its options), or (None, None) without the options.  use_buffers=True
     — averaged running statistics stand in for swa_utils.update_bn's cumulative pass — unless args.swa_update_bn asks

@@ -97,18 +97,26 @@ class FusionCell(nn.Module):
                 and classifier.in_features == self._multiplier * self.C * self.L
                 and all(op._default for n in self._step_nodes for op in n.node_cell.node_ops))
 
-    def forward(self, input_features, weights, weights_are_logits=False, classifier=None):
+    def forward(self, input_features, weights, weights_are_logits=False, classifier=None, arch=None):
         """weights: the softmaxed alphas (k, 2), as in the reference; FusionNetwork passes the
         raw alphas with weights_are_logits=True so that every arch softmax of the cell runs
         in one kernel launch.  classifier (FusionNetwork.forward_classified): a bmnas.nn.Linear
-        the cell's output feeds — the call then returns ITS output, with K7 + Linear as one launch."""
+        the cell's output feeds — the call then returns ITS output, with K7 + Linear as one launch.
+        arch (FusionNetwork with a relaxation set): the logits [betas_0, gammas_0, betas_1, ...] the step nodes
+        softmax INSTEAD of their own betas / gammas (bmnas.nn.ArchRelaxation's z); None: the nodes' own."""
         states = list(input_features)
         dev = states[0].device
         w = weights if weights.device == dev else weights.to(dev)
+        if arch is not None and len(arch) != 2 * len(self._step_nodes):
+            raise ValueError(f'FusionCell.forward: arch holds {len(arch)} tensors, the cell has '
+                             f'{len(self._step_nodes)} step nodes (betas and gammas of each)')
         if self._fusable and all(op._default for n in self._step_nodes for op in n.node_cell.node_ops):
-            arch = []
-            for n in self._step_nodes:
-                arch += [t if t.device == dev else t.to(dev) for t in (n.betas, n.gammas)]
+            if arch is None:
+                arch = []
+                for n in self._step_nodes:
+                    arch += [t if t.device == dev else t.to(dev) for t in (n.betas, n.gammas)]
+            else:
+                arch = list(arch)
             if classifier is not None and states[0].is_cuda and self.head_fusable(classifier):
                 from bmnas import cell as K
                 out = FusedCellFn.apply(self, self.training, weights_are_logits, w, 2, *states, *arch,
@@ -127,7 +135,7 @@ class FusionCell(nn.Module):
                 sif = mixed_edge_sum(states, w, offset)
             else:
                 sif = general_edge_sum(self._ops, states, w, offset)
-            s = self._step_nodes[i](sif, sif)
+            s = self._step_nodes[i](sif, sif) if arch is None else self._step_nodes[i](sif, sif, arch[2 * i:2 * i + 2])
             offset += len(states)
             states.append(s)
         out = CatLnFn.apply(True, self.ln.weight, self.ln.bias, None, *states[-self._multiplier:])
@@ -150,6 +158,29 @@ class FusionNetwork(nn.Module):
         self.cell_arch_parameters = self.cell.arch_parameters()
         self._initialize_alphas()
         self._arch_parameters = [self.alphas_edges] + self.cell_arch_parameters
+        self._relaxation = None
+
+    def set_relaxation(self, relaxation):
+        """relaxation: a bmnas.nn.ArchRelaxation, or None (the default: the plain softmax at temperature 1, not one
+        launch or bit different from a network that never had one).  With it, forward / forward_classified run ONE
+        launch z = (a + G) / tau over [alphas_edges, betas_0, gammas_0, ...] and the cell and its step nodes softmax
+        z where they softmaxed the raw tensors.  genotype() keeps reading the raw tensors: tau > 0 does not change an
+        argmax, and the noise is not part of the architecture."""
+        if relaxation is not None and self.alphas_edges.is_cuda:
+            relaxation.to(self.alphas_edges.device)
+        self._relaxation = relaxation
+        return self
+
+    @property
+    def relaxation(self):
+        return self._relaxation
+
+    def _relaxed(self):
+        """-> (alpha logits, arch argument of the cell): the raw tensors, or the relaxation's z."""
+        if self._relaxation is None:
+            return self.alphas_edges, None
+        z = self._relaxation(self.training, *self._arch_parameters)
+        return z[0], list(z[1:])
 
     def _initialize_alphas(self):
         k = sum(self._num_input_nodes + i for i in range(self._steps))
@@ -162,19 +193,27 @@ class FusionNetwork(nn.Module):
         t.data = fn(t.data)
         if t.grad is not None:
             t.grad.data = fn(t.grad.data)
+        if self.__dict__.get('_relaxation') is not None and t.is_cuda:
+            self._relaxation.to(t.device)
         return self
 
     def forward(self, input_features):
         assert self._num_input_nodes == len(input_features)
         # softmax(alphas_edges) (reference :95) is folded into the fused cell call
-        return self.cell(input_features, self.alphas_edges, weights_are_logits=True)
+        if self._relaxation is None:
+            return self.cell(input_features, self.alphas_edges, weights_are_logits=True)
+        alpha, arch = self._relaxed()
+        return self.cell(input_features, alpha, weights_are_logits=True, arch=arch)
 
     def forward_classified(self, input_features, classifier):
         """classifier(self(input_features)) — what Searchable_*.forward does next
         (mmimdb_darts_searchable.py:113-114) — with the cell's LayerNorm tail and the classifier as
         one launch where the shapes allow (FusionCell.head_fusable), else exactly that composition."""
         assert self._num_input_nodes == len(input_features)
-        return self.cell(input_features, self.alphas_edges, weights_are_logits=True, classifier=classifier)
+        if self._relaxation is None:
+            return self.cell(input_features, self.alphas_edges, weights_are_logits=True, classifier=classifier)
+        alpha, arch = self._relaxed()
+        return self.cell(input_features, alpha, weights_are_logits=True, classifier=classifier, arch=arch)
 
     def _loss(self, input_features, labels):
         return self._criterion(self(input_features), labels)

@@ -143,9 +143,12 @@ class FusionNode(nn.Module):
                 t.grad.data = fn(t.grad.data)
         return self
 
-    def forward(self, x, y):
-        edge_weights = arch_softmax(self.betas, x.device)
-        node_weights = arch_softmax(self.gammas, x.device)
+    def forward(self, x, y, arch=None):
+        """arch (optional): the logits (betas', gammas') softmaxed INSTEAD of the node's own tensors — the relaxed
+        z of bmnas.nn.ArchRelaxation, handed down by FusionCell.forward; None: the reference's call."""
+        betas, gammas = (self.betas, self.gammas) if arch is None else arch
+        edge_weights = arch_softmax(betas, x.device)
+        node_weights = arch_softmax(gammas, x.device)
         return self.node_cell(x, y, edge_weights, node_weights)
 
     def arch_parameters(self):

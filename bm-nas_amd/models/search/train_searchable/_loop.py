@@ -299,6 +299,31 @@ def check_accum(args, world=None):
     return m
 
 
+def _set_relaxation(model, args, status, num_epochs):
+    """args.arch_tau / args.arch_tau_min / args.arch_gumbel (models.search._common.relaxation_option, which refuses the
+    combinations that are not built before anything moves) -> the bmnas.nn.ArchRelaxation now set on model.fusion_net, or
+    None without the options: the model is then not touched.  A relaxation left on the network by an earlier run() is
+    kept — captured steps hold the address of its device block — and takes the new settings; its noise counter goes on."""
+    from models.search._common import data_parallel_world, relaxation_option
+    relax = relaxation_option(args, status, num_epochs, world=max(_world(), data_parallel_world(args)))
+    if relax is None:
+        return None
+    net = getattr(model, 'fusion_net', None)
+    if not hasattr(net, 'set_relaxation'):
+        raise ValueError('args.arch_tau / args.arch_tau_min / args.arch_gumbel need a search hypernet '
+                         '(model.fusion_net.set_relaxation)')
+    kept = net.relaxation
+    if kept is None:
+        net.set_relaxation(relax)
+        return relax
+    if kept.gumbel != relax.gumbel:
+        model.__dict__.pop('_bmnas_forward_graphs', None)        # (whether noise is drawn is baked into a captured pass)
+    settings = relax.state_dict()
+    settings['counter'] = kept.counter
+    kept.load_state_dict(settings)
+    return kept
+
+
 def _observe(event, **info):
     """tests/test_outer_loop_golden_gpu.py pins the loop against the reference's trainers through this hook
     (run.observer = callable(event, **info)); None in production: no host synchronisation is added."""
@@ -314,6 +339,7 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     init: what the first epoch's metric is compared with (the reference starts from best_f1 = init_f1 with `>`,
     train_searchable/mmimdb.py:19,162, and from best_acc = 0 with `>=`, ntu.py:18,135); None: always accepted."""
     m_accum = check_accum(args)              # (first: a refused combination moves nothing)
+    relax = _set_relaxation(model, args, status, num_epochs)      # (args.arch_tau / arch_tau_min / arch_gumbel; else None)
     cosine = isinstance(scheduler, sc.LRCosineAnnealingScheduler)
     device = _model_device(model, device)
     from bmnas.graph import GraphedTrainStep
@@ -323,6 +349,8 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     wk_graph, wk_attempts = None, 0
     f_graphs = _ForwardGraphs.of(model, criterion, args, logger)
     stats = run.stats = dict(graph_replays=0, eager_steps=0, forward_replays=0, k_step_replays=0)
+    if relax is not None:                    # (without the options run.stats has the keys it always had)
+        stats['relax_tau'] = relax.tau       # the last temperature set: the schedule's value of the current epoch
     # args.device_stats: the phase statistics in one device accumulator, one launch per batch (bmnas.metrics.PhaseStats);
     # None — the option absent, or a meter that is not the loop's own — and `tally` below is the two statements of always
     from models.search._common import device_stats_option
@@ -376,6 +404,8 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
     for epoch in range(num_epochs):
         logger.info('Epoch: {}'.format(epoch))
         logger.info('EXP: {}'.format(args.save))
+        if relax is not None:
+            stats['relax_tau'] = relax.set_epoch(epoch)      # one device fill, outside any replay (captured steps read it)
         phases = ['train', 'dev'] if status == 'search' else eval_phases
         for phase in phases:
             if phase == 'train':
@@ -383,6 +413,8 @@ def run(model, architect, criterion, optimizer, scheduler, dataloaders, dataset_
                     scheduler.step()
                 if architect is not None:
                     architect.log_learning_rate(logger)
+                if relax is not None:
+                    logger.info("Architecture Temperature: {}".format(relax.tau))
                 model.train()
             elif phase == 'dev':
                 if status == 'eval' and not cosine:

@@ -1300,6 +1300,39 @@ int bmnas_phase_stats_acc(const float* logits, const int64_t* labels, const floa
 int bmnas_phase_stats_f1(const float* logits, const float* targets, const float* loss, float logit_threshold, int n,
                          int O, uint64_t* acc, void* stream);
 
+/* ---- temperature / Gumbel-softmax relaxation of the architecture tensors (csrc/relax.hip) -----------------------------
+ * The search hypernet softmaxes alphas_edges / betas / gammas at temperature 1 (model_search.py:95,
+ * node_search.py:102-103).  These two launches sit in FRONT of that softmax and behind its backward:
+ *   forward    z = a / tau                         (gumbel == 0; no Philox is evaluated)
+ *              z = (a + G) / tau                   (gumbel != 0)
+ *   backward   da = dz / tau
+ * with tau, the noise seed and the step counter read BY ADDRESS from a device block the host allocates — an edit between
+ * two replays of a captured launch takes effect, nothing is frozen into a hipGraph: */
+typedef struct {
+  float tau;        /* > 0: checked on the host, where it is set */
+  uint64_t seed;
+  uint64_t step;    /* the noise counter: one draw per value */
+} bmnas_arch_relax_state_t;
+/* Up to BMNAS_MAX_PTRS tensors per launch, taken as ONE flat element sequence (tensor order, row-major) that starts at
+ * flat index e0 (>= 0).  Element e draws
+ *   w = philox4x32_10(ctr = (step << 32) + (e >> 2), key = seed ^ 0x6A09E667F3BCC908)[e & 3]      (the generator of
+ *       bmnas_dropout_t: counter words 2, 3 fixed as there)
+ *   u = ((w >> 9) + 0.5f) * 2^-23        exact in fp32, in [2^-24, 1 - 2^-24] (a 24-bit mantissa would round to u = 1)
+ *   G = -logf(-logf(u))                  finite, in [-2.82, 16.64]
+ * with `step` the block's counter as the launch finds it.  Every operation is rounded on its own (plain add, correctly
+ * rounded division, the accurate logf).  noise (nullable; entries nullable): noise[t] receives G — the audit export, the
+ * counterpart of bmnas_dropout_mask; not written with gumbel == 0.  advance != 0: state->step += 1, exactly once, after
+ * every read of the counter (the launch is one workgroup: a barrier and one thread's ordinary store; no atomics,
+ * bit-identical from run to run).  More than BMNAS_MAX_PTRS tensors: several calls, e0 the running element count, advance
+ * on the last call only — together the bits of one launch.  cols: any value >= 1 (elementwise; no four-column limit).
+ * BMNAS_E_ARG (nothing launched): a NULL a / z / rows / cols / state or entry of a / z / dz / da, n < 1, e0 < 0, a
+ * rows[t] or cols[t] < 1.  BMNAS_E_LIMIT (nothing launched): n > BMNAS_MAX_PTRS, more than 65536 elements in a call.
+ * The backward walks the tensors the same way and reads tau only.  Stream work only: capturable. */
+int bmnas_arch_relax_fwd(const float* const* a, float* const* z, float* const* noise, const int* rows, const int* cols,
+                         int n, int64_t e0, bmnas_arch_relax_state_t* state, int gumbel, int advance, void* stream);
+int bmnas_arch_relax_bwd(const float* const* dz, float* const* da, const int* rows, const int* cols, int n,
+                         const bmnas_arch_relax_state_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
