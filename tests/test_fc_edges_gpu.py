@@ -25,7 +25,8 @@ FULL = ['none', 'fc_relu', 'fc_mish', 'skip']
 LISTS = [FULL, ['skip', 'fc_mish', 'none'], ['none', 'skip', 'fc_relu']]
 # (n, C, L, b, inner): inner = 2 states that are ONE tensor and 2-column weight rows (a search NodeCell's first sum)
 SHAPES = [(6, 192, 16, 128, False), (7, 192, 16, 37, False), (8, 128, 8, 64, False), (9, 128, 8, 7, False),
-          (2, 192, 16, 128, True), (2, 128, 8, 8, True), (4, 128, 8, 6, False)]
+          (2, 192, 16, 128, True), (2, 128, 8, 8, True), (4, 128, 8, 6, False), (3, 48, 8, 5, False),
+          (2, 80, 4, 3, True)]
 MODES = ['eval', 'train_nodrop', 'train_drop']
 NEAR = 2e-5
 

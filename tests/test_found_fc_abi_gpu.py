@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from fc_edges_util import act64, dact64, guarded, guards_intact
 from gpu_util import assert_close_of_scale, assert_close_scaled, dev
 
 pytestmark = pytest.mark.gpu
@@ -23,18 +24,6 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(16, 4, 3), (32, 16, 5), (80, 8, 9), (32, 8, 33), (192, 16, 6)]
 KINDS = [(0,), (1,), (0, 1), (1, 0, 0, 1)]
 EPS, MOMENTUM, P_DROP = 1e-5, 0.1, 0.25
-
-
-def act64(u, mish):
-    return u * torch.tanh(torch.nn.functional.softplus(u)) if mish else torch.relu(u)
-
-
-def dact64(u, mish):
-    if not mish:
-        return (u > 0).double()
-    sp = torch.nn.functional.softplus(u)
-    t = torch.tanh(sp)
-    return t + u * torch.sigmoid(u) * (1 - t * t)
 
 
 def make_case(Cc, L, b, kinds, seed):
@@ -97,22 +86,6 @@ def reference(xs, edges, masks, training, b, Cc, L):
         dxs[q['src']] += torch.einsum('mk,bml->bkl', W, dU)
         res.append(r)
     return res, dxs
-
-
-def guarded(n_rows, row_shape, guard=2):
-    """n_rows tensors of row_shape laid out in one NaN-filled buffer with `guard` NaN rows in front of, between and
-    behind them -> (buffer, views, guard views)."""
-    per = int(np.prod(row_shape))
-    buf = torch.full(((guard + 1) * n_rows + guard, per), float('nan'), device=dev(), dtype=torch.float32)
-    rows = [buf[guard + (guard + 1) * i].view(*row_shape) for i in range(n_rows)]
-    keep = torch.ones(buf.shape[0], dtype=torch.bool)
-    for i in range(n_rows):
-        keep[guard + (guard + 1) * i] = False
-    return buf, rows, keep.to(dev())
-
-
-def guards_intact(buf, keep):
-    return bool(torch.isnan(buf[keep]).all())
 
 
 def run_gpu(xs, edges, need_dx, drops, training, b, Cc, L):
