@@ -415,23 +415,11 @@ def node_mixed_fwd(x, y, gamma_row, P, training, ln=None, Weff=None, stats=None,
     same = x is y or x.data_ptr() == y.data_ptr()
     sv = MixedSaved()
     sv.x, sv.y, sv.same, sv.gamma, sv.P, sv.training = x, y, same, gamma_row, P, training
-    # attention branch
     sv.d_attn = DROP.make(P.attn_p, x.numel(), training)
-    p1 = torch.empty_like(x)
-    sv.xhat1 = torch.empty_like(x)
-    sv.stats1 = _empty(x, b * 2)
-    sv.p1 = p1
     sv.d_glu = DROP.make(P.glu_p, x.numel(), training)
     sv.d_fc = DROP.make(P.fc_p, x.numel(), training)
-    sv.merged = same and FUSE_ATTN_GEMM
-    if sv.merged:
-        U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C,
-                                  attn=(x, y, P.ln_w, P.ln_b, p1, sv.xhat1, sv.stats1, C, sv.d_attn), Weff=Weff,
-                                  stats=stats)
-    else:
-        with _Fork(x.device) as fork:
-            fork.side(lambda: lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, p1, sv.xhat1, sv.stats1, b, C, L, sv.d_attn))
-            U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C, Weff=Weff, stats=stats)
+    U, chan = _attn_conv_fwd(sv, x, y, same, P, training, True, 3 * C, Weff=Weff, stats=stats)
+    p1 = sv.p1
     out = torch.empty_like(x)
     fin = sv.conv.fin                        # BatchNorm finalised inside the mix kernel (or NO_FIN)
     if not launch_mix:                       # the caller's out_conv launch forms `out` (bmnas_node_mix_conv_fwd)
@@ -566,6 +554,58 @@ def _mixed_conv_fwd(sv, x, y, same, P, training, C, attn=None, Weff=None, stats=
     return U, chan
 
 
+def _attn_conv_fwd(sv, x, y, same, P, training, has_attn, M, Weff=None, stats=None):
+    """The attention branch (has_attn) beside the stacked conv of M rows (0: the list holds no conv) -> (U, chan), None
+    without a conv; sv.p1 / xhat1 / stats1 (None without attention), sv.conv and sv.merged are set.  x is y under
+    FUSE_ATTN_GEMM: both in one launch; else the attention on the _Fork side stream next to the conv, or whichever of
+    the two there is alone."""
+    b, C, L = x.shape
+    sv.p1 = sv.xhat1 = sv.stats1 = sv.conv = None
+    fuse = has_attn and M > 0 and same and FUSE_ATTN_GEMM
+    # forward: the merged launch takes any M; backward: its merged kernels are those of M = 3C (the default list's),
+    # other row counts run the conv backward as its own (one-launch) call with the attention backward behind it
+    sv.merged = fuse and M == 3 * C
+    if not has_attn:
+        return _mixed_conv_fwd(sv, x, y, same, P, training, C, Weff=Weff, stats=stats) if M > 0 else (None, None)
+    sv.p1, sv.xhat1, sv.stats1 = torch.empty_like(x), torch.empty_like(x), _empty(x, b * 2)
+    if fuse:
+        return _mixed_conv_fwd(sv, x, y, same, P, training, C,
+                               attn=(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, C, sv.d_attn), Weff=Weff,
+                               stats=stats)
+
+    def attn_alone():
+        lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, b, C, L, sv.d_attn)
+    if M == 0:
+        attn_alone()
+        return None, None
+    with _Fork(x.device) as fork:
+        fork.side(attn_alone)
+        return _mixed_conv_fwd(sv, x, y, same, P, training, C, Weff=Weff, stats=stats)
+
+
+def _mixed_contract_bwd(sv, g, gcol, dV, bn_grad, slots, G, fork=None, acc=None):
+    """The contractions behind a mix backward launch: the conv's data and weight gradients and the attention backward,
+    into slots = [x_slot] (x is y) | [x_slot, y_slot].  gcol: the gamma column of ScaleDotAttn (None: a list without it).
+    acc: the accumulate mask of the attention backward when it is a launch of its own — None: the slots' own state,
+    read behind the conv."""
+    x, y = sv.x, sv.y
+    b, C, L = x.shape
+    if sv.merged and slots[0].extra is None:
+        # every contraction in one launch: the attention gradient is produced next to the data-gradient GEMM, into its
+        # own buffer; whoever consumes x_slot adds the two parts (g2 / gz2 of the K1 backward)
+        slots[0].extra = torch.empty_like(x)
+        conv_bn_bwd(sv.conv, dV, bn_grad, slots, G.stack_dW, G.stack_dbias, fork,
+                    attn=(g, gcol, x, y, sv.P.ln_w, sv.xhat1, sv.stats1, slots[0].extra, None, 0, C, sv.d_attn))
+        return
+    if sv.conv is not None:
+        conv_bn_bwd(sv.conv, dV, bn_grad, slots, G.stack_dW, G.stack_dbias, fork)
+    if gcol is not None:
+        dx, dy = slots[0].buf(), (slots[1].buf() if len(slots) > 1 else None)
+        if acc is None:
+            acc = slots[0].acc_bit() | (slots[1].acc_bit() << 1 if dy is not None else 0)
+        lib.sdpa_ln_bwd(g, gcol, x, y, sv.P.ln_w, sv.xhat1, sv.stats1, dx, dy, acc, b, C, L, sv.d_attn)
+
+
 class Deferred:
     """LayerNorm affine-gradient problems collected during a backward pass and flushed in
     ONE launch at its end (they feed nothing downstream)."""
@@ -612,52 +652,33 @@ def node_mixed_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_stride=
     M = 3 * C
     dV = _empty(x, b, M, L) if pre_done is None else pre_done[0]
     bn_grad = G.stack_bn_grad            # [dW_bn (3C) | dB_bn (3C)], zero-initialised by caller
+    gcol = sv.gamma[1:2]
     with _Fork(x.device) as fork:
-        if sv.same and pre_done is not None:
-            # the mix backward already ran as the epilogue of the out_conv data-gradient tiles
+        if sv.same:
+            # pre_done: the mix backward already ran as the epilogue of the out_conv data-gradient tiles
             # (bmnas_conv1x1_bwd_all_mix): dV, bn_grad, dgamma and x_slot are done; the contractions remain
-            dxb = pre_done[1]
-            if sv.merged and x_slot.extra is None:
-                x_slot.extra = torch.empty_like(x)
-                conv_bn_bwd(sv.conv, dV, bn_grad, [x_slot], G.stack_dW, G.stack_dbias, fork,
-                            attn=(g, sv.gamma[1:2], x, y, sv.P.ln_w, sv.xhat1, sv.stats1, x_slot.extra, None,
-                                  0, C, sv.d_attn))
-            else:
-                conv_bn_bwd(sv.conv, dV, bn_grad, [x_slot], G.stack_dW, G.stack_dbias, fork)
-                lib.sdpa_ln_bwd(g, sv.gamma[1:2], x, y, sv.P.ln_w, sv.xhat1, sv.stats1, dxb, None, 1, b, C, L,
-                                sv.d_attn)
-        elif sv.same:
-            if ln is not None:
-                gy, pre, ln_w, stats, r_slot, g_slot, lazy = ln
-                g = g_slot.buf()
-                g_slot.written = True
-                rbuf, racc = r_slot.buf(), r_slot.acc_bit()
-            dxb, acc = x_slot.buf(), x_slot.acc_bit()
-            if ln is not None and lazy is not None:
-                bn_part = _empty(x, lib.node_mix_lnp_bwd_rows(b) * 6 * C) if DETERMINISTIC else None
-                lib.node_mix_lnp_bwd(gy, pre, ln_w, stats, lazy.lnp_head, lazy.lnp_k1, g, rbuf, racc, x, y, sv.p1,
-                                     sv.conv.U, sv.conv.chan, sv.gamma, dgamma_row, dxb, None, acc, dV, bn_grad,
-                                     b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride, bn_part)
-            elif ln is not None:
-                lib.node_mix_ln_bwd(gy, pre, ln_w, stats, g, rbuf, racc, x, y, sv.p1, sv.conv.U, sv.conv.chan,
-                                    sv.gamma, dgamma_row, dxb, None, acc, dV, bn_grad, b, C, L, sv.d_glu,
-                                    sv.d_fc, shards, shard_stride)
-            else:
-                lib.node_mix_bwd(g, x, y, sv.p1, sv.conv.U, sv.conv.chan, sv.gamma, dgamma_row, dxb, None, acc,
-                                 dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride, nxt)
-            if nxt is not None:
-                g = nxt[-1]                  # the launch completed this step's gradient there
-            if sv.merged and x_slot.extra is None:
-                # the attention gradient is produced next to the data-gradient GEMM, into its own
-                # buffer; whoever consumes x_slot adds the two parts (g2 / gz2 of the K1 backward)
-                x_slot.extra = torch.empty_like(x)
-                conv_bn_bwd(sv.conv, dV, bn_grad, [x_slot], G.stack_dW, G.stack_dbias, fork,
-                            attn=(g, sv.gamma[1:2], x, y, sv.P.ln_w, sv.xhat1, sv.stats1, x_slot.extra, None,
-                                  0, C, sv.d_attn))
-            else:
-                conv_bn_bwd(sv.conv, dV, bn_grad, [x_slot], G.stack_dW, G.stack_dbias, fork)
-                lib.sdpa_ln_bwd(g, sv.gamma[1:2], x, y, sv.P.ln_w, sv.xhat1, sv.stats1, dxb, None, 1, b, C, L,
-                                sv.d_attn)
+            if pre_done is None:
+                if ln is not None:
+                    gy, pre, ln_w, stats, r_slot, g_slot, lazy = ln
+                    g = g_slot.buf()
+                    g_slot.written = True
+                    rbuf, racc = r_slot.buf(), r_slot.acc_bit()
+                dxb, acc = x_slot.buf(), x_slot.acc_bit()
+                if ln is not None and lazy is not None:
+                    bn_part = _empty(x, lib.node_mix_lnp_bwd_rows(b) * 6 * C) if DETERMINISTIC else None
+                    lib.node_mix_lnp_bwd(gy, pre, ln_w, stats, lazy.lnp_head, lazy.lnp_k1, g, rbuf, racc, x, y, sv.p1,
+                                         sv.conv.U, sv.conv.chan, sv.gamma, dgamma_row, dxb, None, acc, dV, bn_grad,
+                                         b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride, bn_part)
+                elif ln is not None:
+                    lib.node_mix_ln_bwd(gy, pre, ln_w, stats, g, rbuf, racc, x, y, sv.p1, sv.conv.U, sv.conv.chan,
+                                        sv.gamma, dgamma_row, dxb, None, acc, dV, bn_grad, b, C, L, sv.d_glu,
+                                        sv.d_fc, shards, shard_stride)
+                else:
+                    lib.node_mix_bwd(g, x, y, sv.p1, sv.conv.U, sv.conv.chan, sv.gamma, dgamma_row, dxb, None, acc,
+                                     dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride, nxt)
+                if nxt is not None:
+                    g = nxt[-1]                  # the launch completed this step's gradient there
+            _mixed_contract_bwd(sv, g, gcol, dV, bn_grad, [x_slot], G, fork, 1)
         else:
             dxb, dyb = x_slot.buf(), y_slot.buf()
             acc = x_slot.acc_bit() | (y_slot.acc_bit() << 1)
@@ -665,9 +686,7 @@ def node_mixed_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_stride=
                              dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride, nxt)
             if nxt is not None:
                 g = nxt[-1]
-            conv_bn_bwd(sv.conv, dV, bn_grad, [x_slot, y_slot], G.stack_dW, G.stack_dbias, fork)
-            lib.sdpa_ln_bwd(g, sv.gamma[1:2], x, y, sv.P.ln_w, sv.xhat1, sv.stats1, dxb, dyb, 3, b, C, L,
-                            sv.d_attn)
+            _mixed_contract_bwd(sv, g, gcol, dV, bn_grad, [x_slot, y_slot], G, fork, 3)
     _attn_affine_bwd(sv, g, G, deferred)
 
 
@@ -694,31 +713,10 @@ def node_mixed_sel_fwd(x, y, gamma_row, P, training):
             sv.d_glu = DROP.make(P.glu_p, x.numel(), training)
         elif name == 'ConcatFC':
             sv.d_fc = DROP.make(P.fc_p, x.numel(), training)
-    sv.p1 = sv.xhat1 = sv.stats1 = sv.conv = None
-    sv.merged = False
-    attn = None
     if has_attn:
         sv.attn_col = prims.index('ScaleDotAttn')
-        sv.p1, sv.xhat1, sv.stats1 = torch.empty_like(x), torch.empty_like(x), _empty(x, b * 2)
-        attn = (x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, C, sv.d_attn)
-    U = chan = None
-    fin = lib.NO_FIN
-    if M > 0:
-        if has_attn and same and FUSE_ATTN_GEMM:
-            # forward: the merged launch takes any M; backward: its merged kernels are those of M = 3C, other row
-            # counts run the conv backward as its own (one-launch) call with the attention backward behind it
-            sv.merged = M == 3 * C
-            U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C, attn=attn)
-        elif has_attn:
-            with _Fork(x.device) as fork:
-                fork.side(lambda: lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, b, C, L,
-                                                  sv.d_attn))
-                U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C)
-        else:
-            U, chan = _mixed_conv_fwd(sv, x, y, same, P, training, C)
-        fin = sv.conv.fin
-    elif has_attn:
-        lib.sdpa_ln_fwd(x, y, P.ln_w, P.ln_b, sv.p1, sv.xhat1, sv.stats1, b, C, L, sv.d_attn)
+    U, chan = _attn_conv_fwd(sv, x, y, same, P, training, has_attn, M)
+    fin = sv.conv.fin if M > 0 else lib.NO_FIN
     out = torch.empty_like(x)
     lib.node_mix_sel_fwd(x if has_sum else None, y if has_sum else None, sv.p1, U, chan, gamma_row, sv.sel, out,
                          b, C, L, sv.d_glu, sv.d_fc, fin, fc_act=P.fc_act)
@@ -747,24 +745,8 @@ def node_mixed_sel_bwd(sv, g, dgamma_row, x_slot, y_slot, G, shards=1, shard_str
     lib.node_mix_sel_bwd(g, x if has_sum else None, y if has_sum else None, sv.p1, U, chan, sv.gamma, sv.sel,
                          dgamma_row, dxb, dyb, acc, dV, bn_grad, b, C, L, sv.d_glu, sv.d_fc, shards, shard_stride,
                          fc_act=P.fc_act)
-    slots = [x_slot] if sv.same else [x_slot, y_slot]
-    if has_attn:
-        gcol = sv.gamma[sv.attn_col:sv.attn_col + 1]
-    if sv.merged and x_slot.extra is None:
-        # every contraction in one launch, exactly as node_mixed_bwd: the attention gradient goes to its own buffer
-        x_slot.extra = torch.empty_like(x)
-        conv_bn_bwd(sv.conv, dV, bn_grad, slots, G.stack_dW, G.stack_dbias,
-                    attn=(g, gcol, x, y, P.ln_w, sv.xhat1, sv.stats1, x_slot.extra, None, 0, C, sv.d_attn))
-    else:
-        if M > 0:
-            conv_bn_bwd(sv.conv, dV, bn_grad, slots, G.stack_dW, G.stack_dbias)
-        if has_attn:
-            dxa, amask = x_slot.buf(), x_slot.acc_bit()
-            dya = None
-            if not sv.same:
-                dya = y_slot.buf()
-                amask |= y_slot.acc_bit() << 1
-            lib.sdpa_ln_bwd(g, gcol, x, y, P.ln_w, sv.xhat1, sv.stats1, dxa, dya, amask, b, C, L, sv.d_attn)
+    gcol = sv.gamma[sv.attn_col:sv.attn_col + 1] if has_attn else None
+    _mixed_contract_bwd(sv, g, gcol, dV, bn_grad, [x_slot] if sv.same else [x_slot, y_slot], G)
     if has_attn:
         _attn_affine_bwd(sv, g, G, deferred)
 

@@ -28,6 +28,32 @@ def _f32(t):
     return t
 
 
+def _round4(n):
+    """n floats rounded up to a multiple of four: slices carved at such offsets stay 16-byte aligned."""
+    return (n + 3) // 4 * 4
+
+
+# ---- the gradients a conv + BatchNorm of M rows and weight row stride ldw accumulates with atomics: ONE zero-filled chunk
+# bn_grad [2M: the BatchNorm's dweight | dbias] | dW (M, ldw) | dbias [M] — the layout of every conv + BatchNorm Function
+def conv_grad_floats(M, ldw):
+    return 2 * M + M * ldw + M
+
+
+def conv_grad_split(buf, M, ldw, off=0):
+    """-> (bn_grad, dW, dbias) of the chunk that starts at float `off` of buf."""
+    w, e = off + 2 * M, off + 2 * M + M * ldw
+    return buf[off:w], buf[w:e].view(M, ldw), buf[e:e + M]
+
+
+def conv_grad_offsets(M, ldws, base=0):
+    """The group form: where the chunks of len(ldws) convs start behind `base` floats, each on a multiple of four floats;
+    one entry more than chunks, the last being the floats of the whole buffer."""
+    offs = [base]
+    for ldw in ldws:
+        offs.append(offs[-1] + _round4(conv_grad_floats(M, ldw)))
+    return offs
+
+
 # ------------------------------------------------------------------- arch softmax
 class ArchSoftmaxFn(Function):
     """softmax(logits, dim=-1) for the (rows, 2|4) architecture parameters
@@ -196,7 +222,7 @@ class _StepArena:
     def take(self, n):
         """n floats (exactly n: callers view the slice by shape); the cursor advances by n rounded up to a multiple of
         four so that every slice stays 16-byte aligned."""
-        step = (n + 3) // 4 * 4
+        step = _round4(n)
         if self.off + step > self.buf.numel():
             return None
         v = self.buf[self.off:self.off + n]
@@ -244,7 +270,7 @@ def zeros_for_step(n, device):
     """n zero-filled floats: a slice of the captured step's arena (cleared in front of every replay by the batch-copy
     launch), else torch.zeros — one fill launch."""
     if _ARENA_NEED is not None:
-        _ARENA_NEED[0] += (n + 3) // 4 * 4
+        _ARENA_NEED[0] += _round4(n)
     if _ARENA is not None and _ARENA.buf.device == device:
         v = _ARENA.take(n)
         if v is not None:
@@ -352,7 +378,7 @@ class FoundHeadFn(Function):
         b, C, L = states[0].shape
         Wc, bc = _c(_f32(W)), _c(_f32(bias))
         O = Wc.shape[0]
-        hb_n = (3 * b * O + 3) // 4 * 4
+        hb_n = _round4(3 * b * O)
         buf = zeros_for_step(hb_n + 4, dev)                   # logits | A | B accumulate with atomics; + the loss scalar
         head = K.HeadState(W=Wc, bias=bc, hb=buf[:3 * b * O].view(3, b, O), loss=buf[hb_n:hb_n + 1],
                            marker=torch.empty((b, O), device=dev, dtype=torch.float32))
@@ -562,17 +588,13 @@ class _ZeroPool:
         self.off = 0
         self.in_backward = False
 
-    @staticmethod
-    def _round(n):
-        return (n + 3) // 4 * 4   # slices stay 16-byte aligned
-
     def announce(self, n):
         if self.in_backward:      # a new step's forward: the previous pass is over
             self.in_backward, self.pending, self.chunk = False, 0, None
-        self.pending += self._round(n)
+        self.pending += _round4(n)
 
     def take(self, n, device):
-        n = self._round(n)
+        n = _round4(n)
         cap = device.type == 'cuda' and torch.cuda.is_current_stream_capturing()
         if self.chunk is not None and getattr(self, 'captured', cap) != cap:
             self.chunk, self.in_backward = None, False      # allocated inside / outside a capture that is over
@@ -615,7 +637,7 @@ class _FwdStatPool:
 
     def take(self, M):
         """-> zero-filled view of STAT_SHARDS * M * 2 floats (the interface conv_bn_fwd expects of `stats`)."""
-        n = (K.STAT_SHARDS * M * 2 + 3) // 4 * 4
+        n = _round4(K.STAT_SHARDS * M * 2)
         dev = self.device
         cap = dev.type == 'cuda' and torch.cuda.is_current_stream_capturing()
         if self.open and getattr(self, 'captured', cap) != cap:
@@ -645,6 +667,66 @@ def reset_pools():
 FUSE_STANDALONE_BN = K.FUSE_BN_FINALIZE
 
 
+# activation -> (forward wrapper, backward wrapper, divisor of the output channels: GLU halves them).  NAMES, looked up in
+# bmnas.lib when the launch is issued: lib.profile_begin swaps those module attributes for timed wrappers, which function
+# objects bound here at import would bypass
+_ACTS = {'glu': ('bn_glu_fwd', 'bn_glu_bwd', 2), 'relu': ('bn_relu_fwd', 'bn_relu_bwd', 1),
+         'mish': ('bn_mish_fwd', 'bn_mish_bwd', 1)}
+
+
+def _conv_bn_front(srcs, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, training, momentum):
+    """The front end of every conv + BatchNorm forward: contiguous fp32 sources, W viewed as (M, K_in), the conv GEMM with
+    its batch statistics -> (srcs, U, chan, sv)."""
+    srcs = [_c(_f32(s)) for s in srcs]
+    C_src = srcs[0].shape[1]
+    M = conv_w.shape[0]
+    K_in = len(srcs) * C_src
+    pool = None
+    if training and FUSE_STANDALONE_BN:
+        pool = FWD_STAT_POOL             # statistics finalised inside the consumer launch (no bn_finalize launch)
+        pool.device = srcs[0].device
+    U, chan, sv = K.conv_bn_fwd(srcs, C_src, _c(conv_w).view(M, K_in), K_in, _c(conv_b), _c(bn_w), _c(bn_b), rm, rv, nbt,
+                                training, stats=pool, momentum=momentum)
+    return srcs, U, chan, sv
+
+
+def _take_conv_grads(sv):
+    """(bn_grad, dW, dbias) of the conv saved in sv: ONE zero-filled buffer for the three gradients that are accumulated
+    with atomics, carved out of one fill per backward pass (_ZeroPool)."""
+    return conv_grad_split(ZERO_POOL.take(conv_grad_floats(sv.M, sv.ldw), sv.U.device), sv.M, sv.ldw)
+
+
+def _conv_bn_act_bwd(ctx, g, g_thru=()):
+    """The backward of ConvBnActFn and — g_thru: the gradients that arrived for the handed-back sources — of
+    ConvBnActThruFn."""
+    sv = ctx.sv
+    U = sv.U
+    b, M, L = U.shape
+    _, bwd, div = _ACTS[ctx.act]
+    g = _c(g)
+    dV = torch.empty_like(U)
+    bn_grad, dW, dbias = _take_conv_grads(sv)
+    getattr(lib, bwd)(g, U, sv.chan, dV, bn_grad, b, M // div, L, ctx.drop)
+    arrived = [g_thru[q] if q < len(g_thru) else None for q in range(len(sv.srcs))]
+    slots = []
+    for q, (s, gt) in enumerate(zip(sv.srcs, arrived)):
+        if not ctx.needs_input_grad[11 + q]:
+            slots.append(None)
+            continue
+        slot = K.GradSlot(s)
+        if gt is not None and gt.is_contiguous() and gt.dtype == torch.float32:
+            slot.t, slot.written = gt, True          # the later readers' gradient: accumulated onto, in place
+        slots.append(slot)
+    K.conv_bn_bwd(sv, dV, bn_grad, slots, dW, dbias)
+    dsrcs = []
+    for slot, gt in zip(slots, arrived):
+        d = slot.get() if slot is not None else None
+        if slot is not None and gt is not None and d is not gt:
+            d = gt if d is None else d + gt          # (a non-contiguous arrival: the engine's way)
+        dsrcs.append(d)
+    return (None, None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:], *dsrcs)
+
+
 class ConvBnActFn(Function):
     """cat(srcs) -> Conv1d(k=1) -> BatchNorm1d -> glu(dim=1) | relu | mish -> Dropout(p).
     LinearGLU (node_operations.py:30-39), ConcatFC (:49-56), CatConvMish (:74-82), NodeCell out_conv
@@ -653,57 +735,22 @@ class ConvBnActFn(Function):
     @staticmethod
     def forward(ctx, act, p, training, rm, rv, nbt, momentum, conv_w, conv_b, bn_w, bn_b, *srcs):
         _require_gpu(srcs[0], 'conv1x1 + BatchNorm')
-        if act not in ('glu', 'relu', 'mish'):               # before anything is launched or a buffer is updated
+        if act not in _ACTS:                                 # before anything is launched or a buffer is updated
             raise ValueError(f'conv1x1 + BatchNorm: no kernel for the activation {act!r}')
-        srcs = [_c(_f32(s)) for s in srcs]
-        b, C_src, L = srcs[0].shape
-        M = conv_w.shape[0]
-        K_in = len(srcs) * C_src
-        W = _c(conv_w).view(M, K_in)
-        pool = None
-        if training and FUSE_STANDALONE_BN:
-            pool = FWD_STAT_POOL             # statistics finalised inside bn_relu_fwd / bn_glu_fwd (no bn_finalize launch)
-            pool.device = srcs[0].device
-        U, chan, sv = K.conv_bn_fwd(srcs, C_src, W, K_in, _c(conv_b), _c(bn_w), _c(bn_b), rm, rv, nbt,
-                                    training, stats=pool, momentum=momentum)
-        if act == 'glu':
-            Cout = M // 2
-            out = torch.empty((b, Cout, L), device=U.device, dtype=torch.float32)
-            drop = K.DROP.make(p, out.numel(), training)
-            lib.bn_glu_fwd(U, chan, out, b, Cout, L, drop, sv.fin)
-        else:
-            out = torch.empty((b, M, L), device=U.device, dtype=torch.float32)
-            drop = K.DROP.make(p, out.numel(), training)
-            (lib.bn_mish_fwd if act == 'mish' else lib.bn_relu_fwd)(U, chan, out, b, M, L, drop, sv.fin)
+        fwd, _, div = _ACTS[act]
+        srcs, U, chan, sv = _conv_bn_front(srcs, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, training, momentum)
+        b, M, L = U.shape
+        out = torch.empty((b, M // div, L), device=U.device, dtype=torch.float32)
+        drop = K.DROP.make(p, out.numel(), training)
+        getattr(lib, fwd)(U, chan, out, b, M // div, L, drop, sv.fin)
         ctx.act, ctx.sv, ctx.drop, ctx.wshape = act, sv, drop, tuple(conv_w.shape)
         if any(ctx.needs_input_grad):
-            ZERO_POOL.announce(2 * M + M * sv.ldw + M)
+            ZERO_POOL.announce(conv_grad_floats(M, sv.ldw))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        sv, act = ctx.sv, ctx.act
-        U = sv.U
-        b, M, L = U.shape
-        g = _c(g)
-        dV = torch.empty_like(U)
-        # ONE zero-filled buffer for the three gradients that are accumulated with atomics, carved out of
-        # one fill per backward pass (_ZeroPool)
-        zero = ZERO_POOL.take(2 * M + M * sv.ldw + M, U.device)
-        bn_grad = zero[:2 * M]
-        dW = zero[2 * M:2 * M + M * sv.ldw].view(M, sv.ldw)
-        dbias = zero[2 * M + M * sv.ldw:]
-        if act == 'glu':
-            lib.bn_glu_bwd(g, U, sv.chan, dV, bn_grad, b, M // 2, L, ctx.drop)
-        elif act == 'mish':
-            lib.bn_mish_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
-        else:
-            lib.bn_relu_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
-        slots = [K.GradSlot(s) if ctx.needs_input_grad[11 + q] else None for q, s in enumerate(sv.srcs)]
-        K.conv_bn_bwd(sv, dV, bn_grad, slots, dW, dbias)
-        dsrcs = [s.get() if s is not None else None for s in slots]
-        return (None, None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:],
-                *dsrcs)
+        return _conv_bn_act_bwd(ctx, g)
 
 
 class ConvBnActThruFn(Function):
@@ -723,44 +770,9 @@ class ConvBnActThruFn(Function):
 
     @staticmethod
     def backward(ctx, g, *g_thru):
-        sv, act = ctx.sv, ctx.act
-        n = len(sv.srcs)
         if g is None:                       # only the handed-back sources were differentiated: identity
             return (None,) * 11 + tuple(g_thru)
-        U = sv.U
-        b, M, L = U.shape
-        g = _c(g)
-        dV = torch.empty_like(U)
-        zero = ZERO_POOL.take(2 * M + M * sv.ldw + M, U.device)
-        bn_grad = zero[:2 * M]
-        dW = zero[2 * M:2 * M + M * sv.ldw].view(M, sv.ldw)
-        dbias = zero[2 * M + M * sv.ldw:]
-        if act == 'glu':
-            lib.bn_glu_bwd(g, U, sv.chan, dV, bn_grad, b, M // 2, L, ctx.drop)
-        elif act == 'mish':
-            lib.bn_mish_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
-        else:
-            lib.bn_relu_bwd(g, U, sv.chan, dV, bn_grad, b, M, L, ctx.drop)
-        slots = []
-        for q, s in enumerate(sv.srcs):
-            gt = g_thru[q] if q < len(g_thru) else None
-            if not ctx.needs_input_grad[11 + q]:
-                slots.append(None)
-                continue
-            slot = K.GradSlot(s)
-            if gt is not None and gt.is_contiguous() and gt.dtype == torch.float32:
-                slot.t, slot.written = gt, True          # the later readers' gradient: accumulated onto, in place
-            slots.append(slot)
-        K.conv_bn_bwd(sv, dV, bn_grad, slots, dW, dbias)
-        dsrcs = []
-        for q, slot in enumerate(slots):
-            gt = g_thru[q] if q < len(g_thru) else None
-            d = slot.get() if slot is not None else None
-            if slot is not None and gt is not None and d is not gt:
-                d = gt if d is None else d + gt          # (a non-contiguous arrival: the engine's way)
-            dsrcs.append(d)
-        return (None, None, None, None, None, None, None, dW.view(ctx.wshape), dbias, bn_grad[:M], bn_grad[M:],
-                *dsrcs)
+        return _conv_bn_act_bwd(ctx, g, g_thru)
 
 
 class ConvBnReluLnFn(Function):
@@ -778,18 +790,9 @@ class ConvBnReluLnFn(Function):
     @staticmethod
     def forward(ctx, p, training, want_sums, rm, rv, nbt, momentum, conv_w, conv_b, bn_w, bn_b, ln_w, ln_b, x, *srcs):
         _require_gpu(srcs[0], 'conv1x1 + BatchNorm + LayerNorm tail')
-        srcs = [_c(_f32(s)) for s in srcs]
         x = _c(_f32(x))
-        b, C_src, L = srcs[0].shape
-        M = conv_w.shape[0]
-        K_in = len(srcs) * C_src
-        W = _c(conv_w).view(M, K_in)
-        pool = None
-        if training and FUSE_STANDALONE_BN:
-            pool = FWD_STAT_POOL
-            pool.device = srcs[0].device
-        U, chan, sv = K.conv_bn_fwd(srcs, C_src, W, K_in, _c(conv_b), _c(bn_w), _c(bn_b), rm, rv, nbt,
-                                    training, stats=pool, momentum=momentum)
+        srcs, U, chan, sv = _conv_bn_front(srcs, conv_w, conv_b, bn_w, bn_b, rm, rv, nbt, training, momentum)
+        b, M, L = U.shape
         o = torch.empty_like(x)                  # dropout(relu(bn(U))), saved for the backward
         out = torch.empty_like(x)
         stats = torch.empty(b * 2, device=x.device, dtype=torch.float32)
@@ -800,7 +803,7 @@ class ConvBnReluLnFn(Function):
         ctx.sv, ctx.drop, ctx.wshape, ctx.x, ctx.o, ctx.stats, ctx.lw, ctx.lb = sv, drop, tuple(conv_w.shape), x, o, stats, lw, lb
         ctx.leaf = ln_w.is_leaf and ln_b.is_leaf
         if any(ctx.needs_input_grad):
-            ZERO_POOL.announce(2 * M + M * sv.ldw + M)
+            ZERO_POOL.announce(conv_grad_floats(M, sv.ldw))
             ZERO_POOL.announce(2 * lw.numel())
         ctx.mark_non_differentiable(sums)
         ctx.set_materialize_grads(False)
@@ -816,10 +819,7 @@ class ConvBnReluLnFn(Function):
         b, M, L = U.shape
         g = _c(g)
         dV = torch.empty_like(U)
-        zero = ZERO_POOL.take(2 * M + M * sv.ldw + M, U.device)
-        bn_grad = zero[:2 * M]
-        dW = zero[2 * M:2 * M + M * sv.ldw].view(M, sv.ldw)
-        dbias = zero[2 * M + M * sv.ldw:]
+        bn_grad, dW, dbias = _take_conv_grads(sv)
         dx = torch.empty_like(x) if ctx.needs_input_grad[13] else None
         dlw, dlb = _zero_pair(ctx.lw)
         # LayerNorm input gradient, ReLU / dropout mask, BatchNorm reductions and the residual's gradient: one launch
@@ -900,10 +900,7 @@ class ReshapeGroupFn(Function):
         # of the step, in front of every dropout site (bmnas.cell._DropState.take_advance)
         per = K.STAT_SHARDS * M * 2 if training else 0
         want_bwd = any(ctx.needs_input_grad)              # (all False when autograd is not recording)
-        sizes = [2 * M + M * W.shape[1] + M for W in Ws] if want_bwd else []
-        offs = [n * per]
-        for sz in sizes:
-            offs.append(offs[-1] + (sz + 3) // 4 * 4)
+        offs = conv_grad_offsets(M, [W.shape[1] for W in Ws] if want_bwd else [], base=n * per)
         adv = K.DROP.take_advance() if (training and p > 0.0) else None
         pool = torch.empty(offs[-1], device=dev, dtype=torch.float32) if offs[-1] else None
         if pool is not None or adv is not None:
@@ -911,7 +908,7 @@ class ReshapeGroupFn(Function):
         if training:
             shards = K.STAT_SHARDS
             stats = [pool[i * per:(i + 1) * per] for i in range(n)]
-        ctx.zero = (pool, offs, sizes) if want_bwd else None
+        ctx.zero = (pool, offs) if want_bwd else None
         lib.conv1x1_fwd_group(xs, Ws, cbs, Us, stats, shards, b, L, M)
         outs = [torch.empty((b, M, L), device=dev, dtype=torch.float32) for _ in range(n)]
         drops = [K.DROP.make(p, outs[i].numel(), training) for i in range(n)]
@@ -933,18 +930,14 @@ class ReshapeGroupFn(Function):
         gs = [torch.zeros_like(Us[i]) if g is None else _c(g) for i, g in enumerate(gs)]
         # bn_grad | dW | dbias of every layer: the buffer the forward's first launch cleared (a second backward
         # over the same graph gets a fresh one)
+        ldws = [W.shape[1] for W in Ws]
         if ctx.zero is not None:
-            zero, offs, sizes = ctx.zero
+            zero, offs = ctx.zero
             ctx.zero = None
         else:
-            sizes = [2 * M + M * W.shape[1] + M for W in Ws]
-            offs = [0]
-            for sz in sizes:
-                offs.append(offs[-1] + (sz + 3) // 4 * 4)
+            offs = conv_grad_offsets(M, ldws)
             zero = torch.zeros(offs[-1], device=dev, dtype=torch.float32)
-        bn_grads = [zero[offs[i]:offs[i] + 2 * M] for i in range(n)]
-        dWs = [zero[offs[i] + 2 * M:offs[i] + 2 * M + M * Ws[i].shape[1]].view(M, Ws[i].shape[1]) for i in range(n)]
-        dbs = [zero[offs[i] + 2 * M + M * Ws[i].shape[1]:offs[i] + sizes[i]] for i in range(n)]
+        bn_grads, dWs, dbs = map(list, zip(*[conv_grad_split(zero, M, ldw, off) for ldw, off in zip(ldws, offs)]))
         dVs = [torch.empty_like(U) for U in Us]
         lib.bn_relu_bwd_group(gs, Us, ctx.chans, dVs, bn_grads, ctx.drops, b, M, L)
         dxs = [torch.empty_like(x) if ctx.needs_input_grad[4 + i] else None for i, x in enumerate(xs)]
@@ -1024,7 +1017,7 @@ class FcEdgeSumFn(Function):
         b, Cc, L = g.shape
         dev = g.device
         per = 2 * Cc + Cc * Cc + Cc                    # bn_grad | dW | dbias of one (edge, FC primitive)
-        head = (n * P + 3) // 4 * 4
+        head = _round4(n * P)
         pool = torch.empty(head + n * F * per, device=dev, dtype=torch.float32)
         lib.fc_edges_zero(pool, 'bwd')
         dw = pool[:n * P].view(n, P)
@@ -1143,39 +1136,48 @@ class FoundFcEdgesFn(Function):
 
 
 # ---------------------------------------------------------------- search NodeMixedOp
+def _node_mixed_fwd(ctx, fwd, op, training, x, y, gamma_row):
+    """The shared forward of NodeMixedFn / NodeMixedSelFn: x and y contiguous fp32 (ONE object when x is y), the op's
+    parameter pack, the launch sequence `fwd`."""
+    _require_gpu(x, 'NodeMixedOp')
+    same = x is y
+    x = _c(_f32(x))
+    y = x if same else _c(_f32(y))
+    out, sv = fwd(x, y, _c(gamma_row), op.pack(), training)
+    ctx.op, ctx.sv = op, sv
+    return out
+
+
+def _node_mixed_bwd(ctx, bwd, g, dgamma, G):
+    """The shared backward: the input-gradient slots, the launch sequence `bwd`, the attention addend
+    -> (dx, dy — None when x is y —, parameter gradients)."""
+    sv = ctx.sv
+    xs = K.GradSlot(sv.x)
+    ys = None if sv.same else K.GradSlot(sv.y)
+    bwd(sv, _c(g), dgamma, xs, ys, G)
+    dx = xs.get()
+    if xs.extra is not None:                 # attention part produced next to the GEMM
+        dx = dx.add_(xs.extra) if dx is not None else xs.extra
+    return dx, (None if sv.same else ys.get()), ctx.op.grads_in_param_order(G)
+
+
 class NodeMixedFn(Function):
     """NodeMixedOp.forward(x, y, weights) (node_operations.py:118-120) as one fused
     sequence (attention+LN, stacked conv GEMM + BN statistics, gamma-mix)."""
 
     @staticmethod
     def forward(ctx, op, training, x, y, gamma_row, *params):
-        _require_gpu(x, 'NodeMixedOp')
-        same = x is y
-        x = _c(_f32(x))
-        y = x if same else _c(_f32(y))
-        P = op.pack()
-        out, sv = K.node_mixed_fwd(x, y, _c(gamma_row), P, training)
-        ctx.op, ctx.sv = op, sv
-        return out
+        return _node_mixed_fwd(ctx, K.node_mixed_fwd, op, training, x, y, gamma_row)
 
     @staticmethod
     def backward(ctx, g):
-        sv, op = ctx.sv, ctx.op
-        x = sv.x
-        G = op.grad_pack(x.device)
-        dgamma = torch.zeros(4, device=x.device, dtype=torch.float32)
-        xs = K.GradSlot(x)
-        ys = None if sv.same else K.GradSlot(sv.y)
-        K.node_mixed_bwd(sv, _c(g), dgamma, xs, ys, G)
-        dx = xs.get()
-        if xs.extra is not None:                 # attention part produced next to the GEMM
-            dx = dx.add_(xs.extra)
-        if sv.same:
-            # x and y are the same tensor object: autograd adds both returned halves
-            dx_half, dy = dx, torch.zeros_like(dx)
-        else:
-            dx_half, dy = dx, ys.get()
-        return (None, None, dx_half, dy, dgamma, *op.grads_in_param_order(G))
+        dev = ctx.sv.x.device
+        G = ctx.op.grad_pack(dev)
+        dgamma = torch.zeros(4, device=dev, dtype=torch.float32)
+        dx, dy, pgrads = _node_mixed_bwd(ctx, K.node_mixed_bwd, g, dgamma, G)
+        if ctx.sv.same:
+            dy = torch.zeros_like(dx)            # x and y are the same tensor object: autograd adds both returned halves
+        return (None, None, dx, dy, dgamma, *pgrads)
 
 
 class NodeMixedSelFn(Function):
@@ -1185,35 +1187,20 @@ class NodeMixedSelFn(Function):
 
     @staticmethod
     def forward(ctx, op, training, x, y, gamma_row, *params):
-        _require_gpu(x, 'NodeMixedOp')
-        same = x is y
-        x = _c(_f32(x))
-        y = x if same else _c(_f32(y))
-        P = op.pack()
-        out, sv = K.node_mixed_sel_fwd(x, y, _c(_f32(gamma_row)), P, training)
-        ctx.op, ctx.sv = op, sv
-        return out
+        return _node_mixed_fwd(ctx, K.node_mixed_sel_fwd, op, training, x, y, _f32(gamma_row))
 
     @staticmethod
     def backward(ctx, g):
-        sv, op = ctx.sv, ctx.op
-        x = sv.x
+        op = ctx.op
         # ONE zero fill for everything the launches accumulate into with atomics, dgamma included
         arena = K.Arena()
         h = op.plan_grads(arena)
         hg = arena.ask(len(op._prims))
-        arena.alloc(x.device)
-        G = op.bind_grads(arena, h)
+        arena.alloc(ctx.sv.x.device)
         dgamma = arena.view(hg)
-        xs = K.GradSlot(x)
-        ys = None if sv.same else K.GradSlot(sv.y)
-        K.node_mixed_sel_bwd(sv, _c(g), dgamma, xs, ys, G)
-        dx = xs.get()
-        if xs.extra is not None:                 # attention part produced next to the GEMM
-            dx = dx.add_(xs.extra) if dx is not None else xs.extra
         # x is y: the one tensor's whole gradient is returned for x (autograd skips the None)
-        dy = None if sv.same else ys.get()
-        return (None, None, dx, dy, dgamma, *op.grads_in_param_order(G))
+        dx, dy, pgrads = _node_mixed_bwd(ctx, K.node_mixed_sel_bwd, g, dgamma, op.bind_grads(arena, h))
+        return (None, None, dx, dy, dgamma, *pgrads)
 
 
 # -------------------------------------------------------------------- fused FusionCell
@@ -1254,7 +1241,7 @@ class FusedCellFn(Function):
         if n_head:
             Wc, bc = _c(_f32(tensors[-2])), _c(_f32(tensors[-1]))
             O = Wc.shape[0]
-            hb_n = (3 * b * O + 3) // 4 * 4
+            hb_n = _round4(3 * b * O)
             head_n = hb_n + 4
         arena = torch.empty(stat_n + head_n, device=dev, dtype=torch.float32) if stat_n + head_n else None
         stats = K.StatArena(xs[0], counts, arena[:stat_n]) if stat_n else None
@@ -1362,7 +1349,7 @@ class LinearFn(Function):
         O = W.shape[0]
         # the k-slices add into `out`: zero-filled by the captured step's arena where there is one (no fill launch)
         if _ARENA_NEED is not None:
-            _ARENA_NEED[0] += (b * O + 3) // 4 * 4
+            _ARENA_NEED[0] += _round4(b * O)
         pre = _ARENA.take(b * O) if (_ARENA is not None and _ARENA.buf.device == feat.device) else None
         out = pre.view(b, O) if pre is not None else torch.empty((b, O), device=feat.device, dtype=torch.float32)
         lib.linear_fwd(feat, W, bias, out, b, O, Kd, out_is_zero=pre is not None)
